@@ -2,9 +2,13 @@
 """Benchmark of the hot path: sphere-tracing depth render forward + backward.
 
 Metric (BASELINE.json): depth renders/sec fwd+bwd, 640x480 @ 64^3 SDF; grad max-abs-err vs ref.
-The line carries both halves: `value` (renders/s) and `grad_max_abs_err` (d/dSDF, + the `grad_*` keys beside it and
-`parity`), the errors of the benchmarked build's last step against the oracle.  After the headline it appends BASELINE.json's
-other single-GPU configurations (`configs`: C1, C2 with the CPU port beside them, C5 with its time to result, C3_l1).
+A plain run measures the headline only: set-up, pre-warm and warm-up, the K timed steps, and one result line with
+`value` (renders/s), `ms_per_step` and the roofline read from the timed steps' own events.  `--full` adds everything
+else, after the headline: the other half of the metric, `grad_max_abs_err` (d/dSDF, + the `grad_*` keys beside it and
+`parity`: the errors of the benchmarked build's last step against the oracle), the CPU port (`cpu_baseline`), GPU clock
+telemetry, BASELINE.json's other single-GPU configurations (`configs`: C1, C2 with the CPU port beside them, C5 with
+its time to result, C3_l1), and for N > 1 the other exchange and the multi-rank extras.
+`--dump-outputs DIR` writes what the last timed step returned to its caller as float32 .npy files (`dump_outputs`).
 
 Workload per GPU ("C3", BASELINE.json configs[2]): 256 seeded random
 poses of the synthetic blobs(0) 64^3 SDF at 640x480, threshold 0.005, upstream gradient
@@ -15,7 +19,7 @@ reported, `value` is the one asked for).  N GPUs = N shards of 256 views of one
 256*N-view batch (configs[3] at N=8), so scaling is weak.  Everything is resident in HBM
 before the timed region.  `--batch 1` gives configs[1] (one view per launch).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]      (N > 1: spawns its own N ranks)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]   (N > 1: spawns its own N ranks)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 """
 import argparse
@@ -42,9 +46,17 @@ def parse():
     ap.add_argument("--batch", type=int, default=256, help="views per GPU per step")
     ap.add_argument("--width", type=int, default=640)
     ap.add_argument("--height", type=int, default=480)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true", help="skip the gradient-error report against the oracle")
-    ap.add_argument("--no-configs", action="store_true", help="skip the C1 / C2 / C5 / C3_l1 side measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure and check everything else: gradient errors against the "
+                         "oracle, the CPU port, GPU clock telemetry, the C1 / C2 / C5 / C3_l1 side measurements, and "
+                         "for N > 1 the other exchange and the multi-rank extras (off: the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (depth images: a seeded sample of whole views; "
+                         "d/dSDF and the pose gradients) to DIR/<name>.npy, float32, rank 0")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU port")
+    ap.add_argument("--no-parity", action="store_true",
+                    help="with --full: skip the gradient-error report against the oracle")
+    ap.add_argument("--no-configs", action="store_true", help="with --full: skip the C1 / C2 / C5 / C3_l1 side measurements")
     ap.add_argument("--prewarm-ms", type=float, default=300.0,
                     help="untimed steps before the warm-up steps until this much wall time has passed (clock ramp)")
     ap.add_argument("--cpu-sample", type=int, default=0, help="views in the CPU sample (0 = auto)")
@@ -52,7 +64,7 @@ def parse():
                     help="N > 1: which exchange of d/dSDF `value` is measured with.  ring: one all-reduce of M/2 "
                          "volumes per M/2 steps, waited for when the ring wraps (independent steps); sync: every "
                          "step's volume is summed before the next forward starts (the dependency of "
-                         "render-and-compare).  The other one is measured too and reported beside it.")
+                         "render-and-compare).  With --full the other one is measured too and reported beside it.")
     ap.add_argument("--watchdog-s", type=float, default=0.0,
                     help="N > 1: a rank that has not come out of process-group start-up / its first collective after "
                          "this many seconds reports its stage and exits non-zero (default 0 = 120 s + 15 s per rank: "
@@ -117,6 +129,31 @@ def synthetic_inputs(B_total, rank, B, W, H, device):
     gen.manual_seed(1234 + rank)
     g = torch.rand((B, H, W), device=device, generator=gen) * 2 - 1
     return sdf, (pos[sl], quat[sl], isc[sl]), t(sdf), t(pos[sl]), t(quat[sl]), t(isc[sl]), g
+
+
+DUMP_DEPTH_BYTES = 48 * 2 ** 20     # the depth sample; with the gradients a dump stays below 64 MB
+
+
+def dump_outputs(out_dir, plan):
+    """What the last step handed its caller -- the forward's depth images and the backward's (d/dSDF, d/dposition,
+    d/dquaternion, d/dinverse-scale) -- as float32 `out_dir/<name>.npy`.  The B depth images of a default step are
+    315 MB, so `depth_sample.npy` holds as many whole views as fit in DUMP_DEPTH_BYTES, chosen by a generator seeded
+    with 0 and kept in view order (all B when they fit; a view larger than the budget is itself sampled by pixel,
+    same generator).  The choice depends on the shapes only: two builds given the same arguments dump the same views."""
+    os.makedirs(out_dir, exist_ok=True)
+    B, H, W = plan.depth.shape
+    rng = np.random.default_rng(0)
+    per_view = H * W * 4
+    views = np.sort(rng.choice(B, min(B, max(1, DUMP_DEPTH_BYTES // per_view)), replace=False))
+    depth = plan.depth[torch.as_tensor(views, device=plan.depth.device)]
+    if per_view > DUMP_DEPTH_BYTES:
+        pix = np.sort(rng.choice(H * W, DUMP_DEPTH_BYTES // 4, replace=False))
+        depth = depth.reshape(len(views), H * W)[:, torch.as_tensor(pix, device=depth.device)]
+    out = {"depth_sample": depth, "grad_sdf": plan.g_sdf, "grad_position": plan.g_pos, "grad_quaternion": plan.g_quat,
+           "grad_inv_scale": plan.g_inv_scale}
+    for name, t in out.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), t.detach().to(torch.float32).cpu().numpy())
+    return sorted(out)
 
 
 def _time_oracle(lib, sdf, pos, quat, isc, W, H, thr, threads, budget_cpu_s):
@@ -444,8 +481,9 @@ def main():
     from sdfest_amd import BatchRenderPlan, Camera
     from tools.bench_extra import Telemetry, extra_configs, parity_report
 
-    tele = Telemetry(local_rank)
-    tele.start()
+    tele = Telemetry(local_rank) if args.full else None
+    if tele:
+        tele.start()
     W, H, B, thr = args.width, args.height, args.batch, 0.005
     sdf_np, poses_np, sdf, pos, quat, isc, g = synthetic_inputs(B * N, rank, B, W, H, device)
     cam = Camera(W, H, W / 2.0, W / 2.0, W / 2.0, H / 2.0, pixel_center=0.5)
@@ -597,7 +635,7 @@ def main():
                     step()
                 torch.cuda.synchronize()
         barrier()
-        if mark:
+        if mark and tele:
             tele.mark("t0")      # (also reads the clocks here, just outside the timed region)
         t0 = time.perf_counter()
         for k in range(args.steps):
@@ -605,7 +643,7 @@ def main():
         t_issue = time.perf_counter() - t0
         barrier()
         el = time.perf_counter() - t0
-        if mark:
+        if mark and tele:
             tele.mark("t1")
         if use_dist:
             tt = torch.tensor([el], device=device, dtype=torch.float64)
@@ -618,14 +656,16 @@ def main():
     # (t_enqueued: host time to issue the K steps -- GPU-bound if below `elapsed`)
     elapsed, t_enqueued = timed(main_mode, events, time_collective=True, mark=True)
     events = [e for e in events if e is not None]
-    # the other exchange, K steps of its own after the headline's region (N > 1 only)
+    dumped = dump_outputs(args.dump_outputs, plan) if args.dump_outputs and rank == 0 else None
+    # the other exchange, K steps of its own after the headline's region (N > 1, --full only)
     elapsed_other = None
-    if use_dist:
+    if use_dist and args.full:
         other_mode = "sync" if main_mode == "ring" else "ring"
         elapsed_other, _ = timed(other_mode, None, time_collective=True)
         state["mode"] = main_mode
-    time.sleep(0.005)
-    tele.stop()
+    if tele:
+        time.sleep(0.005)
+        tele.stop()
     def plain_barrier():
         if use_dist:
             dist.barrier()
@@ -738,16 +778,20 @@ def main():
             "prewarm": {"untimed_steps": n_pre, "ms": round(prewarm_ms, 1),
                         "why": "clock ramp: the timed region follows >= --prewarm-ms of the same steps"},
             "prologue_fallbacks_in_timed_region": fallbacks,
-            "gpu_telemetry": tele.summary("t0", "t1"),
         }
+        if tele:
+            line["gpu_telemetry"] = tele.summary("t0", "t1")
+        if dumped:
+            line["outputs_dumped"] = {"dir": args.dump_outputs, "files": [f"{n}.npy" for n in dumped]}
         if collective:
             line["collective"] = collective
+        if collective and elapsed_other is not None:
             v_other = views / elapsed_other
             line["value_ring_exchange"] = round(value if main_mode == "ring" else v_other, 1)
             line["value_sync_exchange"] = round(value if main_mode == "sync" else v_other, 1)
             line["ms_per_step_sync_exchange"] = round((elapsed if main_mode == "sync" else elapsed_other)
                                                       / args.steps * 1e3, 4)
-        if N == 1 and not args.no_parity:
+        if N == 1 and args.full and not args.no_parity:
             # the other half of the metric: errors of the benchmarked build's last step against the reference
             # semantics (sdf_renderer_cuda.cu:334-467, simple_renderer.py:317-458) through the pinned oracle
             par = parity_report(plan, g, sdf, (pos, quat, isc), sdf_np, poses_np, W, H, thr)
@@ -762,18 +806,18 @@ def main():
             line["grad_pose_max_abs_err_benchmark_upstream"] = par["grad_pose_benchmark_upstream"]["max_abs_err"]
             line["grad_pose_max_err_over_sum_of_term_magnitudes"] = \
                 par["grad_pose_benchmark_upstream"]["max_err_over_sum_of_term_magnitudes"]
-        if N == 1 and not args.no_cpu_baseline:
+        if N == 1 and args.full and not args.no_cpu_baseline:
             sample = args.cpu_sample or min(B, 256)
             line["cpu_baseline"] = cpu_baseline(sdf_np, poses_np, W, H, thr, sample)
             line["speedup_vs_cpu"] = round(value / line["cpu_baseline"]["value"], 1)
-        if N == 1 and not args.no_configs:
+        if N == 1 and args.full and not args.no_configs:
             del plan
             torch.cuda.empty_cache()
             line["configs"] = extra_configs(sdf_np, device, HBM_PEAK)
     line = line if rank == 0 else {}
     # the extras of a multi-rank run, AFTER the headline is complete and each under its own guard (every rank enters;
     # only rank 0's line matters): the sharded loop between graphs, then (opt-in) with its all-reduce inside the graphs
-    extras = use_dist and (N > 1 or os.environ.get("SDFR_BENCH_LOOP_SHARDED") == "1")
+    extras = args.full and use_dist and (N > 1 or os.environ.get("SDFR_BENCH_LOOP_SHARDED") == "1")
     if extras and rank == 0:
         # The finished measurement goes out NOW: a native abort inside an extra -- a fault in a collective, the
         # process group's watchdog, the job watchdog -- kills the process without a word, and the guards above only

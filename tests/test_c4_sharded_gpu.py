@@ -148,7 +148,7 @@ def test_bench_py_with_two_ranks_in_rehearsal_mode(tmp_path, exchange):
     env = dict(os.environ, SDFR_BENCH_SHARE_GPU="1", SDFR_BENCH_BACKEND="gloo", SDFR_BENCH_GRAD_VOLUMES="4")
     res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "1",
                           "--batch", "24", "--width", "320", "--height", "240", "--prewarm-ms", "0",
-                          "--exchange", exchange],
+                          "--exchange", exchange, "--full"],
                          capture_output=True, text=True, timeout=600, env=env)
     assert res.returncode == 0, res.stderr[-2000:]
     assert "stage: init_process_group" in res.stderr and "WATCHDOG" not in res.stderr
@@ -193,7 +193,7 @@ def test_bench_py_with_five_ranks_in_rehearsal_mode():
     root = os.path.dirname(HERE)
     env = dict(os.environ, SDFR_BENCH_SHARE_GPU="1", SDFR_BENCH_BACKEND="gloo", SDFR_BENCH_GRAD_VOLUMES="4")
     res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "5", "--steps", "3", "--warmup", "1",
-                          "--batch", "8", "--width", "160", "--height", "120", "--prewarm-ms", "0"],
+                          "--batch", "8", "--width", "160", "--height", "120", "--prewarm-ms", "0", "--full"],
                          capture_output=True, text=True, timeout=900, env=env)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
