@@ -38,11 +38,11 @@
  *   (sdf_view_stride = R*R*R elements).
  *
  * STABILITY -- group 1 below is the boundary: its signatures and semantics are what a binding relies on and do not change
- * without SDFR_VERSION's major number changing.  Groups 2 - 4 are UNSTABLE: they exist for this repository's own host
+ * without SDFR_VERSION's major number changing.  Groups 2 - 5 are UNSTABLE: they exist for this repository's own host
  * code (the Python modules under sdfest_amd/), follow its needs from round to round (arguments were added in every round so far), and are
  * exported only because that host code is Python over ctypes; bind to them at your own risk, pinned to one SDFR_VERSION.
  *
- * CONTENTS -- four groups; a binding from another language needs group 1 only
+ * CONTENTS -- five groups; a binding from another language needs group 1 only
  *   1. CORE: the reference boundary (what sdf_renderer_cpp, losses.pc_loss and SDFDecoder.forward are replaced by)
  *        sdfr_version, sdfr_last_error
  *        sdfr_render_forward[_workspace_bytes], sdfr_render_backward[_workspace_bytes]
@@ -67,6 +67,8 @@
  *   4. [unstable] GENERATOR / INITIALISATION (the forward-only callers around the loop)
  *        sdfr_affine_mask; sdfr_pointnet_layer[_counted], sdfr_linear_vec, sdfr_orientation_posterior,
  *        sdfr_init_estimate
+ *   5. [unstable] MESH: marching cubes over N grids (SDFPipeline.generate_mesh, after the estimate)
+ *        sdfr_mesh_tables, sdfr_mesh_workspace_bytes, sdfr_mesh_count, sdfr_mesh_emit
  * (Within the file the groups follow the order in which the reference's code runs; every declaration carries the
  * reference file:line it replaces.)
  */
@@ -804,6 +806,33 @@ SDFR_API int sdfr_init_estimate(const float* head, int latent, const float* grid
                        const float* centroid, const float* cam_pos, const float* cam_quat, int mean_shape,
                        int take_if_better, const float* posterior_max, float* best, float* params, int device,
                        void* stream);
+
+/* ==== 5. MESH ================================================================================= */
+/* ---- marching cubes: simple_setup.py:621-669 (generate_mesh: skimage.measure.marching_cubes) ----------------------
+ * N grids sdf [N][R][R][R] (2 <= R <= 256), each its own mesh.  complete = 1: every grid inside a virtual border of
+ * 1.0 (the reference's F.pad(sdf, (1,)*6, value=1.0); nothing is copied), side M = R + 2; else M = R.
+ *   a corner is inside iff v < level; one vertex per crossed grid edge, shared by its triangles (a welded mesh)
+ *   vertex order: grid point g = (i M + j) M + k ascending, then its edges along axis 0, 1, 2
+ *   face order:   cell (minimum corner g) ascending, then the case table's triangle order
+ *   position:     (a + t (b - a)) s - s (M - 1) / 2 per axis, t = (level - v_a) / (v_b - v_a), s = 2 / (R - 1)
+ *   winding:      (b - a) x (c - a) points toward increasing SDF
+ *   normals:      np.gradient of the (padded) grid at both edge ends, lerped by t, normalised (0 where it vanishes)
+ * Integer scans only: the same bits every run, whatever N.  Two calls with the same arguments and workspace:
+ *   sdfr_mesh_count  totals [N][4] (device int32) = {V, F, min, max} per grid (min / max of the padded volume as
+ *                    float bits: skimage raises unless min <= level <= max); the caller reads them back, then
+ *   sdfr_mesh_emit   vertices [sum V][3] float, normals [sum V][3] float (nullable), faces [sum F][3] int32 with the
+ *                    grids one after the other; face indices are local to their grid's vertices.  `totals` is the
+ *                    count's (still on the device); sdf, level, complete and the workspace are the count's too. */
+/* host copies of the case tables (no GPU needed): edge_mask[256] (bit e = edge e crossed), tri_table[256][16] (up
+ * to five edge triples, -1 terminated).  Corner c = dx + 2 dy + 4 dz; edge e = 4 a + (the other two offsets, the
+ * lower axis first) along axis a. */
+SDFR_API int sdfr_mesh_tables(unsigned short* h_edge_mask, signed char* h_tri_table);
+SDFR_API size_t sdfr_mesh_workspace_bytes(int N, int R, int complete);   /* 0 for invalid arguments */
+SDFR_API int sdfr_mesh_count(const float* sdf, int N, int R, int complete, float level, int* totals,
+                             void* workspace, size_t workspace_bytes, int device, void* stream);
+SDFR_API int sdfr_mesh_emit(const float* sdf, int N, int R, int complete, float level, const int* totals,
+                            float* vertices, float* normals, int* faces, void* workspace, size_t workspace_bytes,
+                            int device, void* stream);
 
 #ifdef __cplusplus
 }

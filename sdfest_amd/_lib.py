@@ -147,6 +147,10 @@ SIGNATURES = {
     "sdfr_affine_mask": (c_int, [c_fp, c_int, c_int, c_int, c_fp, c_fp, c_int, c_fp]),
     "sdfr_nn_loss_forward": (c_int, [c_fp, c_int, c_fp, c_int, c_fp, c_fp, c_int, c_fp]),
     "sdfr_nn_loss_backward": (c_int, [c_fp, c_fp, c_int, c_fp, c_int, c_fp, c_fp, c_fp, c_fp, c_int, c_fp]),
+    "sdfr_mesh_tables": (c_int, [c_fp, c_fp]),
+    "sdfr_mesh_workspace_bytes": (c_sz, [c_int, c_int, c_int]),
+    "sdfr_mesh_count": (c_int, [c_fp, c_int, c_int, c_int, c_f, c_fp, c_fp, c_sz, c_int, c_fp]),
+    "sdfr_mesh_emit": (c_int, [c_fp, c_int, c_int, c_int, c_f, c_fp, c_fp, c_fp, c_fp, c_fp, c_sz, c_int, c_fp]),
 }
 
 

@@ -13,17 +13,23 @@ A caller of the reference replaces ``from sdfest.estimation.simple_setup import 
                         no capture, no Python per iteration (:408-470)
     result selection    :583-596
 
+After the estimate, ``generate_mesh`` turns a latent and a scale into a mesh as the reference's does (:621-669), with
+marching cubes on the GPU (``mesh.extract_mesh``) instead of skimage + open3d; ``generate_meshes`` does the same for
+the K rows of ``estimate_objects`` in one batched decode and one launch sequence.
+
 What is NOT here (out of scope): plots (``visualize``), step logs (``log_path``), animations
-(``animation_path``), mesh export (``generate_mesh``) and weight downloads -- the first three arguments are accepted
-and ignored with a warning, weights come as state dicts or from a local file.
+(``animation_path``) and weight downloads -- the first three arguments are accepted and ignored with a warning,
+weights come as state dicts or from a local file.  ``generate_mesh`` returns ``mesh.Mesh`` (device tensors, OBJ / PLY
+writers), not an open3d ``TriangleMesh``.
 """
 import os
 import warnings
-from typing import Dict, Mapping, Optional, Tuple
+from typing import Dict, List, Mapping, Optional, Tuple
 
 import torch
 
 from .differentiable_renderer import Camera, parse_sdf_grad_mode, render_depth_gpu
+from .mesh import Mesh, extract_mesh
 from .init_network import NoDepthError, ResidentInit, SDFPoseNet, adjust_categorical_posterior, nn_init
 from .pipeline import FusedRenderAndCompare, MultiObjectRenderAndCompare, _selection_strategy, preprocess_depth
 from .vae import SDFDecoder
@@ -151,6 +157,36 @@ class SDFPipeline:
         """simple_setup.py:609-619"""
         sdf = self.vae.decode(latent)
         return self.render(sdf[0, 0], position, orientation, 1 / scale)
+
+    def generate_mesh(self, latent: torch.Tensor, scale: torch.Tensor, complete_mesh: bool = False) -> Optional[Mesh]:
+        """simple_setup.py:621-669: the mesh of latent (1,L) at relative scale (1,), without pose; None if the config
+        has no ``iso_threshold`` (the reference's ``except KeyError``).  complete_mesh: pad the SDF with 1.0 first (a
+        closed mesh).  ValueError if the level lies outside the decoded SDF's range, as skimage raises."""
+        with torch.no_grad():
+            sdf = self.vae.decode(latent)
+            try:
+                level = self.config["iso_threshold"]
+            except KeyError:
+                return None
+            mesh = extract_mesh(sdf[0, 0], level, complete=complete_mesh)
+        mesh.update_scale(float(scale.reshape(-1)[0]), rel_scale=True)
+        return mesh
+
+    def generate_meshes(self, latents: torch.Tensor, scales: torch.Tensor,
+                        complete_mesh: bool = False) -> Optional[List[Mesh]]:
+        """``generate_mesh`` for K objects at once (the rows of ``estimate_objects``): latents (K,L), scales (K,) ->
+        K meshes from one batched decode and one marching-cubes launch sequence.  The reference has none (its
+        generate_mesh "only supports batch size 1")."""
+        with torch.no_grad():
+            sdf = self.vae.decode(latents)
+            try:
+                level = self.config["iso_threshold"]
+            except KeyError:
+                return None
+            meshes = extract_mesh(sdf[:, 0], level, complete=complete_mesh)
+        for m, s in zip(meshes, scales.reshape(-1).tolist()):
+            m.update_scale(float(s), rel_scale=True)
+        return meshes
 
     MAX_CACHED_LOOPS = 4     # per kind: a loop holds its point clouds at capacity (3.7 MB per 640x480 view) and its graphs
 
