@@ -38,11 +38,11 @@
  *   (sdf_view_stride = R*R*R elements).
  *
  * STABILITY -- group 1 below is the boundary: its signatures and semantics are what a binding relies on and do not change
- * without SDFR_VERSION's major number changing.  Groups 2 - 5 are UNSTABLE: they exist for this repository's own host
+ * without SDFR_VERSION's major number changing.  Groups 2 - 6 are UNSTABLE: they exist for this repository's own host
  * code (the Python modules under sdfest_amd/), follow its needs from round to round (arguments were added in every round so far), and are
  * exported only because that host code is Python over ctypes; bind to them at your own risk, pinned to one SDFR_VERSION.
  *
- * CONTENTS -- five groups; a binding from another language needs group 1 only
+ * CONTENTS -- six groups; a binding from another language needs group 1 only
  *   1. CORE: the reference boundary (what sdf_renderer_cpp, losses.pc_loss and SDFDecoder.forward are replaced by)
  *        sdfr_version, sdfr_last_error
  *        sdfr_render_forward[_workspace_bytes], sdfr_render_backward[_workspace_bytes]
@@ -69,6 +69,8 @@
  *        sdfr_init_estimate
  *   5. [unstable] MESH: marching cubes over N grids (SDFPipeline.generate_mesh, after the estimate)
  *        sdfr_mesh_tables, sdfr_mesh_workspace_bytes, sdfr_mesh_count, sdfr_mesh_emit
+ *   6. [unstable] METRICS: surface sampling and exact neighbour search for reconstruction metrics (the evaluation)
+ *        sdfr_sample_workspace_bytes, sdfr_sample_points, sdfr_nn_workspace_bytes, sdfr_nn_query, sdfr_nn_reduce
  * (Within the file the groups follow the order in which the reference's code runs; every declaration carries the
  * reference file:line it replaces.)
  */
@@ -832,6 +834,61 @@ SDFR_API int sdfr_mesh_count(const float* sdf, int N, int R, int complete, float
                              void* workspace, size_t workspace_bytes, int device, void* stream);
 SDFR_API int sdfr_mesh_emit(const float* sdf, int N, int R, int complete, float level, const int* totals,
                             float* vertices, float* normals, int* faces, void* workspace, size_t workspace_bytes,
+                            int device, void* stream);
+
+/* ==== 6. METRICS ============================================================================== */
+/* ---- uniform surface sampling: open3d's TriangleMesh.sample_points_uniformly (rendering_evaluation.py:290-295) -----
+ * K meshes, n points each, one record per mesh in a device table (the meshes may be slices of shared buffers):
+ *   triangle t is chosen with probability area_t / sum(area): u from a 53-bit double, t = the first face with
+ *   cdf[t] > u cdf[F - 1] (cdf: the inclusive fp64 scan of |(b - a) x (c - a)| over the record's unscaled fp32
+ *   vertices, in an order fixed by F; zero-area faces are never chosen); point = (1 - sqrt r1) a + sqrt r1 (1 - r2) b
+ *   + sqrt r1 r2 c; then p := R(quat) (factor p) + position.
+ *   random words: Philox-4x32-10, key = {seed & 0xffffffff, seed >> 32}, counter = {sample index i, 0, 0, 0};
+ *   words x, y -> u = ((x >> 5) 2^26 + (y >> 6)) 2^-53, z -> r1 = (z >> 8) 2^-24, w -> r2 = (w >> 8) 2^-24.
+ *   The mesh's position in the table is not part of the stream: a batch equals its single calls bit for bit.
+ * Outputs points [K][n][3] float; normals [K][n][3] float (nullable: the barycentric blend of the record's vertex
+ * normals, rotated, normalised; NaN for a record without normals); triangles [K][n] int32 (nullable).
+ * A record whose faces leave [0, total_faces) of the workspace, or whose every face has zero area, gives NaN points
+ * and triangle -1.  Requirements: 1 <= num_faces <= max_faces for every record, the records' CDF ranges
+ * [cdf_offset, cdf_offset + num_faces) disjoint inside [0, total_faces). */
+typedef struct sdfr_sample_mesh {
+  const float* vertices;   /* [num_vertices][3], unscaled */
+  const int* faces;        /* [num_faces][3] vertex indices */
+  const float* normals;    /* [num_vertices][3] or NULL */
+  long long cdf_offset;    /* the mesh's first element of the workspace's fp64 CDF */
+  int num_vertices, num_faces;
+  float factor;            /* uniform scale (the Mesh's _factor) */
+  float quat[4];           /* (x, y, z, w) */
+  float position[3];
+} sdfr_sample_mesh;        /* 72 bytes */
+SDFR_API size_t sdfr_sample_workspace_bytes(int K, long long total_faces, int max_faces);   /* 0: invalid */
+SDFR_API int sdfr_sample_points(const sdfr_sample_mesh* meshes, int K, long long total_faces, int max_faces, int n,
+                                unsigned long long seed, float* points, float* normals, int* triangles,
+                                void* workspace, size_t workspace_bytes, int device, void* stream);
+
+/* ---- exact neighbours: scipy.spatial.KDTree(refs).query(queries, p=p) (metrics.py), brute force, O(N M) ------------
+ * K pairs: query set k = queries[q_offsets[k] .. q_offsets[k+1]) against reference set k = refs[r_offsets[k] ..
+ * r_offsets[k+1]) (device int64 offsets, [K + 1]; max_q / max_r: host bounds of every pair's sizes, they shape the
+ * grid; offsets are clamped to [0, total], so wrong ones give wrong answers, never out-of-bounds accesses).
+ *   p in [1, inf] (p = 1, 2, inf specialised); the fp32 value sum |q_i - r_i|^p (max |q_i - r_i| for p = inf), from
+ *   coordinate differences, decides; ties go to the lowest reference index; the winner's distance is then recomputed
+ *   in fp64.  farthest = 1: the farthest reference point instead (with refs = queries, max over the queries of it is
+ *   the set's diameter).  Per query: dist [total_q] double, index [total_q] int32 (nullable; local to its reference
+ *   set).  A query with no reference point (empty set, NaN) gets NaN and -1.  The result is the same bits whatever the
+ *   batch or the run: per-workgroup winners merge through integer atomics on (float bits << 32 | index). */
+SDFR_API size_t sdfr_nn_workspace_bytes(int K, long long total_q, int max_q);   /* 0: invalid */
+SDFR_API int sdfr_nn_query(const float* queries, const long long* q_offsets, long long total_q, int max_q,
+                           const float* refs, const long long* r_offsets, long long total_r, int max_r, int K,
+                           float p, int farthest, double* dist, int* index, void* workspace, size_t workspace_bytes,
+                           int device, void* stream);
+/* per pair k over dist[offsets[k] .. offsets[k+1]), fp64 in a fixed tree order (the same bits for a pair whatever K):
+ * stats [K][SDFR_NN_STATS] = {sum d, max d, count, NaN count, count(d < t_j) for j < SDFR_NN_MAX_THRESHOLDS,
+ * count(d / extent[k] < t_j) for j < SDFR_NN_MAX_THRESHOLDS}; NaN distances are left out of the sum, max and counts;
+ * t_j = h_thresholds[j] for j < num_thresholds (0 in the rest); extent [K] device, nullable (then 1). */
+#define SDFR_NN_MAX_THRESHOLDS 4
+#define SDFR_NN_STATS (4 + 2 * SDFR_NN_MAX_THRESHOLDS)
+SDFR_API int sdfr_nn_reduce(const double* dist, const long long* offsets, long long total, int K,
+                            const double* h_thresholds, int num_thresholds, const double* extent, double* stats,
                             int device, void* stream);
 
 #ifdef __cplusplus

@@ -151,6 +151,13 @@ SIGNATURES = {
     "sdfr_mesh_workspace_bytes": (c_sz, [c_int, c_int, c_int]),
     "sdfr_mesh_count": (c_int, [c_fp, c_int, c_int, c_int, c_f, c_fp, c_fp, c_sz, c_int, c_fp]),
     "sdfr_mesh_emit": (c_int, [c_fp, c_int, c_int, c_int, c_f, c_fp, c_fp, c_fp, c_fp, c_fp, c_sz, c_int, c_fp]),
+    "sdfr_sample_workspace_bytes": (c_sz, [c_int, c_ll, c_int]),
+    "sdfr_sample_points": (c_int, [c_fp, c_int, c_ll, c_int, c_int, ctypes.c_ulonglong, c_fp, c_fp, c_fp, c_fp, c_sz,
+                                   c_int, c_fp]),
+    "sdfr_nn_workspace_bytes": (c_sz, [c_int, c_ll, c_int]),
+    "sdfr_nn_query": (c_int, [c_fp, c_fp, c_ll, c_int, c_fp, c_fp, c_ll, c_int, c_int, c_f, c_int, c_fp, c_fp, c_fp,
+                              c_sz, c_int, c_fp]),
+    "sdfr_nn_reduce": (c_int, [c_fp, c_fp, c_ll, c_int, c_fp, c_int, c_fp, c_fp, c_int, c_fp]),
 }
 
 

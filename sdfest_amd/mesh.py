@@ -14,7 +14,7 @@ import torch
 from . import _lib
 from .pipeline import quaternion_apply
 
-__all__ = ["Mesh", "extract_mesh"]
+__all__ = ["Mesh", "extract_mesh", "sample_points"]
 
 
 class Mesh:
@@ -120,6 +120,21 @@ class Mesh:
             fh.write(vert.tobytes())
             fh.write(face.tobytes())
 
+    def sample_points_uniformly(self, number_of_points: int = 100, seed: int = 0, transformed: bool = True,
+                                normals: bool = False, return_triangles: bool = False):
+        """``number_of_points`` points uniformly distributed over the surface (open3d's ``sample_points_uniformly``
+        rule: triangle by area, then barycentrics (1 - sqrt r1, sqrt r1 (1 - r2), sqrt r1 r2)), on the GPU
+        (``sdfr_sample_points``, csrc/metrics.hip).
+
+        The mesh is scaled, and posed if `transformed` (else only scaled, as ``numpy(transformed=False)``).  The random
+        stream depends on `seed` and the sample index only: the same seed gives the same samples on every call, and
+        two meshes sampled with one seed use the same random numbers (as the reference samples ground truth and
+        estimate).  Returns points (n,3) float32; with `normals` also (n,3) unit normals (the mesh needs vertex
+        normals); with `return_triangles` also the (n,) int32 face of every point."""
+        pts, nrm, tri = _sample([self], number_of_points, seed, transformed, normals)
+        out = (pts[0],) + ((nrm[0],) if normals else ()) + ((tri[0],) if return_triangles else ())
+        return out[0] if len(out) == 1 else out
+
     def __repr__(self) -> str:
         return (f"Mesh(V={self.vertices.shape[0]}, F={self.faces.shape[0]}, scale={self.scale}, "
                 f"rel_scale={self.rel_scale})")
@@ -186,3 +201,74 @@ def extract_mesh(sdf: torch.Tensor, level: float, complete: bool = False,
     meshes = [Mesh(verts[vo[n]:vo[n + 1]], faces[fo[n]:fo[n + 1]],
                    nrm[vo[n]:vo[n + 1]] if nrm is not None else None) for n in range(N)]
     return meshes[0] if single else meshes
+
+
+# sdfr_sample_mesh (include/sdfr.h): 72 bytes
+_SAMPLE_RECORD = np.dtype({"names": ["vertices", "faces", "normals", "cdf_offset", "num_vertices", "num_faces",
+                                     "factor", "quat", "position"],
+                           "formats": ["<u8", "<u8", "<u8", "<i8", "<i4", "<i4", "<f4", ("<f4", 4), ("<f4", 3)],
+                           "offsets": [0, 8, 16, 24, 32, 36, 40, 44, 60], "itemsize": 72})
+
+
+def _sample(meshes: List[Mesh], n: int, seed: int, transformed: bool, normals: bool):
+    """points (K,n,3), normals (K,n,3) or None, triangles (K,n) int32 for K meshes on one device: one launch
+    sequence, no host synchronisation"""
+    n = int(n)
+    if n < 1:
+        raise ValueError(f"number_of_points={n} must be >= 1")
+    if not meshes:
+        raise ValueError("no meshes to sample")
+    if not 0 <= int(seed) < 2 ** 64:
+        raise ValueError(f"seed={seed} must be in [0, 2^64)")
+    dev = meshes[0].vertices.device
+    if dev.type != "cuda":
+        raise TypeError("meshes must live on a CUDA device (sdfest_amd has no CPU path)")
+    K = len(meshes)
+    rec = np.zeros(K, dtype=_SAMPLE_RECORD)
+    keep = []
+    off = 0
+    for k, m in enumerate(meshes):
+        if m.vertices.device != dev:
+            raise ValueError("all meshes must live on one device")
+        F = int(m.faces.shape[0])
+        if F == 0 or m.vertices.shape[0] == 0:
+            raise ValueError(f"mesh {k} has no faces to sample")
+        if normals and m.normals is None:
+            raise ValueError(f"mesh {k} has no vertex normals (extract_mesh(..., normals=True))")
+        v = m.vertices.detach().to(torch.float32).contiguous()
+        f = m.faces.detach().to(torch.int32).contiguous()
+        nr = m.normals.detach().to(torch.float32).contiguous() if (normals and m.normals is not None) else None
+        keep += [v, f, nr]
+        rec[k]["vertices"], rec[k]["faces"] = v.data_ptr(), f.data_ptr()
+        rec[k]["normals"] = nr.data_ptr() if nr is not None else 0
+        rec[k]["cdf_offset"], rec[k]["num_vertices"], rec[k]["num_faces"] = off, v.shape[0], F
+        rec[k]["factor"] = m._factor
+        rec[k]["quat"] = (0.0, 0.0, 0.0, 1.0)
+        off += F
+    max_f = max(int(m.faces.shape[0]) for m in meshes)
+    L = _lib.lib()
+    ws_bytes = L.sdfr_sample_workspace_bytes(K, off, max_f)
+    if ws_bytes == 0:
+        _lib.check(-1, "sdfr_sample_workspace_bytes")
+    table = torch.from_numpy(rec.view(np.uint8)).pin_memory().to(dev, non_blocking=True)
+    if transformed:   # the poses stay on the device: floats 11..14 and 15..17 of each record
+        tab = table.view(torch.float32).view(K, _SAMPLE_RECORD.itemsize // 4)
+        tab[:, 11:15] = torch.stack([m.orientation.detach().to(dev, torch.float32) for m in meshes])
+        tab[:, 15:18] = torch.stack([m.position.detach().to(dev, torch.float32) for m in meshes])
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    pts = torch.empty((K, n, 3), dtype=torch.float32, device=dev)
+    nrm = torch.empty((K, n, 3), dtype=torch.float32, device=dev) if normals else None
+    tri = torch.empty((K, n), dtype=torch.int32, device=dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    with torch.cuda.device(dev):
+        _lib.check(L.sdfr_sample_points(_ptr(table), K, off, max_f, n, int(seed), _ptr(pts),
+                                        _ptr(nrm) if nrm is not None else None, _ptr(tri), _ptr(ws), ws_bytes,
+                                        dev.index, stream), "sdfr_sample_points")
+    del keep   # freed tensors are reused only by later work on this stream: the launches read them first
+    return pts, nrm, tri
+
+
+def sample_points(meshes: List[Mesh], number_of_points: int, seed: int = 0, transformed: bool = True) -> torch.Tensor:
+    """``Mesh.sample_points_uniformly`` for K meshes in one launch sequence: (K, number_of_points, 3) float32.  Mesh k's
+    points equal ``meshes[k].sample_points_uniformly(number_of_points, seed, transformed)`` bit for bit."""
+    return _sample(list(meshes), number_of_points, seed, transformed, False)[0]
