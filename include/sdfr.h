@@ -38,11 +38,11 @@
  *   (sdf_view_stride = R*R*R elements).
  *
  * STABILITY -- group 1 below is the boundary: its signatures and semantics are what a binding relies on and do not change
- * without SDFR_VERSION's major number changing.  Groups 2 - 6 are UNSTABLE: they exist for this repository's own host
+ * without SDFR_VERSION's major number changing.  Groups 2 - 7 are UNSTABLE: they exist for this repository's own host
  * code (the Python modules under sdfest_amd/), follow its needs from round to round (arguments were added in every round so far), and are
  * exported only because that host code is Python over ctypes; bind to them at your own risk, pinned to one SDFR_VERSION.
  *
- * CONTENTS -- six groups; a binding from another language needs group 1 only
+ * CONTENTS -- seven groups; a binding from another language needs group 1 only
  *   1. CORE: the reference boundary (what sdf_renderer_cpp, losses.pc_loss and SDFDecoder.forward are replaced by)
  *        sdfr_version, sdfr_last_error
  *        sdfr_render_forward[_workspace_bytes], sdfr_render_backward[_workspace_bytes]
@@ -71,6 +71,8 @@
  *        sdfr_mesh_tables, sdfr_mesh_workspace_bytes, sdfr_mesh_count, sdfr_mesh_emit
  *   6. [unstable] METRICS: surface sampling and exact neighbour search for reconstruction metrics (the evaluation)
  *        sdfr_sample_workspace_bytes, sdfr_sample_points, sdfr_nn_workspace_bytes, sdfr_nn_query, sdfr_nn_reduce
+ *   7. [unstable] ENCODER: the VAE's encoder half (SDFVAE.encode / forward / sample / prepare_input)
+ *        sdfr_encoder_create / _destroy / _workspace_bytes / _forward, sdfr_normal_sample, sdfr_clamp
  * (Within the file the groups follow the order in which the reference's code runs; every declaration carries the
  * reference file:line it replaces.)
  */
@@ -890,6 +892,43 @@ SDFR_API int sdfr_nn_query(const float* queries, const long long* q_offsets, lon
 SDFR_API int sdfr_nn_reduce(const double* dist, const long long* offsets, long long total, int K,
                             const double* h_thresholds, int num_thresholds, const double* extent, double* stats,
                             int device, void* stream);
+
+/* ==== 7. ENCODER ============================================================================== */
+/* ---- SDFEncoder.forward (sdf_vae.py:103-169) and the noise of SDFVAE.encode / sample (:60-77) ------------------------
+ * N cubic grids x [N][1][D][D][D] -> means [N][L], log_var [N][L] and (z nullable) z = means + exp(0.5 log_var) eps.
+ * The layers are h_ops [n_ops][SDFR_ENC_OP_INTS] = {type, a, b, kernel, stride, padding, relu, 0} over (C, S, S, S)
+ * (C = 1, S = D at first; Flatten is no op, torch's (C, D, H, W) order is the flattened one):
+ *   SDFR_ENC_CONV     Conv3d: a = in_channels (= C), b = out_channels, cubic kernel, stride, zero padding, with bias;
+ *                     S -> (S + 2 padding - kernel) / stride + 1
+ *   SDFR_ENC_MAXPOOL  MaxPool3d: kernel, stride, padding 0, floor (a, b unused)
+ *   SDFR_ENC_LINEAR   Linear: a = in_features (= C S^3, or the previous Linear's b), b = out_features; the
+ *                     activation is flat from here on, no 3-d op may follow
+ *   SDFR_ENC_RELU     ReLU (all other fields 0); relu = 1 in any other op applies a ReLU to its output
+ * h_params: for every CONV / LINEAR op in order its weight (torch's layout: [b][a][k][k][k] / [b][a]) and bias [b];
+ * then linear_means.weight [L][F], .bias [L], linear_log_var.weight [L][F], .bias [L] (F = the flat feature count).
+ * Anything else, or a size or parameter count that does not add up, is SDFR_E_INVALID at creation, naming the op.
+ * Results: fixed summation orders, no atomics -- a row's means / log_var are the same bits whatever N, its position
+ * in the batch, or the run.  eps[i][j]: Philox-4x32-10, key = {seed & 0xffffffff, seed >> 32}, counter = {i, j, 0,
+ * 0x56414531}; words x, y -> u1 = ((x >> 5) 2^26 + (y >> 6)) 2^-53, z, w -> u2 likewise; eps = sqrt(-2 ln(1 - u1))
+ * cos(2 pi u2) in fp64, rounded to fp32; z = eps * float(exp(0.5 log_var)) + means, two fp32 roundings.  eps depends on
+ * (seed, i, j) only. */
+#define SDFR_ENC_CONV 1
+#define SDFR_ENC_MAXPOOL 2
+#define SDFR_ENC_LINEAR 3
+#define SDFR_ENC_RELU 4
+#define SDFR_ENC_OP_INTS 8
+typedef struct sdfr_encoder sdfr_encoder;
+SDFR_API int sdfr_encoder_create(const float* h_params, size_t n_params, int volume, int latent, int n_ops,
+                                 const int* h_ops, int device, sdfr_encoder** out_handle);
+SDFR_API void sdfr_encoder_destroy(sdfr_encoder* encoder);
+SDFR_API size_t sdfr_encoder_workspace_bytes(const sdfr_encoder* encoder, int N);   /* 0: NULL encoder or N < 1 */
+SDFR_API int sdfr_encoder_forward(const sdfr_encoder* encoder, const float* x, int N, float* means, float* log_var,
+                                  float* z, unsigned long long seed, void* workspace, size_t workspace_bytes,
+                                  void* stream);
+/* out [n][L] = eps of rows 0 .. n-1 (the stream above: SDFVAE.sample, zero means and unit std) */
+SDFR_API int sdfr_normal_sample(float* out, int n, int L, unsigned long long seed, int device, void* stream);
+/* x[i] = min(max(x[i], -t), t) in place, t >= 0 (SDFEncoder.prepare_input: the tsdf clamp) */
+SDFR_API int sdfr_clamp(float* x, size_t count, float t, int device, void* stream);
 
 #ifdef __cplusplus
 }

@@ -158,6 +158,12 @@ SIGNATURES = {
     "sdfr_nn_query": (c_int, [c_fp, c_fp, c_ll, c_int, c_fp, c_fp, c_ll, c_int, c_int, c_f, c_int, c_fp, c_fp, c_fp,
                               c_sz, c_int, c_fp]),
     "sdfr_nn_reduce": (c_int, [c_fp, c_fp, c_ll, c_int, c_fp, c_int, c_fp, c_fp, c_int, c_fp]),
+    "sdfr_encoder_create": (c_int, [c_fp, c_sz, c_int, c_int, c_int, c_fp, c_int, c_fp]),
+    "sdfr_encoder_destroy": (None, [c_fp]),
+    "sdfr_encoder_workspace_bytes": (c_sz, [c_fp, c_int]),
+    "sdfr_encoder_forward": (c_int, [c_fp, c_fp, c_int, c_fp, c_fp, c_fp, ctypes.c_ulonglong, c_fp, c_sz, c_fp]),
+    "sdfr_normal_sample": (c_int, [c_fp, c_int, c_int, ctypes.c_ulonglong, c_int, c_fp]),
+    "sdfr_clamp": (c_int, [c_fp, c_sz, c_f, c_int, c_fp]),
 }
 
 

@@ -178,6 +178,12 @@ static __global__ void copy_words_kernel(float* __restrict__ dst, const float* _
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (i < n) dst[i] = src[i];
 }
+// grid: ceil(count / 256);  clamp a tensor in place to [-clamp, clamp] (the decoder's enforce_tsdf when the last layer
+// already has the volume size; the encoder's prepare_input, sdfr_clamp)
+static __global__ void clamp_kernel(float* __restrict__ x, size_t count, float clamp) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < count) x[i] = fminf(fmaxf(x[i], -clamp), clamp);
+}
 inline void zero_words_async(float* p, size_t n, hipStream_t st) {
   if (n) hipLaunchKernelGGL(zero_words_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, p, n);
 }

@@ -559,12 +559,6 @@ __global__ __launch_bounds__(256) void resize3_mix_kernel(const float* __restric
   }
 }
 
-// grid: ceil(count / 256);  clamp a tensor in place (only when the last layer already has the
-// volume size and enforce_tsdf is set)
-__global__ void clamp_kernel(float* __restrict__ x, size_t count, float clamp) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < count) x[i] = fminf(fmaxf(x[i], -clamp), clamp);
-}
 
 
 // Copy n floats (n % 4 == 0, both 16-byte aligned) global -> LDS with a whole workgroup: 16-byte

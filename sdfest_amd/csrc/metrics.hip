@@ -29,6 +29,7 @@
 #include <cmath>
 
 #include "common.hpp"
+#include "philox.hpp"
 
 // the CPU twin (tests/metrics_twin.py) evaluates every expression in this file operation by operation
 #pragma clang fp contract(off)
@@ -53,25 +54,6 @@ __device__ __forceinline__ int sample_faces(const sdfr_sample_mesh& m, long long
   const bool ok = m.num_faces >= 1 && m.num_faces <= max_faces && m.cdf_offset >= 0 &&
                   m.cdf_offset + m.num_faces <= total_faces;
   return ok ? m.num_faces : 0;
-}
-
-// ---- Philox-4x32-10 (Salmon et al., SC'11), the Random123 round function and Weyl key schedule ----------------------
-struct U4 {
-  unsigned x, y, z, w;
-};
-
-__device__ __forceinline__ U4 philox4x32_10(U4 c, unsigned k0, unsigned k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned long long p0 = (unsigned long long)0xD2511F53u * c.x;
-    const unsigned long long p1 = (unsigned long long)0xCD9E8D57u * c.z;
-    const unsigned hi0 = (unsigned)(p0 >> 32), lo0 = (unsigned)p0;
-    const unsigned hi1 = (unsigned)(p1 >> 32), lo1 = (unsigned)p1;
-    c = U4{hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0};
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  return c;
 }
 
 __device__ __forceinline__ V3 quat_rotate(const float* q, V3 v) {
