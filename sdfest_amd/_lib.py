@@ -1,170 +1,109 @@
-"""ctypes binding of libsdfr_hip.so (the C ABI declared in include/sdfr.h).
+"""ctypes binding of libsdfr_hip.so, derived from its C ABI header include/sdfr.h.
 
 The shared library is built in-tree by ``sdfest_amd/csrc/Makefile`` (see
 ``__graft_entry__.build``).  There is NO fallback: if the library is missing
 or a call fails, the error is raised -- the product never computes on the CPU.
+
+The header is the binding's one source: at import, every ``SDFR_API`` declaration becomes an entry of
+``SIGNATURES`` and every integer ``#define`` an entry of ``ABI``.  A type or a macro that cannot be read
+raises, so a new declaration is never bound wrong unnoticed.
 """
+import ast
 import ctypes
+import operator
 import os
+import re
 import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
+HEADER = os.path.join(os.path.dirname(_HERE), "include", "sdfr.h")
 # SDFR_LIB: another build of the same library (timing experiments: tools/microbench/build_variant.sh)
 LIB_PATH = os.environ.get("SDFR_LIB") or os.path.join(_HERE, "libsdfr_hip.so")
 _lib = None
 
-c_fp = ctypes.c_void_p
-c_int = ctypes.c_int
-c_ll = ctypes.c_longlong
-c_f = ctypes.c_float
-c_sz = ctypes.c_size_t
-
-# name -> (restype, argtypes); mirrors include/sdfr.h declaration by declaration
-SIGNATURES = {
-    "sdfr_version": (c_int, []),
-    "sdfr_last_error": (ctypes.c_char_p, []),
-    "sdfr_render_forward_workspace_bytes": (c_sz, [c_int, c_int, c_int, c_int]),
-    "sdfr_render_sync_offset": (c_sz, [c_int]),
-    "sdfr_decoder_set_option": (c_int, [c_fp, c_int, c_int]),
-    "sdfr_render_partials_offset": (c_sz, [c_int, c_int, c_int, c_int, c_int]),
-    "sdfr_render_step_forward_l1": (c_int, [c_fp, c_int, c_ll, c_fp, c_fp, c_fp, c_int, c_int, c_int,
-                                            c_f, c_f, c_f, c_f, c_f, c_fp, c_fp, c_fp, c_fp, c_fp, c_ll, c_fp, c_sz,
-                                            c_fp, c_int, c_fp]),
-    "sdfr_render_step_backward_l1_pc": (c_int, [c_fp, c_f, c_fp, c_fp, c_fp, c_fp, c_int, c_ll, c_fp, c_fp, c_fp,
-                                                c_int, c_int, c_int, c_f, c_f, c_f, c_f, c_int, c_fp, c_ll, c_fp, c_sz,
-                                                c_f, c_fp, c_fp, c_int, c_fp, c_fp, c_sz, c_fp, c_fp, c_int, c_fp]),
-    "sdfr_render_step_fused_l1_pc": (c_int, [c_fp, c_int, c_ll, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_f, c_f, c_f,
-                                             c_f, c_f, c_fp, c_fp, c_int, c_fp, c_fp, c_fp, c_sz, c_f, c_fp, c_fp, c_int,
-                                             c_fp, c_sz, c_int, c_fp]),
-    "sdfr_render_fused_view_count_offset": (c_sz, [c_int, c_int]),
-    "sdfr_render_fused_tile_loss_offset": (c_sz, [c_int, c_int, c_int, c_int]),
-    "sdfr_loop_tail_fused": (c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_f, c_f, c_f, c_f, c_int, c_fp, c_fp, c_int,
-                                     c_fp, c_sz, c_sz, c_sz, c_f, c_fp, c_int, c_int, c_fp, c_fp, c_int, c_fp, c_fp, c_fp,
-                                     c_fp, c_fp, c_fp, c_fp, c_f, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_fp]),
-    "sdfr_render_step_backward_l1": (c_int, [c_fp, c_f, c_fp, c_fp, c_fp, c_fp, c_int, c_ll, c_int, c_int, c_int,
-                                             c_f, c_f, c_f, c_f, c_int, c_fp, c_ll, c_fp, c_fp, c_fp, c_fp, c_sz,
-                                             c_fp, c_fp, c_int, c_fp]),
-    "sdfr_loop_tail": (c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_f, c_f, c_f, c_f, c_int, c_fp, c_fp, c_int,
-                               c_fp, c_sz, c_int, c_int, c_fp, c_fp, c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp,
-                               c_f, c_fp, c_fp, c_fp, c_int, c_fp]),
-    "sdfr_pose_to_views_objects": (c_int, [c_fp, c_int, c_int, c_fp, c_fp, c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_int,
-                                           c_fp]),
-    "sdfr_loop_tail_objects": (c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_f, c_f, c_f, c_f, c_int, c_fp, c_fp,
-                                       c_int, c_fp, c_sz, c_int, c_int, c_fp, c_fp, c_int, c_fp, c_fp, c_fp, c_fp, c_fp,
-                                       c_fp, c_fp, c_fp, c_int, c_fp]),
-    "sdfr_loop_view_records": (c_int, [c_fp, c_sz, c_int, c_int, c_int, c_fp, c_int, c_fp, c_int, c_fp, c_fp, c_int,
-                                       c_int, c_int, c_fp, c_int, c_fp]),
-    "sdfr_loop_tail_records": (c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_f, c_f, c_f, c_f, c_int, c_fp, c_fp,
-                                       c_int, c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_f, c_fp, c_fp,
-                                       c_fp, c_int, c_fp]),
-    "sdfr_inlier_counts_record": (c_int, [c_fp, c_fp, c_int, c_int, c_f, c_fp, c_fp, c_int, c_fp]),
-    "sdfr_inlier_update_record": (c_int, [c_fp, c_fp, c_fp, c_int, c_fp, c_fp, c_int, c_fp, c_int, c_fp]),
-    "sdfr_render_fixed_volume_offset": (c_sz, [c_int, c_int, c_int, c_int, c_int]),
-    "sdfr_fixed_to_float": (c_int, [c_fp, c_sz, c_fp, c_int, c_fp]),
-    "sdfr_render_forward": (c_int, [c_fp, c_int, c_ll, c_fp, c_fp, c_fp, c_int, c_int, c_int,
-                                    c_f, c_f, c_f, c_f, c_f, c_fp, c_fp, c_sz, c_int, c_fp]),
-    "sdfr_render_backward_workspace_bytes": (c_sz, [c_int, c_int, c_int, c_int]),
-    "sdfr_render_backward": (c_int, [c_fp, c_fp, c_fp, c_int, c_ll, c_fp, c_fp, c_fp, c_int,
-                                     c_int, c_int, c_f, c_f, c_f, c_f, c_int, c_fp, c_ll, c_fp,
-                                     c_fp, c_fp, c_fp, c_sz, c_int, c_fp]),
-    "sdfr_render_step_workspace_bytes": (c_sz, [c_int, c_int, c_int, c_int]),
-    "sdfr_render_step_forward": (c_int, [c_fp, c_int, c_ll, c_fp, c_fp, c_fp, c_int, c_int, c_int,
-                                         c_f, c_f, c_f, c_f, c_f, c_fp, c_fp, c_ll, c_fp, c_sz, c_int, c_fp]),
-    "sdfr_render_step_forward_counted": (c_int, [c_fp, c_int, c_ll, c_fp, c_fp, c_fp, c_int, c_int, c_int,
-                                                 c_f, c_f, c_f, c_f, c_f, c_fp, c_fp, c_ll, c_fp, c_sz, c_fp, c_int,
-                                                 c_fp]),
-    "sdfr_render_step_backward": (c_int, [c_fp, c_fp, c_fp, c_int, c_ll, c_int, c_int, c_int,
-                                          c_f, c_f, c_f, c_f, c_int, c_fp, c_ll, c_fp, c_fp, c_fp,
-                                          c_fp, c_sz, c_int, c_fp]),
-    "sdfr_render_forward_l1_workspace_bytes": (c_sz, [c_int, c_int, c_int, c_int]),
-    "sdfr_render_forward_l1": (c_int, [c_fp, c_int, c_ll, c_fp, c_fp, c_fp, c_int, c_int, c_int,
-                                       c_f, c_f, c_f, c_f, c_f, c_fp, c_fp, c_fp, c_fp, c_fp, c_sz,
-                                       c_int, c_fp]),
-    "sdfr_render_backward_l1": (c_int, [c_fp, c_f, c_fp, c_fp, c_fp, c_fp, c_int, c_ll, c_fp, c_fp,
-                                        c_fp, c_int, c_int, c_int, c_f, c_f, c_f, c_f, c_int, c_fp,
-                                        c_ll, c_fp, c_fp, c_fp, c_fp, c_sz, c_int, c_fp]),
-    "sdfr_pc_loss_forward": (c_int, [c_fp, c_fp, c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_int, c_ll,
-                                     c_fp, c_int, c_fp]),
-    "sdfr_pc_loss_backward_workspace_bytes": (c_sz, [c_int, c_int]),
-    "sdfr_pc_loss_backward": (c_int, [c_fp, c_fp, c_fp, c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_int,
-                                      c_ll, c_fp, c_ll, c_fp, c_fp, c_fp, c_fp, c_sz, c_int, c_fp]),
-    "sdfr_pc_l1_backward": (c_int, [c_f, c_fp, c_fp, c_fp, c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_int, c_ll,
-                                    c_fp, c_ll, c_fp, c_fp, c_fp, c_fp, c_sz, c_int, c_fp]),
-    "sdfr_pc_l1_backward_accumulate": (c_int, [c_f, c_fp, c_fp, c_fp, c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_int, c_ll,
-                                    c_fp, c_ll, c_fp, c_fp, c_fp, c_fp, c_sz, c_int, c_fp]),
-    "sdfr_decoder_create": (c_int, [c_fp, c_sz, c_int, c_int, c_fp, c_int, c_fp, c_fp, c_fp, c_fp,
-                                    c_fp, c_int, c_f, c_int, c_fp]),
-    "sdfr_decoder_destroy": (None, [c_fp]),
-    "sdfr_decoder_workspace_bytes": (c_sz, [c_fp, c_int]),
-    "sdfr_decoder_tape_bytes": (c_sz, [c_fp, c_int]),
-    "sdfr_decoder_forward": (c_int, [c_fp, c_fp, c_int, c_int, c_fp, c_fp, c_fp, c_sz, c_fp]),
-    "sdfr_decoder_forward_stage": (c_int, [c_fp, c_fp, c_int, c_int, c_fp, c_fp, c_fp, c_sz, c_fp, c_int]),
-    "sdfr_decoder_backward_workspace_bytes": (c_sz, [c_fp, c_int]),
-    "sdfr_decoder_backward_latent": (c_int, [c_fp, c_fp, c_fp, c_fp, c_int, c_fp, c_fp, c_sz, c_fp]),
-    "sdfr_decoder_backward_latent_deferred": (c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, c_sz, c_fp, c_fp]),
-    "sdfr_decoder_backward_latent_deferred_scaled": (c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_fp, c_f, c_fp, c_sz,
-                                                             c_fp, c_fp]),
-    "sdfr_decoder_backward_latent_deferred_batch": (c_int, [c_fp, c_fp, c_fp, c_fp, c_int, c_fp, c_sz, c_fp, c_fp]),
-    "sdfr_pose_to_views": (c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_fp, c_fp, c_fp, c_fp, c_int, c_fp]),
-    "sdfr_views_to_pose_grad": (c_int, [c_fp, c_fp, c_fp, c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp,
-                                        c_fp, c_fp, c_fp, c_int, c_fp]),
-    "sdfr_views_to_pose_grad_deferred": (c_int, [c_fp, c_fp, c_fp, c_int, c_fp, c_int, c_int, c_fp, c_fp, c_int,
-                                                 c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_fp]),
-    "sdfr_render_backward_l1_pc": (c_int, [c_fp, c_f, c_fp, c_fp, c_fp, c_fp, c_int, c_ll, c_fp, c_fp, c_fp,
-                                           c_int, c_int, c_int, c_f, c_f, c_f, c_f, c_int, c_fp, c_ll, c_fp, c_sz,
-                                           c_f, c_fp, c_fp, c_int, c_fp, c_fp, c_sz, c_int, c_fp]),
-    "sdfr_depth_l1_workspace_bytes": (c_sz, [c_int, c_int, c_int]),
-    "sdfr_depth_l1_loss": (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_f, c_fp, c_fp, c_fp, c_sz, c_int, c_fp]),
-    "sdfr_pc_l1_loss": (c_int, [c_fp, c_fp, c_int, c_int, c_f, c_fp, c_fp, c_int, c_fp]),
-    "sdfr_depth_points_workspace_bytes": (c_sz, [c_int, c_int, c_int]),
-    "sdfr_depth_count": (c_int, [c_fp, c_int, c_int, c_int, c_fp, c_fp, c_sz, c_int, c_fp]),
-    "sdfr_depth_to_points": (c_int, [c_fp, c_int, c_int, c_int, c_f, c_f, c_f, c_f, c_fp, c_fp, c_fp, c_int,
-                                     c_fp]),
-    "sdfr_depth_count_ordered": (c_int, [c_fp, c_int, c_int, c_int, c_int, c_fp, c_fp, c_sz, c_int, c_fp]),
-    "sdfr_depth_to_points_ordered": (c_int, [c_fp, c_int, c_int, c_int, c_int, c_f, c_f, c_f, c_f, c_fp, c_fp, c_fp,
-                                             c_int, c_fp]),
-    "sdfr_depth_centroid_workspace_bytes": (c_sz, [c_int, c_int, c_int]),
-    "sdfr_depth_count_centroid": (c_int, [c_fp, c_int, c_int, c_int, c_int, c_f, c_f, c_f, c_f, c_fp, c_fp, c_fp, c_fp,
-                                          c_sz, c_int, c_fp]),
-    "sdfr_depth_to_points_shifted": (c_int, [c_fp, c_int, c_int, c_int, c_int, c_f, c_f, c_f, c_f, c_fp, c_fp, c_fp,
-                                             c_fp, c_fp, c_int, c_fp]),
-    "sdfr_depth_to_points_resident": (c_int, [c_fp, c_int, c_int, c_int, c_int, c_f, c_f, c_f, c_f, c_fp, c_fp, c_fp,
-                                              c_sz, c_fp, c_int, c_fp]),
-    "sdfr_preprocess_depth": (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_f, c_int, c_fp, c_int, c_fp]),
-    "sdfr_add_inplace": (c_int, [c_fp, c_fp, c_sz, c_int, c_fp]),
-    "sdfr_adam_step": (c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_f, c_f, c_f, c_f, c_int, c_int, c_fp]),
-    "sdfr_point_constraint": (c_int, [c_fp, c_fp, c_fp, c_f, c_fp, c_fp, c_int, c_fp]),
-    "sdfr_inlier_ratio": (c_int, [c_fp, c_fp, c_int, c_int, c_f, c_fp, c_fp, c_fp, c_int, c_fp, c_fp, c_int,
-                                  c_fp, c_int, c_fp]),
-    "sdfr_pointnet_layer": (c_int, [c_fp, c_int, c_int, c_int, c_fp, c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int,
-                                    c_fp, c_int, c_fp]),
-    "sdfr_pointnet_layer_counted": (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_fp, c_int, c_fp, c_fp, c_fp, c_fp, c_fp,
-                                            c_int, c_int, c_fp, c_int, c_fp]),
-    "sdfr_init_estimate": (c_int, [c_fp, c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_fp, c_fp, c_fp, c_int,
-                                   c_fp]),
-    "sdfr_linear_vec": (c_int, [c_fp, c_int, c_int, c_fp, c_int, c_fp, c_fp, c_fp, c_int, c_fp, c_int, c_int, c_fp]),
-    "sdfr_orientation_posterior": (c_int, [c_fp, c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_fp]),
-    "sdfr_affine_mask": (c_int, [c_fp, c_int, c_int, c_int, c_fp, c_fp, c_int, c_fp]),
-    "sdfr_nn_loss_forward": (c_int, [c_fp, c_int, c_fp, c_int, c_fp, c_fp, c_int, c_fp]),
-    "sdfr_nn_loss_backward": (c_int, [c_fp, c_fp, c_int, c_fp, c_int, c_fp, c_fp, c_fp, c_fp, c_int, c_fp]),
-    "sdfr_mesh_tables": (c_int, [c_fp, c_fp]),
-    "sdfr_mesh_workspace_bytes": (c_sz, [c_int, c_int, c_int]),
-    "sdfr_mesh_count": (c_int, [c_fp, c_int, c_int, c_int, c_f, c_fp, c_fp, c_sz, c_int, c_fp]),
-    "sdfr_mesh_emit": (c_int, [c_fp, c_int, c_int, c_int, c_f, c_fp, c_fp, c_fp, c_fp, c_fp, c_sz, c_int, c_fp]),
-    "sdfr_sample_workspace_bytes": (c_sz, [c_int, c_ll, c_int]),
-    "sdfr_sample_points": (c_int, [c_fp, c_int, c_ll, c_int, c_int, ctypes.c_ulonglong, c_fp, c_fp, c_fp, c_fp, c_sz,
-                                   c_int, c_fp]),
-    "sdfr_nn_workspace_bytes": (c_sz, [c_int, c_ll, c_int]),
-    "sdfr_nn_query": (c_int, [c_fp, c_fp, c_ll, c_int, c_fp, c_fp, c_ll, c_int, c_int, c_f, c_int, c_fp, c_fp, c_fp,
-                              c_sz, c_int, c_fp]),
-    "sdfr_nn_reduce": (c_int, [c_fp, c_fp, c_ll, c_int, c_fp, c_int, c_fp, c_fp, c_int, c_fp]),
-    "sdfr_encoder_create": (c_int, [c_fp, c_sz, c_int, c_int, c_int, c_fp, c_int, c_fp]),
-    "sdfr_encoder_destroy": (None, [c_fp]),
-    "sdfr_encoder_workspace_bytes": (c_sz, [c_fp, c_int]),
-    "sdfr_encoder_forward": (c_int, [c_fp, c_fp, c_int, c_fp, c_fp, c_fp, ctypes.c_ulonglong, c_fp, c_sz, c_fp]),
-    "sdfr_normal_sample": (c_int, [c_fp, c_int, c_int, ctypes.c_ulonglong, c_int, c_fp]),
-    "sdfr_clamp": (c_int, [c_fp, c_sz, c_f, c_int, c_fp]),
+# by-value C types of the ABI; any pointer is c_void_p, a returned `const char*` c_char_p, a returned `void` None
+_CTYPES = {
+    "int": ctypes.c_int,
+    "float": ctypes.c_float,
+    "size_t": ctypes.c_size_t,
+    "long long": ctypes.c_longlong,
+    "unsigned long long": ctypes.c_ulonglong,
 }
+_C_WORDS = {"const", "signed", "unsigned", "char", "short", "int", "long", "float", "double", "void"}
+_NOT_CONSTANTS = {"SDFR_H_", "SDFR_API"}   # the include guard and the export attribute
+_INT_OPS = {ast.Add: operator.add, ast.Sub: operator.sub, ast.Mult: operator.mul, ast.LShift: operator.lshift,
+            ast.BitOr: operator.or_, ast.USub: operator.neg}
+
+
+def _ctype(ctype: str, func: str, returned: bool = False):
+    words = ctype.replace("*", " * ").split()
+    if returned and words == ["const", "char", "*"]:
+        return ctypes.c_char_p
+    if "*" in words:
+        return ctypes.c_void_p
+    if returned and words == ["void"]:
+        return None
+    t = _CTYPES.get(" ".join(w for w in words if w != "const"))
+    if t is None:
+        raise ValueError(f"{func}: no ctypes type for the C type '{ctype.strip()}'")
+    return t
+
+
+def _param(param: str, func: str):
+    m = re.fullmatch(r"([\w\s*]*[\s*])([A-Za-z_]\w*)", param.strip())
+    if not m or m.group(2) in _C_WORDS:
+        raise ValueError(f"{func}: parameter '{param.strip()}' has no name")
+    return _ctype(m.group(1), func)
+
+
+def _int_expr(node, known: dict) -> int:
+    if isinstance(node, ast.Constant) and type(node.value) is int:
+        return node.value
+    if isinstance(node, ast.Name):
+        return known[node.id]
+    if isinstance(node, ast.UnaryOp) and type(node.op) in _INT_OPS:
+        return _INT_OPS[type(node.op)](_int_expr(node.operand, known))
+    if isinstance(node, ast.BinOp) and type(node.op) in _INT_OPS:
+        return _INT_OPS[type(node.op)](_int_expr(node.left, known), _int_expr(node.right, known))
+    raise ValueError(ast.dump(node))
+
+
+def parse_header(text: str):
+    """(signatures, constants) of the C ABI header `text`: {name: (restype, [argtypes])} of every ``SDFR_API``
+    declaration, and {name: int} of every ``#define`` but the include guard and ``SDFR_API``.  A macro's value is
+    an integer literal (decimal or hex, optional ``u``) or an expression of such literals and earlier macros."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    constants = {}
+    for name, value in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(\w+)(.*)$", text, re.M):
+        if name in _NOT_CONSTANTS:
+            continue
+        try:
+            expr = re.sub(r"\b(0[xX][0-9a-fA-F]+|\d+)[uU]\b", r"\1", value.strip())
+            constants[name] = _int_expr(ast.parse(expr, mode="eval").body, constants)
+        except (SyntaxError, ValueError, KeyError):
+            raise ValueError(f"#define {name}{value}: not an integer constant expression") from None
+    signatures = {}
+    declarations = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+    for decl in re.findall(r"\bSDFR_API\b([^;]*);", declarations):
+        m = re.fullmatch(r"\s*([\w\s*]+?)\s*\b(sdfr_\w+)\s*\(([^()]*)\)\s*", decl)
+        if not m:
+            raise ValueError(f"cannot read the declaration 'SDFR_API {' '.join(decl.split())};'")
+        ret, func, params = m.groups()
+        args = [] if params.strip() == "void" else [_param(p, func) for p in params.split(",")]
+        signatures[func] = (_ctype(ret, func, returned=True), args)
+    return signatures, constants
+
+
+def _read_header():
+    try:
+        with open(HEADER) as f:
+            return parse_header(f.read())
+    except FileNotFoundError:
+        raise ImportError(f"{HEADER} not found: sdfest_amd binds libsdfr_hip.so from this header and must be "
+                          "imported from the repository tree") from None
+
+
+SIGNATURES, ABI = _read_header()
 
 
 def build(verbose: bool = False) -> str:

@@ -39,13 +39,16 @@ class Camera:
         return self.fx, self.fy, self.cx + shift, self.cy + shift, self.s
 
 
-# sdf_grad_mode values (include/sdfr.h)
-SDF_GRAD_EXACT = 0
-SDF_GRAD_CUDA_COMPAT = 1
-SDF_GRAD_DETERMINISTIC = 0x100    # flag bit: integer accumulation of d/dSDF, bitwise reproducible
-FIXED_QUANTUM_BITS = 40
-BWD_HALF_GRID = 0x200             # flag bit: performance hint "every view is close" (views_are_close)
-BWD_SMALL_TILES = 0x400           # flag bit: 32 x 8 backward tiles whatever the batch (pose sums independent of it)
+# sdf_grad_mode values and flag bits (include/sdfr.h).  Flags: DETERMINISTIC, integer accumulation of d/dSDF (bitwise
+# reproducible); HALF_GRID, the performance hint "every view is close" (views_are_close); SMALL_TILES, 32 x 8 backward
+# tiles whatever the batch (pose sums independent of it).
+SDF_GRAD_EXACT = _lib.ABI["SDFR_SDF_GRAD_EXACT"]
+SDF_GRAD_CUDA_COMPAT = _lib.ABI["SDFR_SDF_GRAD_CUDA_COMPAT"]
+SDF_GRAD_DETERMINISTIC = _lib.ABI["SDFR_SDF_GRAD_DETERMINISTIC"]
+FIXED_QUANTUM_BITS = _lib.ABI["SDFR_FIXED_QUANTUM_BITS"]
+BWD_HALF_GRID = _lib.ABI["SDFR_BWD_HALF_GRID"]
+BWD_SMALL_TILES = _lib.ABI["SDFR_BWD_SMALL_TILES"]
+VIEW_RECORD_FLOATS = _lib.ABI["SDFR_VIEW_RECORD_FLOATS"]   # the sharded loop's exchange record of one view
 
 
 def parse_sdf_grad_mode(value) -> int:
@@ -62,7 +65,6 @@ def parse_sdf_grad_mode(value) -> int:
     if int(value) not in (SDF_GRAD_EXACT, SDF_GRAD_CUDA_COMPAT):
         raise ValueError(f"sdf_grad_mode {value!r}: expected 0 (exact) or 1 (cuda_compat)")
     return int(value)
-VIEW_RECORD_FLOATS = 20           # SDFR_VIEW_RECORD_FLOATS: the sharded loop's exchange record of one view
 
 
 def close_view_fraction(position, inv_scale, camera: "Camera", R: int) -> float:
@@ -181,7 +183,7 @@ def forward_raw(sdf, position, orientation, inv_scale, width, height, cx, cy, fx
 
 
 def backward_raw(grad_depth, depth, sdf, position, orientation, inv_scale, width, height, cx, cy,
-                 fx, fy, sdf_grad_mode=0):
+                 fx, fy, sdf_grad_mode=SDF_GRAD_EXACT):
     """Equivalent of ``sdf_renderer_cpp.backward`` (sdf_renderer.cpp:63-86), batched.
 
     Returns (g_sdf like sdf, g_position (B,3), g_orientation (B,4), g_inv_scale (B,)).
@@ -241,7 +243,7 @@ def step_forward_raw(sdf, position, orientation, inv_scale, width, height, cx, c
 
 
 def step_backward_raw(state, grad_depth, depth, sdf, position, orientation, inv_scale, width, height, cx, cy,
-                      fx, fy, sdf_grad_mode=0):
+                      fx, fy, sdf_grad_mode=SDF_GRAD_EXACT):
     """Second half of the step begun by ``step_forward_raw`` (same return value as ``backward_raw``).  A state
     that has been used already (a second backward through a retained graph), or a backward on another stream,
     takes the stand-alone call."""
@@ -360,12 +362,12 @@ def render_depth_gpu(sdf: torch.Tensor, position: torch.Tensor, orientation: tor
 
 
 # d depth / d sdf weights: 0 = exact (numpy twin), 1 = the CUDA kernel's permutation
-render_depth_gpu.sdf_grad_mode = 0
+render_depth_gpu.sdf_grad_mode = SDF_GRAD_EXACT
 
 
 def render_depth_batch(sdf: torch.Tensor, positions: torch.Tensor, orientations: torch.Tensor,
                        inv_scales: torch.Tensor, threshold: float, camera: Camera,
-                       sdf_grad_mode: int = 0) -> torch.Tensor:
+                       sdf_grad_mode: int = SDF_GRAD_EXACT) -> torch.Tensor:
     """B views in one launch: view b equals render_depth_gpu(sdf, positions[b], ...).
 
     The reference loops over views in Python (estimation/simple_setup.py:420-446); this is
@@ -436,7 +438,7 @@ class _RenderL1Batch(torch.autograd.Function):
 
 def render_depth_l1_batch(sdf: torch.Tensor, positions: torch.Tensor, orientations: torch.Tensor,
                           inv_scales: torch.Tensor, targets: torch.Tensor, threshold: float,
-                          camera: Camera, sdf_grad_mode: int = 0):
+                          camera: Camera, sdf_grad_mode: int = SDF_GRAD_EXACT):
     """``render_depth_batch`` and the depth term of ``SDFPipeline._compute_view_losses``
     (estimation/simple_setup.py:129-135) in one pass over the images.
 
@@ -457,7 +459,7 @@ class BatchRenderPlan:
     """
 
     def __init__(self, R: int, B: int, camera: Camera, device="cuda", per_view_sdf: bool = False,
-                 sdf_grad_mode: int = 0, grad_volumes: int = 2, close_views="auto",
+                 sdf_grad_mode: int = SDF_GRAD_EXACT, grad_volumes: int = 2, close_views="auto",
                  grad_tail_words: int = 0):
         """close_views: the ``SDFR_BWD_HALF_GRID`` hint of a step's backward -- half the workgroups when (nearly) all
         views are close (``views_are_close``); same results either way, views that are not close are slower with it.

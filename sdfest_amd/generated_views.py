@@ -156,7 +156,7 @@ def depth_to_pointsets(depth: torch.Tensor, camera: Camera, tiled: bool = False)
         counts = torch.empty(V, dtype=torch.int32, device=dev)
         ws = torch.empty(max(L.sdfr_depth_points_workspace_bytes(V, W, H), 256), dtype=torch.uint8, device=dev)
         st = torch.cuda.current_stream(dev).cuda_stream
-        order = 1 if tiled else 0
+        order = _lib.ABI["SDFR_POINT_ORDER_TILED" if tiled else "SDFR_POINT_ORDER_ROW_MAJOR"]
         _lib.check(L.sdfr_depth_count_ordered(depth.data_ptr(), V, W, H, order, counts.data_ptr(), ws.data_ptr(),
                                               ws.numel(), dev.index, st), "sdfr_depth_count")
         counts64 = counts.to(torch.int64)
@@ -221,9 +221,10 @@ def depth_to_centred_pointsets(depth: torch.Tensor, camera: Camera, noise: Optio
     centroid = torch.empty((V, 3), dtype=torch.float32, device=dev)
     ws = torch.empty(max(L.sdfr_depth_centroid_workspace_bytes(V, W, H), 256), dtype=torch.uint8, device=dev)
     st = torch.cuda.current_stream(dev).cuda_stream
-    _lib.check(L.sdfr_depth_count_centroid(depth.data_ptr(), V, W, H, 0, 1.0 / fx, 1.0 / fy, cx, cy, counts.data_ptr(),
-                                           offsets.data_ptr(), centroid.data_ptr(), ws.data_ptr(), ws.numel(),
-                                           dev.index, st), "sdfr_depth_count_centroid")
+    order = _lib.ABI["SDFR_POINT_ORDER_ROW_MAJOR"]
+    _lib.check(L.sdfr_depth_count_centroid(depth.data_ptr(), V, W, H, order, 1.0 / fx, 1.0 / fy, cx, cy,
+                                           counts.data_ptr(), offsets.data_ptr(), centroid.data_ptr(), ws.data_ptr(),
+                                           ws.numel(), dev.index, st), "sdfr_depth_count_centroid")
     noise_dev = None if noise is None else noise.to(centroid).contiguous()
     host = torch.empty(V, dtype=torch.int32).pin_memory()
     host.copy_(counts, non_blocking=True)
@@ -236,7 +237,7 @@ def depth_to_centred_pointsets(depth: torch.Tensor, camera: Camera, noise: Optio
     counts64 = counts.to(torch.int64)
     pts = torch.empty((int(counts_host.sum()), 3), dtype=torch.float32, device=dev)
     if pts.shape[0]:
-        _lib.check(L.sdfr_depth_to_points_shifted(depth.data_ptr(), V, W, H, 0, 1.0 / fx, 1.0 / fy, cx, cy,
+        _lib.check(L.sdfr_depth_to_points_shifted(depth.data_ptr(), V, W, H, order, 1.0 / fx, 1.0 / fy, cx, cy,
                                                   offsets.data_ptr(), ws.data_ptr(), centroid.data_ptr(),
                                                   noise_dev.data_ptr() if noise_dev is not None else None,
                                                   pts.data_ptr(), dev.index, st), "sdfr_depth_to_points_shifted")

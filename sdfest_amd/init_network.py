@@ -335,12 +335,13 @@ class ResidentInit:
         best = self.strategy == "best" and not self.objects
         if best:
             self.best.zero_()
+        order = _lib.ABI["SDFR_POINT_ORDER_ROW_MAJOR"]
         for v in views:
             img = depth[v]
-            _lib.check(L.sdfr_depth_count_centroid(img.data_ptr(), 1, W, H, 0, 1.0 / fx, 1.0 / fy, cx0, cy0,
+            _lib.check(L.sdfr_depth_count_centroid(img.data_ptr(), 1, W, H, order, 1.0 / fx, 1.0 / fy, cx0, cy0,
                                                    self.count.data_ptr(), self.offset1.data_ptr(), self.centroid.data_ptr(),
                                                    ws.data_ptr(), ws.numel(), d, st), "sdfr_depth_count_centroid")
-            _lib.check(L.sdfr_depth_to_points_shifted(img.data_ptr(), 1, W, H, 0, 1.0 / fx, 1.0 / fy, cx0, cy0,
+            _lib.check(L.sdfr_depth_to_points_shifted(img.data_ptr(), 1, W, H, order, 1.0 / fx, 1.0 / fy, cx0, cy0,
                                                       self.offset1.data_ptr(), ws.data_ptr(),
                                                       self.centroid.data_ptr() if self.normalize_pose else None, None,
                                                       self.points.data_ptr(), d, st), "sdfr_depth_to_points_shifted")

@@ -171,7 +171,7 @@ def extract_mesh(sdf: torch.Tensor, level: float, complete: bool = False,
     cpl = 1 if complete else 0
     ws_bytes = L.sdfr_mesh_workspace_bytes(N, R, cpl)
     if ws_bytes == 0:
-        _lib.check(-1, "sdfr_mesh_workspace_bytes")
+        _lib.check(_lib.ABI["SDFR_E_INVALID"], "sdfr_mesh_workspace_bytes")
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     totals = torch.empty((N, 4), dtype=torch.int32, device=dev)
     stream = torch.cuda.current_stream(dev).cuda_stream
@@ -249,7 +249,7 @@ def _sample(meshes: List[Mesh], n: int, seed: int, transformed: bool, normals: b
     L = _lib.lib()
     ws_bytes = L.sdfr_sample_workspace_bytes(K, off, max_f)
     if ws_bytes == 0:
-        _lib.check(-1, "sdfr_sample_workspace_bytes")
+        _lib.check(_lib.ABI["SDFR_E_INVALID"], "sdfr_sample_workspace_bytes")
     table = torch.from_numpy(rec.view(np.uint8)).pin_memory().to(dev, non_blocking=True)
     if transformed:   # the poses stay on the device: floats 11..14 and 15..17 of each record
         tab = table.view(torch.float32).view(K, _SAMPLE_RECORD.itemsize // 4)

@@ -22,8 +22,8 @@ from . import _lib
 __all__ = ["mean_accuracy", "mean_completeness", "symmetric_chamfer", "accuracy_thresh", "completeness_thresh",
            "reconstruction_fscore", "extent", "correct_thresh", "reconstruction_metrics", "evaluate_metrics", "nearest_neighbors"]
 
-_MAX_T = 4    # SDFR_NN_MAX_THRESHOLDS
-_STATS = 12   # SDFR_NN_STATS: sum, max, count, NaN count, 4 counts, 4 normalised counts
+_MAX_T = _lib.ABI["SDFR_NN_MAX_THRESHOLDS"]
+_STATS = _lib.ABI["SDFR_NN_STATS"]   # sum, max, count, NaN count, _MAX_T counts, _MAX_T normalised counts
 PointSet = Union[np.ndarray, torch.Tensor]
 
 
@@ -60,7 +60,7 @@ def _nn(q, qoff, qsizes, r, roff, rsizes, p: float, farthest: bool, dev: torch.d
     max_q, max_r = int(qsizes.max()), int(rsizes.max())
     ws_bytes = L.sdfr_nn_workspace_bytes(K, total_q, max_q)
     if ws_bytes == 0:
-        _lib.check(-1, "sdfr_nn_workspace_bytes")
+        _lib.check(_lib.ABI["SDFR_E_INVALID"], "sdfr_nn_workspace_bytes")
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     dist = torch.empty(total_q, dtype=torch.float64, device=dev)
     stream = torch.cuda.current_stream(dev).cuda_stream

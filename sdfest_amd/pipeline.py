@@ -14,7 +14,8 @@ from typing import Dict, List, Optional, Sequence
 
 import torch
 
-from .differentiable_renderer import Camera, render_depth_batch
+from . import _lib
+from .differentiable_renderer import SDF_GRAD_EXACT, Camera, render_depth_batch
 from .losses import pc_loss_batch, point_constraint_loss
 
 
@@ -91,7 +92,6 @@ def preprocess_depth(depth_images: torch.Tensor, masks: Optional[torch.Tensor], 
     its host synchronisation, and an index_put).  depth_images (N,H,W) float32 CUDA contiguous; masks: bool (or
     uint8) of the same shape, None = keep every pixel.  copy_to = (tensor (n,H,W), begin, end): the preprocessed
     images [begin, end) are also written there in the same pass (whole batch only when begin, end span it)."""
-    from . import _lib
     if not (isinstance(depth_images, torch.Tensor) and depth_images.is_cuda and depth_images.dtype is torch.float32
             and depth_images.is_contiguous() and depth_images.dim() == 3):
         raise RuntimeError("depth_images must be a contiguous float32 CUDA tensor of shape (N, H, W)")
@@ -297,8 +297,8 @@ class FusedRenderAndCompare:
                  shape_optimization: bool = True, device="cuda", fuse_depth_loss: bool = True,
                  point_constraint: Optional[Sequence] = None, track_inliers: Optional[bool] = None,
                  merge_launches: bool = True, graph_iterations: int = 5, process_group=None,
-                 exchange: str = "sdf", sdf_grad_mode: int = 0, form: str = "auto", views: Optional[int] = None,
-                 graph_collective: bool = False, defer_loss: Optional[bool] = None,
+                 exchange: str = "sdf", sdf_grad_mode: int = SDF_GRAD_EXACT, form: str = "auto",
+                 views: Optional[int] = None, graph_collective: bool = False, defer_loss: Optional[bool] = None,
                  fused_render: Optional[bool] = None, fc_in_tail: Optional[bool] = None):
         """depth_images (V,H,W): the first observation (``rebind`` takes the next ones: the reference calls its
         pipeline once per detected object with fresh images, simple_setup.py:213-225, and so re-uses nothing; this
@@ -353,7 +353,6 @@ class FusedRenderAndCompare:
         (``sdfr_views_to_pose_grad_deferred``, up to 64 views); False: one launch each.  Same numbers.
         track_inliers: run the inlier-ratio bookkeeping of :177-211 every iteration (two small launches);
         default: only for ``result_selection_strategy == "best_inlier_ratio"``."""
-        from . import _lib
         from .differentiable_renderer import BatchRenderPlan
         # True: the depth-L1 runs inside the render kernels (sdfr_render_forward_l1 / _backward_l1) and the
         # point-cloud L1 inside the sampler's backward (sdfr_pc_l1_backward);
@@ -562,9 +561,9 @@ class FusedRenderAndCompare:
                 self.cam_quat_all.copy_(camera_orientations.reshape(self.V_all, 4))
             fx, fy, cx0, cy0, _ = self.cam.get_pinhole_camera_parameters(0.0)
             self.check(L.sdfr_depth_to_points_resident(
-                self.target.data_ptr(), self.V, self.W, self.H, 1, 1.0 / fx, 1.0 / fy, cx0, cy0,
-                self.counts.data_ptr(), self.offsets.data_ptr(), self.ws_points.data_ptr(), self.ws_points.numel(),
-                self.points.data_ptr(), d, st), "sdfr_depth_to_points_resident")
+                self.target.data_ptr(), self.V, self.W, self.H, _lib.ABI["SDFR_POINT_ORDER_TILED"], 1.0 / fx,
+                1.0 / fy, cx0, cy0, self.counts.data_ptr(), self.offsets.data_ptr(), self.ws_points.data_ptr(),
+                self.ws_points.numel(), self.points.data_ptr(), d, st), "sdfr_depth_to_points_resident")
             if point_constraint is not None:
                 src, tgt, wgt = point_constraint
                 self._con_points[0:3].copy_(torch.as_tensor(src).reshape(3))
@@ -1157,8 +1156,7 @@ class MultiObjectRenderAndCompare:
     device); ``__call__`` replays captured graphs."""
 
     def __init__(self, decoder, camera: Camera, config: Dict, objects: int, shape_optimization: bool = True,
-                 device="cuda", graph_iterations: int = 5, sdf_grad_mode: int = 0):
-        from . import _lib
+                 device="cuda", graph_iterations: int = 5, sdf_grad_mode: int = SDF_GRAD_EXACT):
         from .differentiable_renderer import BatchRenderPlan
         self.L, self.check = _lib.lib(), _lib.check
         self.dec, self.cam, self.cfg = decoder, camera, config
@@ -1237,9 +1235,10 @@ class MultiObjectRenderAndCompare:
                 self.cam_quat.copy_(camera_orientation.reshape(1, 4))
             fx, fy, cx0, cy0, _ = self.cam.get_pinhole_camera_parameters(0.0)
             self.check(self.L.sdfr_depth_to_points_resident(
-                self.target.data_ptr(), self.K, self.W, self.H, 1, 1.0 / fx, 1.0 / fy, cx0, cy0, self.counts.data_ptr(),
-                self.offsets.data_ptr(), self.ws_points.data_ptr(), self.ws_points.numel(), self.points.data_ptr(),
-                self.dev.index, self._stream()), "sdfr_depth_to_points_resident")
+                self.target.data_ptr(), self.K, self.W, self.H, _lib.ABI["SDFR_POINT_ORDER_TILED"], 1.0 / fx,
+                1.0 / fy, cx0, cy0, self.counts.data_ptr(), self.offsets.data_ptr(), self.ws_points.data_ptr(),
+                self.ws_points.numel(), self.points.data_ptr(), self.dev.index, self._stream()),
+                "sdfr_depth_to_points_resident")
         self.bound = True
         return self
 

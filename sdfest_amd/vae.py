@@ -117,7 +117,8 @@ class SDFDecoder:
             self._L.sdfr_decoder_destroy(h)
             self._h = None
 
-    OPTIONS = {"fused_resize": 0, "tiled_vjp": 1, "fc_one_wave": 2, "fused_single": 3}     # SDFR_DECODER_OPT_* (include/sdfr.h)
+    OPTIONS = {name: _lib.ABI["SDFR_DECODER_OPT_" + name.upper()]      # include/sdfr.h
+               for name in ("fused_resize", "tiled_vjp", "fc_one_wave", "fused_single")}
 
     def set_option(self, name: str, value: int) -> int:
         """Select one of two equivalent kernel forms for THIS decoder (``sdfr_decoder_set_option``: same results bit
@@ -187,7 +188,7 @@ class SDFDecoder:
 # ---- encoder ------------------------------------------------------------------------------------------------------
 # reference: SDFEncoder (sdf_vae.py:103-169) builds `locate(type)(**args)` for every layer_infos entry; these are the
 # types and arguments the kernels implement (encoder.hip).  Anything else is rejected when the encoder is created.
-ENC_CONV, ENC_MAXPOOL, ENC_LINEAR, ENC_RELU = 1, 2, 3, 4          # SDFR_ENC_* (include/sdfr.h)
+ENC_CONV, ENC_MAXPOOL, ENC_LINEAR, ENC_RELU = (_lib.ABI[f"SDFR_ENC_{t}"] for t in ("CONV", "MAXPOOL", "LINEAR", "RELU"))
 _CONV_ARGS = {"in_channels", "out_channels", "kernel_size", "stride", "padding", "dilation", "groups", "bias",
               "padding_mode"}
 _POOL_ARGS = {"kernel_size", "stride", "padding", "dilation", "return_indices", "ceil_mode"}
@@ -384,7 +385,7 @@ class SDFEncoder:
         self._volume_size = int(volume_size)
         self.latent_size = int(latent_size)
         self._tsdf = tsdf
-        ops = np.ascontiguousarray(np.array(self.plan["ops"], dtype=np.int32).reshape(-1, 8))
+        ops = np.ascontiguousarray(np.array(self.plan["ops"], dtype=np.int32).reshape(-1, _lib.ABI["SDFR_ENC_OP_INTS"]))
         L = _lib.lib()
         handle = ctypes.c_void_p()
         P = lambda a: a.ctypes.data_as(ctypes.c_void_p)

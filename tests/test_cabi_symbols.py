@@ -3,6 +3,7 @@ include/sdfr.h declares (no compute calls: there is no GPU here)."""
 import ctypes
 import os
 import re
+import types
 
 import pytest
 
@@ -60,6 +61,97 @@ def test_binding_table_matches_header(libpath):
         params = m.group(1).strip()
         n = 0 if params in ("", "void") else len(params.split(","))
         assert n == len(args), (name, n, len(args))
+
+
+def test_binding_types_per_c_type():
+    """one declaration per C type the ABI uses: a wrong ctypes type passes every CPU call and breaks on the GPU"""
+    from sdfest_amd import _lib
+    vp, i, f, sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
+    ll, ull = ctypes.c_longlong, ctypes.c_ulonglong
+    assert _lib.SIGNATURES["sdfr_render_forward"] == (i, [vp, i, ll, vp, vp, vp, i, i, i, f, f, f, f, f, vp, vp, sz,
+                                                          i, vp])
+    assert _lib.SIGNATURES["sdfr_sample_points"] == (i, [vp, i, ll, i, i, ull, vp, vp, vp, vp, sz, i, vp])
+    assert _lib.SIGNATURES["sdfr_last_error"] == (ctypes.c_char_p, [])
+    assert _lib.SIGNATURES["sdfr_decoder_destroy"] == (None, [vp])
+
+
+def test_abi_constants_from_header():
+    """the header's macros that the Python side passes to the library or sizes buffers by"""
+    from sdfest_amd import _lib, metrics, vae
+    from sdfest_amd import differentiable_renderer as dr
+    assert (dr.SDF_GRAD_EXACT, dr.SDF_GRAD_CUDA_COMPAT, dr.SDF_GRAD_DETERMINISTIC, dr.FIXED_QUANTUM_BITS) == (0, 1,
+                                                                                                           0x100, 40)
+    assert (dr.BWD_HALF_GRID, dr.BWD_SMALL_TILES, dr.VIEW_RECORD_FLOATS) == (0x200, 0x400, 20)
+    assert (metrics._MAX_T, metrics._STATS, _lib.ABI["SDFR_NN_STATS"]) == (4, 12, 12)
+    assert vae.SDFDecoder.OPTIONS == {"fused_resize": 0, "tiled_vjp": 1, "fc_one_wave": 2, "fused_single": 3}
+    assert (vae.ENC_CONV, vae.ENC_MAXPOOL, vae.ENC_LINEAR, vae.ENC_RELU, _lib.ABI["SDFR_ENC_OP_INTS"]) == (1, 2, 3, 4, 8)
+    assert (_lib.ABI["SDFR_POINT_ORDER_ROW_MAJOR"], _lib.ABI["SDFR_POINT_ORDER_TILED"]) == (0, 1)
+    assert (_lib.ABI["SDFR_E_INVALID"], _lib.ABI["SDFR_SYNC_POLLS_MAGIC"]) == (-1, 0x504F4C4C)
+
+
+def test_parse_header_comments_void_and_expressions():
+    from sdfest_amd import _lib
+    text = """
+#ifndef SDFR_H_
+#define SDFR_H_
+#define SDFR_API __attribute__((visibility("default")))
+#define SDFR_A 3u                     /* unsigned */
+#define SDFR_B (-1)
+#define SDFR_C (4 + 2 * SDFR_A)       // 4 + 6, not 4
+#define SDFR_D 0x10u
+SDFR_API int sdfr_a(void);
+SDFR_API const char* sdfr_b(void);
+SDFR_API void sdfr_c(const float* x /* [n], a, b */, long long n,   // trailing, comment
+                     unsigned long long seed, size_t bytes, float t, int k);
+#endif /* SDFR_H_ */
+"""
+    signatures, constants = _lib.parse_header(text)
+    assert constants == {"SDFR_A": 3, "SDFR_B": -1, "SDFR_C": 10, "SDFR_D": 16}
+    assert signatures == {
+        "sdfr_a": (ctypes.c_int, []),
+        "sdfr_b": (ctypes.c_char_p, []),
+        "sdfr_c": (None, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_ulonglong, ctypes.c_size_t, ctypes.c_float,
+                          ctypes.c_int]),
+    }
+
+
+@pytest.mark.parametrize("text, name", [
+    ("SDFR_API int sdfr_f(int n, bool flag);", "sdfr_f"),            # a type without a ctypes mapping
+    ("SDFR_API bool sdfr_g(void);", "sdfr_g"),
+    ("SDFR_API int sdfr_h(float, int n);", "sdfr_h"),                # a parameter without a name
+    ("SDFR_API int sdfr_i(long long);", "sdfr_i"),
+    ("SDFR_API int sdfr_j(int (*fn)(int));", "sdfr_j"),              # not a form the parser reads
+    ("#define SDFR_X sizeof(int)", "SDFR_X"),
+    ("#define SDFR_Y (SDFR_LATER + 1)", "SDFR_Y"),
+])
+def test_parse_header_rejects_what_it_cannot_bind(text, name):
+    from sdfest_amd import _lib
+    with pytest.raises(ValueError, match=name):
+        _lib.parse_header(text)
+
+
+def test_integration_stub_matches_binding():
+    """INTEGRATION.md section A keeps a hand-written ctypes stub (for the reference's repository): every argtypes and
+    restype it sets is the derived table's"""
+    from sdfest_amd import _lib
+    text = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    block = re.search(r"```python\n(.*?)```", text[text.index("## A."):text.index("## B.")], re.S).group(1)
+    assert 'ctypes.CDLL("libsdfr_hip.so")' in block
+
+    class StandIn:   # in place of the loaded library: records what the stub sets on each function
+        def __getattr__(self, name):
+            setattr(self, name, types.SimpleNamespace())
+            return getattr(self, name)
+
+    lib = StandIn()
+    exec(compile(block.replace('ctypes.CDLL("libsdfr_hip.so")', "_stand_in"), "INTEGRATION.md#A", "exec"),
+         {"_stand_in": lib})
+    bound = vars(lib)
+    assert {"sdfr_render_forward", "sdfr_render_backward"} <= {n for n, fn in bound.items() if hasattr(fn, "argtypes")}
+    for name, fn in bound.items():
+        restype, argtypes = _lib.SIGNATURES[name]
+        assert getattr(fn, "argtypes", argtypes) == argtypes, name
+        assert getattr(fn, "restype", restype) is restype, name
 
 
 def test_version_and_error_string(libpath):
