@@ -930,6 +930,41 @@ SDFR_API int sdfr_normal_sample(float* out, int n, int L, unsigned long long see
 /* x[i] = min(max(x[i], -t), t) in place, t >= 0 (SDFEncoder.prepare_input: the tsdf clamp) */
 SDFR_API int sdfr_clamp(float* x, size_t count, float t, int device, void* stream);
 
+/* ==== 8. MESH DEPTH =========================================================================== */
+/* ---- depth images of triangle meshes: the reference's synthetic.draw_depth_geometry (an off-screen Open3D window) ----
+ * K images [K][H][W] in one call, image k of record k of a sdfr_sample_mesh table (the records sdfr_sample_points
+ * takes; normals and cdf_offset are not read; K poses of one mesh and K different meshes are the same call).  A posed
+ * vertex is R(quat) (factor * v) + position; the camera sits at the origin of that frame, `flags` says which frame:
+ *   SDFR_MESH_DEPTH_OPENGL  x right, y up, looking along -z (this library's renderer): the ray of pixel (row, col) is
+ *                           ((col + 0.5 - cx) / fx, -(row + 0.5 - cy) / fy, -1), depth = -z
+ *   SDFR_MESH_DEPTH_OPEN3D  x right, y down, looking along +z (the reference's draw_depth_geometry): the ray is
+ *                           ((col + 0.5 - cx) / fx, (row + 0.5 - cy) / fy, 1), depth = z
+ * (no skew; cx, cy as Camera.get_pinhole_camera_parameters(0.5) returns them).
+ * depth = the smallest z-depth (not ray length) over the triangles the pixel-centre ray meets with depth > near
+ * (near >= 0), 0 where it meets none; both faces of a triangle count; no far plane.  Coverage is decided per pixel by
+ * the ray (three scalar triple products, inclusive), never by projected vertices: a triangle that crosses the camera
+ * plane is drawn where it is in front.  The term of an edge is computed from its two vertices in one order (lower
+ * vertex index first) and negated for the triangle that walks it the other way, so two triangles that share an edge
+ * (by vertex indices) leave no pixel centre between them.  A triangle with a vertex index outside [0, num_vertices),
+ * a repeated index, a non-finite posed vertex, zero area or seen edge-on covers nothing and reads nothing out of
+ * bounds; so does a record with num_faces outside [1, max_faces] or a NULL vertices / faces pointer (an image of
+ * zeros).  triangle [K][H][W] int32 (nullable): the face that gave the depth, -1 for none; among faces of bitwise
+ * equal depth the lowest index.
+ * Bitwise reproducible: no float atomics; a triangle's depth in a pixel depends on its own three vertices, the
+ * record's pose and the pixel alone -- the same bits on every run, under any permutation of the faces, and for
+ * image k alone or among K.
+ * Workspace: 16 bytes per image (the screen rectangle of the posed mesh; tiles outside it store zeros and leave).
+ * The triangle set-up is recomputed by every 32 x 8-pixel tile inside that rectangle rather than stored per
+ * (image, triangle).  total_faces / max_faces: the sum / a bound of the records' face counts (max_faces shapes the
+ * grid).  No allocation, no host synchronisation; kernels only, so the call can be captured into a graph. */
+#define SDFR_MESH_DEPTH_OPENGL 0
+#define SDFR_MESH_DEPTH_OPEN3D 1
+SDFR_API size_t sdfr_mesh_depth_workspace_bytes(int K, long long total_faces, int max_faces, int W,
+                                                int H);   /* 0: invalid */
+SDFR_API int sdfr_mesh_depth(const sdfr_sample_mesh* meshes, int K, long long total_faces, int max_faces, int W, int H,
+                             float cx, float cy, float fx, float fy, float near, int flags, float* depth,
+                             int* triangle, void* workspace, size_t workspace_bytes, int device, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

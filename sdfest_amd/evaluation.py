@@ -1,0 +1,144 @@
+"""The synthetic-view evaluation loop on the device: what the reference's
+``estimation/scripts/rendering_evaluation.py`` does per mesh (``_generate_views``, ``_evaluate_file``,
+``_compute_metric_stats``) -- depth images of a ground-truth mesh from random cameras, ``SDFPipeline`` on them, the
+estimate's mesh, samples of both surfaces, the reconstruction metrics -- with this package's own stages
+(``render_mesh_depth``, ``SDFPipeline``, ``generate_mesh``, ``sample_points``, ``evaluate_metrics``) and no host round
+trip between them but the one the metrics end in.  Visualisation and logs are out of scope, as in ``simple_setup``.
+"""
+import math
+from typing import Dict, List, Optional, Tuple
+
+import torch
+
+from .generated_views import sample_uniform_quaternions
+from .mesh import Mesh, render_mesh_depth, sample_points
+from .metrics import evaluate_metrics
+from .pipeline import quaternion_apply, quaternion_invert, quaternion_multiply
+
+__all__ = ["view_poses", "generate_views", "evaluate_mesh", "evaluate_meshes", "metric_stats", "DEFAULT_METRICS"]
+
+# the ``metrics:`` mapping of the reference's estimation/configs/rendering_evaluation.yaml
+DEFAULT_METRICS = {
+    "mean_accuracy": {"f": "sdfest.estimation.metrics.mean_accuracy", "kwargs": {}},
+    "mean_completeness": {"f": "sdfest.estimation.metrics.mean_completeness", "kwargs": {}},
+    "chamfer": {"f": "sdfest.estimation.metrics.symmetric_chamfer", "kwargs": {}},
+    "completeness_0_01": {"f": "sdfest.estimation.metrics.completeness_thresh", "kwargs": {"threshold": 0.01}},
+    "accuracy_0_01": {"f": "sdfest.estimation.metrics.accuracy_thresh", "kwargs": {"threshold": 0.01}},
+}
+
+
+def view_poses(camera_orientations: torch.Tensor, mesh_orientation: torch.Tensor,
+               camera_distance: float) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The camera algebra of ``_generate_views`` (rendering_evaluation.py:207-231) for V cameras at once, on whatever
+    device (and in whatever dtype) the inputs are.
+
+    camera_orientations (V,4): OpenGL camera to world, scalar last.  mesh_orientation (4,): the mesh in the world; the
+    mesh sits at the world's origin.  Returns
+      camera_positions (V,3): the camera in the world, `camera_distance` away with the mesh on its principal axis;
+      mesh_positions (V,3), mesh_orientations (V,4): the mesh in each camera's Open3D frame (x right, y down, z
+      forward) -- the position is (0, 0, camera_distance)."""
+    q = camera_orientations
+    V = q.shape[0]
+    back = q.new_tensor([0.0, 0.0, -float(camera_distance)]).expand(V, 3)
+    camera_positions = -quaternion_apply(q, back)
+    o3d_to_ogl = q.new_tensor([1.0, 0.0, 0.0, 0.0]).expand(V, 4)     # the half turn about x
+    o3d_to_world = quaternion_multiply(q, o3d_to_ogl)
+    mesh_orientations = quaternion_multiply(quaternion_invert(o3d_to_world), mesh_orientation.to(q).expand(V, 4))
+    mesh_positions = q.new_tensor([0.0, 0.0, float(camera_distance)]).expand(V, 3).contiguous()
+    return camera_positions, mesh_positions, mesh_orientations
+
+
+def generate_views(mesh: Mesh, camera, num_views: int, camera_distance: float,
+                   generator: Optional[torch.Generator] = None,
+                   camera_orientations: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+    """Random views around `mesh` (``_generate_views``): uniformly distributed camera orientations, every camera
+    `camera_distance` from the mesh with the mesh on its principal axis, the mesh in its own world orientation at the
+    world's origin (its ``position`` is set to zero, as the reference sets it).
+
+    Returns the reference's dictionary, ready for ``SDFPipeline.__call__(**views)``: depth_images (V,H,W) float32,
+    masks (V,H,W) bool (= depth != 0), color_images (V,H,W,3) zeros, camera_positions (V,3), camera_orientations (V,4)
+    (OpenGL camera to world), all on the mesh's device.  All views are rendered by one ``render_mesh_depth`` call; a
+    view in which no pixel sees the mesh is drawn again with a new orientation, as the reference draws it again (one
+    host check per round of views, not per view).  camera_orientations (V,4): these orientations instead of random
+    ones (a view that sees nothing is then an error)."""
+    V = int(num_views)
+    if V < 1:
+        raise ValueError(f"num_views={num_views} must be >= 1")
+    dev = mesh.vertices.device
+    mesh.position = torch.zeros(3, device=dev)
+    H, W = int(camera.height), int(camera.width)
+    depth = torch.empty((V, H, W), dtype=torch.float32, device=dev)
+    cam_q = torch.empty((V, 4), dtype=torch.float32, device=dev)
+    cam_p = torch.empty((V, 3), dtype=torch.float32, device=dev)
+    todo = torch.arange(V, device=dev)
+    if camera_orientations is not None and tuple(camera_orientations.shape) != (V, 4):
+        raise ValueError(f"camera_orientations of shape {tuple(camera_orientations.shape)}: ({V},4) expected")
+    for _ in range(100):
+        if camera_orientations is not None:
+            q = camera_orientations.detach().to(dev, torch.float32)
+        else:
+            q = sample_uniform_quaternions(int(todo.numel()), generator).to(dev)
+        p, mesh_p, mesh_q = view_poses(q, mesh.orientation, camera_distance)
+        d = render_mesh_depth(mesh, camera, mesh_p, mesh_q, convention="open3d")
+        depth[todo], cam_q[todo], cam_p[todo] = d, q, p
+        todo = todo[~(d != 0).flatten(1).any(1)]
+        if todo.numel() == 0:       # the round's one host read
+            break
+        if camera_orientations is not None:
+            raise ValueError(f"generate_views: views {todo.tolist()} of the given camera orientations see nothing")
+    else:
+        raise RuntimeError("generate_views: the mesh cannot be seen from camera_distance "
+                           f"{camera_distance} (100 rounds of empty views)")
+    return {"depth_images": depth, "masks": depth != 0,
+            "color_images": torch.zeros((V, H, W, 3), dtype=torch.float32, device=dev),
+            "camera_positions": cam_p, "camera_orientations": cam_q}
+
+
+def evaluate_mesh(pipeline, gt_mesh: Mesh, num_views: int, camera_distance: float, samples: int, seed: int,
+                  metrics_config: Optional[dict] = None, shape_optimization: bool = True,
+                  generator: Optional[torch.Generator] = None, return_details: bool = False):
+    """``_evaluate_file`` for a mesh already loaded (``Mesh.from_file(path, scale, rel_scale, center=True)``): views of
+    `gt_mesh` -> ``pipeline(**views)`` -> ``pipeline.generate_mesh(latent, scale, complete_mesh=True)`` posed with the
+    estimate -> `samples` points of both meshes in the world with one `seed` -> the metrics of `metrics_config` (the
+    ``metrics:`` mapping of the reference's config; default: that of rendering_evaluation.yaml) as {name: float}.
+
+    With `return_details` also a dictionary of the views, the estimate (position, orientation, scale, latent), the
+    estimated mesh and both point sets."""
+    metrics_config = DEFAULT_METRICS if metrics_config is None else metrics_config
+    views = generate_views(gt_mesh, pipeline.cam, num_views, camera_distance, generator)
+    # the pipeline masks its depth argument in place; the caller's views stay as rendered
+    position, orientation, scale, latent = pipeline(**dict(views, depth_images=views["depth_images"].clone()),
+                                                    shape_optimization=shape_optimization)
+    out_mesh = pipeline.generate_mesh(latent, scale, True)
+    if out_mesh is None:
+        raise KeyError("evaluate_mesh: the pipeline's config has no iso_threshold, so it generates no mesh")
+    out_mesh.position = position[0].detach()
+    out_mesh.orientation = orientation[0].detach()
+    gt_pts = sample_points([gt_mesh], samples, seed)[0]
+    out_pts = sample_points([out_mesh], samples, seed)[0]
+    metrics = evaluate_metrics(gt_pts, out_pts, metrics_config)
+    if return_details:
+        return metrics, {"views": views, "estimate": (position, orientation, scale, latent), "mesh": out_mesh,
+                         "gt_points": gt_pts, "points": out_pts}
+    return metrics
+
+
+def metric_stats(metrics_list: List[Dict[str, float]]) -> Dict[str, Dict[str, float]]:
+    """``_compute_metric_stats``: {name: {"mean", "var" (population), "std"}} over a list of metric dictionaries"""
+    stats = {}
+    n = len(metrics_list)
+    for name in (metrics_list[0] if metrics_list else {}):
+        vals = [float(m[name]) for m in metrics_list]
+        mean = sum(vals) / n
+        var = sum((v - mean) ** 2 for v in vals) / n
+        stats[name] = {"mean": mean, "var": var, "std": math.sqrt(var)}
+    return stats
+
+
+def evaluate_meshes(pipeline, gt_meshes: List[Mesh], num_views: int, camera_distance: float, samples: int, seed: int,
+                    metrics_config: Optional[dict] = None, shape_optimization: bool = True,
+                    generator: Optional[torch.Generator] = None) -> Dict[str, Dict[str, float]]:
+    """``evaluate_mesh`` over a list of ground-truth meshes: the per-metric mean / var / std the reference's
+    ``_compute_metric_stats`` returns"""
+    return metric_stats([evaluate_mesh(pipeline, m, num_views, camera_distance, samples, seed, metrics_config,
+                                       shape_optimization, generator) for m in gt_meshes])

@@ -14,7 +14,7 @@ import torch
 from . import _lib
 from .pipeline import quaternion_apply
 
-__all__ = ["Mesh", "extract_mesh", "sample_points"]
+__all__ = ["Mesh", "extract_mesh", "sample_points", "render_mesh_depth", "draw_depth_geometry"]
 
 
 class Mesh:
@@ -134,6 +134,41 @@ class Mesh:
         pts, nrm, tri = _sample([self], number_of_points, seed, transformed, normals)
         out = (pts[0],) + ((nrm[0],) if normals else ()) + ((tri[0],) if return_triangles else ())
         return out[0] if len(out) == 1 else out
+
+    def render_depth(self, camera, position=None, orientation=None, convention: str = "opengl", near: float = 0.0,
+                     return_triangles: bool = False, out: Optional[torch.Tensor] = None):
+        """The (H,W) depth image of this mesh through `camera` at the origin (``render_mesh_depth`` for one mesh):
+        at its own pose, or at `position` (3,) / `orientation` (4,) where given."""
+        pos = None if position is None else torch.as_tensor(position, dtype=torch.float32).reshape(1, 3)
+        ori = None if orientation is None else torch.as_tensor(orientation, dtype=torch.float32).reshape(1, 4)
+        res = render_mesh_depth(self, camera, pos, ori, convention, near, return_triangles,
+                                None if out is None else out.view((1,) + tuple(out.shape)))
+        return (res[0][0], res[1][0]) if return_triangles else res[0]
+
+    @classmethod
+    def from_file(cls, path: str, scale: float = 1, rel_scale: bool = False, center: bool = False,
+                  device="cuda") -> "Mesh":
+        """The reference's ``synthetic.Mesh(path=...)`` (synthetic.py:41-76) without Open3D: a Wavefront OBJ (``v``
+        and ``f`` lines; corners written ``i``, ``i/j``, ``i/j/k`` or ``i//k``; negative indices count from the last
+        vertex read so far; polygons become triangle fans; everything else is skipped) or a PLY as ``write_ply``
+        writes it (binary little-endian or ascii; float x y z, optional nx ny nz, lists of vertex indices).  Vertex
+        normals are kept where the file has one per vertex (a PLY's nx ny nz; an OBJ whose corners all read
+        ``i//i``).  center: the vertex mean goes to the origin before the scale applies (Open3D's
+        ``translate([0, 0, 0], relative=False)``).  `scale` / `rel_scale` as ``update_scale``.  Parsed with numpy on
+        the host."""
+        with open(path, "rb") as fh:
+            head = fh.read(4)
+        v, f, n = _read_ply(path) if head[:3] == b"ply" else _read_obj(path)
+        if len(f) and (f.min() < 0 or f.max() >= len(v)):
+            raise ValueError(f"{path}: a face refers to vertex {int(f.max() if f.max() >= len(v) else f.min())} "
+                             f"of {len(v)}")
+        if center and len(v):
+            v = v - v.mean(axis=0)
+        dev = torch.device(device)
+        return cls(torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)).to(dev),
+                   torch.from_numpy(np.ascontiguousarray(f, dtype=np.int32).reshape(-1, 3)).to(dev),
+                   None if n is None else torch.from_numpy(np.ascontiguousarray(n, dtype=np.float32)).to(dev),
+                   scale=scale, rel_scale=rel_scale)
 
     def __repr__(self) -> str:
         return (f"Mesh(V={self.vertices.shape[0]}, F={self.faces.shape[0]}, scale={self.scale}, "
@@ -272,3 +307,218 @@ def sample_points(meshes: List[Mesh], number_of_points: int, seed: int = 0, tran
     """``Mesh.sample_points_uniformly`` for K meshes in one launch sequence: (K, number_of_points, 3) float32.  Mesh k's
     points equal ``meshes[k].sample_points_uniformly(number_of_points, seed, transformed)`` bit for bit."""
     return _sample(list(meshes), number_of_points, seed, transformed, False)[0]
+
+
+# ---- files ------------------------------------------------------------------------------------------------------------
+def _read_obj(path: str):
+    """(vertices (V,3) float64, faces (F,3) int64 zero-based, normals (V,3) or None) of a Wavefront OBJ"""
+    verts, norms, faces, fnorm = [], [], [], []
+    with open(path, "r", errors="replace") as fh:
+        for line in fh:
+            tok = line.split("#", 1)[0].split()
+            if not tok:
+                continue
+            if tok[0] == "v":
+                verts.append([float(x) for x in tok[1:4]])
+            elif tok[0] == "vn":
+                norms.append([float(x) for x in tok[1:4]])
+            elif tok[0] == "f":
+                vi, ni = [], []
+                for corner in tok[1:]:
+                    parts = corner.split("/")
+                    i = int(parts[0])
+                    vi.append(i - 1 if i > 0 else len(verts) + i)
+                    k = int(parts[2]) if len(parts) > 2 and parts[2] else 0
+                    ni.append(k - 1 if k > 0 else (len(norms) + k if k < 0 else -1))
+                if len(vi) < 3:
+                    raise ValueError(f"{path}: a face with {len(vi)} corners")
+                for j in range(1, len(vi) - 1):     # a fan about the first corner
+                    faces.append([vi[0], vi[j], vi[j + 1]])
+                    fnorm.append([ni[0], ni[j], ni[j + 1]])
+    v = np.asarray(verts, dtype=np.float64).reshape(-1, 3)
+    f = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
+    n = None
+    if len(norms) == len(v) and len(f) and np.array_equal(np.asarray(fnorm, dtype=np.int64), f):
+        n = np.asarray(norms, dtype=np.float64).reshape(-1, 3)
+    return v, f, n
+
+
+_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2",
+              "uint16": "u2", "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4",
+              "double": "f8", "float64": "f8"}
+
+
+def _read_ply(path: str):
+    """(vertices, faces, normals or None) of a PLY with a vertex element (scalar properties, x y z among them) followed
+    by a face element whose one property is the list of vertex indices"""
+    with open(path, "rb") as fh:
+        data = fh.read()
+    end = data.find(b"end_header")
+    if end < 0:
+        raise ValueError(f"{path}: no end_header")
+    body = data[data.index(b"\n", end) + 1:]
+    fmt, elements = None, []
+    for line in data[:end].decode("ascii", errors="replace").splitlines():
+        tok = line.split()
+        if not tok:
+            continue
+        if tok[0] == "format":
+            fmt = tok[1]
+        elif tok[0] == "element":
+            elements.append((tok[1], int(tok[2]), []))
+        elif tok[0] == "property" and elements:
+            elements[-1][2].append(tok[1:])
+    if fmt not in ("binary_little_endian", "ascii") or [e[0] for e in elements[:2]] != ["vertex", "face"]:
+        raise ValueError(f"{path}: a binary little-endian or ascii PLY with a vertex and a face element is expected")
+    (_, nv, vprops), (_, nf, fprops) = elements[:2]
+    if any(p[0] == "list" for p in vprops) or len(fprops) != 1 or fprops[0][0] != "list":
+        raise ValueError(f"{path}: scalar vertex properties and one face index list are expected")
+    names = [p[1] for p in vprops]
+    ctype, itype = _PLY_TYPES[fprops[0][1]], _PLY_TYPES[fprops[0][2]]
+    if fmt == "ascii":
+        rows = [ln.split() for ln in body.decode("ascii").splitlines() if ln.strip()]
+        vert = {nm: np.array([float(r[j]) for r in rows[:nv]]) for j, nm in enumerate(names)}
+        polys = [[int(x) for x in r[1:1 + int(r[0])]] for r in rows[nv:nv + nf]]
+    else:
+        vdt = np.dtype([(nm, "<" + _PLY_TYPES[p[0]]) for nm, p in zip(names, vprops)])
+        rec = np.frombuffer(body, dtype=vdt, count=nv)
+        vert = {nm: rec[nm].astype(np.float64) for nm in names}
+        rest = body[nv * vdt.itemsize:]
+        tri = np.dtype([("n", "<" + ctype), ("i", "<" + itype, (3,))])
+        polys = None
+        if len(rest) >= nf * tri.itemsize:    # all triangles (what write_ply writes): one read
+            cand = np.frombuffer(rest, dtype=tri, count=nf)
+            if nf == 0 or (cand["n"] == 3).all():
+                polys = cand["i"].astype(np.int64)
+        if polys is None:
+            polys, o = [], 0
+            cs, isz = np.dtype(ctype).itemsize, np.dtype(itype).itemsize
+            for _ in range(nf):
+                c = int(np.frombuffer(rest, dtype="<" + ctype, count=1, offset=o)[0])
+                polys.append(np.frombuffer(rest, dtype="<" + itype, count=c, offset=o + cs).astype(np.int64).tolist())
+                o += cs + c * isz
+    if isinstance(polys, list):
+        polys = [[p[0], p[j], p[j + 1]] for p in polys for j in range(1, len(p) - 1)]
+    v = np.stack([vert["x"], vert["y"], vert["z"]], 1).reshape(-1, 3)
+    n = np.stack([vert["nx"], vert["ny"], vert["nz"]], 1) if all(k in vert for k in ("nx", "ny", "nz")) else None
+    return v, np.asarray(polys, dtype=np.int64).reshape(-1, 3), n
+
+
+# ---- depth images -----------------------------------------------------------------------------------------------------
+_CONVENTIONS = {"opengl": "SDFR_MESH_DEPTH_OPENGL", "open3d": "SDFR_MESH_DEPTH_OPEN3D", "opencv": "SDFR_MESH_DEPTH_OPEN3D"}
+
+
+def render_mesh_depth(meshes: Union[Mesh, List[Mesh]], camera, positions: Optional[torch.Tensor] = None,
+                      orientations: Optional[torch.Tensor] = None, convention: str = "opengl", near: float = 0.0,
+                      return_triangles: bool = False, out: Optional[torch.Tensor] = None):
+    """Depth images of triangle meshes on the GPU (``sdfr_mesh_depth``, csrc/raster.hip): per pixel the smallest z-depth
+    over the triangles its centre ray meets with depth > `near`, 0 where it meets none (the reference's ``depth != 0``
+    mask convention); both faces of a triangle count, there is no far plane.
+
+    meshes: a ``Mesh`` or a list of K.  positions (V,3) / orientations (V,4): poses that replace the meshes' own -- one
+    mesh and V poses give (V,H,W), K meshes take K poses; without them every mesh is drawn at its own pose.  The mesh's
+    scale (``_factor``) always applies.  The camera sits at the origin of the frame the poses refer to; convention
+    "opengl" (x right, y up, looking along -z: ``render_depth_gpu``'s frame) or "open3d" / "opencv" (x right, y down,
+    looking along +z: the reference's ``draw_depth_geometry``).  `camera.s` (skew) must be 0.  out: a (K,H,W) float32
+    buffer to write into.  An empty mesh gives an image of zeros.  Returns the (K,H,W) depth; with `return_triangles`
+    also the (K,H,W) int32 face index behind every pixel (-1: none).  One launch sequence for all images, nothing read
+    back; poses given as device tensors stay on the device."""
+    if convention not in _CONVENTIONS:
+        raise ValueError(f"convention {convention!r}: expected one of {sorted(_CONVENTIONS)}")
+    fx, fy, cx, cy, s = camera.get_pinhole_camera_parameters(0.5)
+    if s != 0:
+        raise ValueError(f"camera skew s={s} is not supported (only s = 0)")
+    near = float(near)
+    if not (0.0 <= near < float("inf")):
+        raise ValueError(f"near={near} must be >= 0 and finite")
+    meshes = [meshes] if isinstance(meshes, Mesh) else list(meshes)
+    if not meshes:
+        raise ValueError("no meshes to render")
+    dev = meshes[0].vertices.device
+    if dev.type != "cuda":
+        raise TypeError("meshes must live on a CUDA device (sdfest_amd has no CPU path)")
+    for name, t, w in (("positions", positions, 3), ("orientations", orientations, 4)):
+        if t is not None and (t.dim() != 2 or t.shape[1] != w):
+            raise ValueError(f"{name} of shape {tuple(t.shape)}: (V,{w}) expected")
+    V = next((int(t.shape[0]) for t in (positions, orientations) if t is not None), None)
+    if positions is not None and orientations is not None and positions.shape[0] != orientations.shape[0]:
+        raise ValueError(f"{positions.shape[0]} positions for {orientations.shape[0]} orientations")
+    if V is not None and len(meshes) == 1:
+        meshes = meshes * V
+    elif V is not None and V != len(meshes):
+        raise ValueError(f"{V} poses for {len(meshes)} meshes (one pose per mesh, or one mesh)")
+    K = len(meshes)
+    W, H = int(camera.width), int(camera.height)
+    if out is not None:
+        if tuple(out.shape) != (K, H, W) or out.dtype != torch.float32 or out.device != dev or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous ({K},{H},{W}) float32 tensor on {dev}")
+        depth = out
+    else:
+        depth = torch.empty((K, H, W), dtype=torch.float32, device=dev)
+    tri = torch.empty((K, H, W), dtype=torch.int32, device=dev) if return_triangles else None
+
+    rec = np.zeros(K, dtype=_SAMPLE_RECORD)
+    keep, cache, total, max_f = [], {}, 0, 0
+    for k, m in enumerate(meshes):
+        if m.vertices.device != dev:
+            raise ValueError("all meshes must live on one device")
+        F = int(m.faces.shape[0]) if m.vertices.shape[0] else 0
+        rec[k]["factor"], rec[k]["quat"] = m._factor, (0.0, 0.0, 0.0, 1.0)
+        if F == 0:
+            continue     # num_faces = 0: the kernel stores an image of zeros
+        if id(m) not in cache:
+            cache[id(m)] = (m.vertices.detach().to(torch.float32).contiguous(),
+                            m.faces.detach().to(torch.int32).contiguous())
+            keep.append(cache[id(m)])
+        v, f = cache[id(m)]
+        rec[k]["vertices"], rec[k]["faces"] = v.data_ptr(), f.data_ptr()
+        rec[k]["cdf_offset"], rec[k]["num_vertices"], rec[k]["num_faces"] = total, v.shape[0], F
+        total += F
+        max_f = max(max_f, F)
+    if total == 0:
+        depth.zero_()
+        if tri is not None:
+            tri.fill_(-1)
+        return (depth, tri) if return_triangles else depth
+    table = torch.from_numpy(rec.view(np.uint8)).pin_memory().to(dev, non_blocking=True)
+    tab = table.view(torch.float32).view(K, _SAMPLE_RECORD.itemsize // 4)   # poses: floats 11..14 and 15..17
+    if orientations is not None:
+        tab[:, 11:15] = orientations.detach().to(dev, torch.float32)
+    else:
+        tab[:, 11:15] = torch.stack([m.orientation.detach().to(dev, torch.float32) for m in meshes])
+    if positions is not None:
+        tab[:, 15:18] = positions.detach().to(dev, torch.float32)
+    else:
+        tab[:, 15:18] = torch.stack([m.position.detach().to(dev, torch.float32) for m in meshes])
+    _mesh_depth_launch(table, total, max_f, (cx, cy, fx, fy), near, _lib.ABI[_CONVENTIONS[convention]], depth, tri)
+    del keep   # as in _sample: freed tensors are reused only by later work on this stream
+    return (depth, tri) if return_triangles else depth
+
+
+def _mesh_depth_launch(table: torch.Tensor, total_faces: int, max_faces: int, intrinsics, near: float, flags: int,
+                       depth: torch.Tensor, triangles: Optional[torch.Tensor] = None,
+                       workspace: Optional[torch.Tensor] = None) -> None:
+    """``sdfr_mesh_depth`` on a device table of K 72-byte records into depth (K,H,W): kernels on the current stream
+    and nothing else, so with a `workspace` made beforehand (``sdfr_mesh_depth_workspace_bytes``) the call can be
+    captured into a graph and replayed after the table's poses were rewritten in place"""
+    dev = depth.device
+    K, H, W = (int(x) for x in depth.shape)
+    cx, cy, fx, fy = intrinsics
+    L = _lib.lib()
+    ws_bytes = L.sdfr_mesh_depth_workspace_bytes(K, total_faces, max_faces, W, H)
+    if ws_bytes == 0:
+        _lib.check(_lib.ABI["SDFR_E_INVALID"], "sdfr_mesh_depth_workspace_bytes")
+    ws = workspace if workspace is not None else torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(L.sdfr_mesh_depth(_ptr(table), K, total_faces, max_faces, W, H, cx, cy, fx, fy, near, flags,
+                                     _ptr(depth), _ptr(triangles) if triangles is not None else None, _ptr(ws),
+                                     ws.numel(), dev.index, torch.cuda.current_stream(dev).cuda_stream),
+                   "sdfr_mesh_depth")
+
+
+def draw_depth_geometry(obj: Mesh, camera) -> torch.Tensor:
+    """The reference's ``synthetic.draw_depth_geometry(obj, camera)`` (synthetic.py:142-171): the (H,W) float32 depth
+    image, on the device, of `obj` at its own pose in the Open3D camera frame (the camera at the origin, x right, y
+    down, looking along +z), 0 where no triangle is seen, back faces shown.  Skew (``camera.s != 0``) raises
+    ``ValueError``: the rasteriser has no skew term, as ``ray_setup`` in render.hip has none."""
+    return render_mesh_depth(obj, camera, convention="open3d")[0]
