@@ -38,11 +38,11 @@
  *   (sdf_view_stride = R*R*R elements).
  *
  * STABILITY -- group 1 below is the boundary: its signatures and semantics are what a binding relies on and do not change
- * without SDFR_VERSION's major number changing.  Groups 2 - 7 are UNSTABLE: they exist for this repository's own host
+ * without SDFR_VERSION's major number changing.  Groups 2 - 9 are UNSTABLE: they exist for this repository's own host
  * code (the Python modules under sdfest_amd/), follow its needs from round to round (arguments were added in every round so far), and are
  * exported only because that host code is Python over ctypes; bind to them at your own risk, pinned to one SDFR_VERSION.
  *
- * CONTENTS -- seven groups; a binding from another language needs group 1 only
+ * CONTENTS -- nine groups; a binding from another language needs group 1 only
  *   1. CORE: the reference boundary (what sdf_renderer_cpp, losses.pc_loss and SDFDecoder.forward are replaced by)
  *        sdfr_version, sdfr_last_error
  *        sdfr_render_forward[_workspace_bytes], sdfr_render_backward[_workspace_bytes]
@@ -73,6 +73,10 @@
  *        sdfr_sample_workspace_bytes, sdfr_sample_points, sdfr_nn_workspace_bytes, sdfr_nn_query, sdfr_nn_reduce
  *   7. [unstable] ENCODER: the VAE's encoder half (SDFVAE.encode / forward / sample / prepare_input)
  *        sdfr_encoder_create / _destroy / _workspace_bytes / _forward, sdfr_normal_sample, sdfr_clamp
+ *   8. [unstable] MESH DEPTH: depth images of triangle meshes (the synthetic views of the evaluation)
+ *        sdfr_mesh_depth_workspace_bytes, sdfr_mesh_depth
+ *   9. [unstable] MESH TO SDF: the signed distance volume of a triangle mesh (what the VAE is trained on and encodes)
+ *        sdfr_mesh_sdf_workspace_bytes, sdfr_mesh_sdf
  * (Within the file the groups follow the order in which the reference's code runs; every declaration carries the
  * reference file:line it replaces.)
  */
@@ -964,6 +968,44 @@ SDFR_API size_t sdfr_mesh_depth_workspace_bytes(int K, long long total_faces, in
 SDFR_API int sdfr_mesh_depth(const sdfr_sample_mesh* meshes, int K, long long total_faces, int max_faces, int W, int H,
                              float cx, float cy, float fx, float fy, float near, int flags, float* depth,
                              int* triangle, void* workspace, size_t workspace_bytes, int device, void* stream);
+
+/* ==== 9. MESH TO SDF ========================================================================== */
+/* ---- the distance volume of a triangle mesh: the reference's vae/sdf_utils.py::mesh_to_sdf (the external mesh_to_sdf
+ * package: distances to a scanned point cloud, signs from depth buffers), computed exactly ------------------------------
+ * K volumes sdf [K][R][R][R] in one call, volume k of record k of a sdfr_sample_mesh table (normals and cdf_offset are
+ * not read).  A posed vertex is R(quat) (factor * v) + position, as in sdfr_sample_points and sdfr_mesh_depth; grid
+ * point (i, j, k) = sdf[i][j][k] sits at ((2 i - (R - 1)) / (R - 1), ...) in that frame: index idx of an axis at
+ * (idx - (R - 1) / 2) * 2 / (R - 1), the corners at -1 and 1, the frame and axis order of sdfr_mesh_emit and of the
+ * renderer.  2 <= R <= 256.
+ *   |sdf|   the Euclidean distance to the closest point of any valid triangle -- in the face, on an edge or at a
+ *           vertex (the closest point by Voronoi region, not a plane distance).  fp32, no contraction; a pair's squared
+ *           distance depends on the grid point and the face's three posed vertices, taken in ascending INDEX order,
+ *           alone; the minimum over the faces is exact, ties go to the lowest face, the square root is taken once.
+ *   sign    w = (1 / 4 pi) sum_t Omega_t,  Omega_t = 2 atan2(A . (B x C), |A||B||C| + (A . B)|C| + (B . C)|A| + (C . A)|B|)
+ *           with A, B, C the face's vertices minus the point: every term in fp32, the sum in fp64 in ascending face
+ *           order.  A point is inside (sdf < 0) iff w > 0.5.  Faces are oriented as Mesh documents: (b - a) x (c - a)
+ *           points out of the object.
+ *   flags   SDFR_MESH_SDF_SIGNED, or SDFR_MESH_SDF_UNSIGNED: no winding work, the output is |signed output| bit for bit
+ *           (winding must then be NULL).
+ *   triangle [K][R^3] int32 (nullable): the closest face, -1 for none.  winding [K][R^3] float (nullable): w, for
+ *           diagnosing meshes that are not closed (then w is neither 0 nor 1 and the sign near 0.5 means little).
+ * A triangle with a vertex index outside [0, num_vertices), a repeated index, a non-finite posed vertex or zero area
+ * contributes neither distance nor winding and reads nothing out of bounds.  A record without a valid face, with a NULL
+ * vertices / faces pointer, with num_faces outside [1, max_faces], or whose faces do not fit into total_faces gives a
+ * volume of NaN (winding NaN, triangle -1), as the sampler does.
+ * Bitwise reproducible: no float atomics; volume k is the same bits on every run, alone or among K, at any position in
+ * the table.  The unsigned field and `triangle` do not depend on the order of the faces (up to the permutation); the
+ * signed field's sign is not promised to be so, its sum being ordered.
+ * Workspace: 16 bytes per record (rounded up to 64) + 64 bytes per face of total_faces: every face is posed once.
+ * total_faces / max_faces: the sum / a bound of the records' face counts (max_faces shapes the set-up's grid).  No
+ * allocation, no host synchronisation; kernels only, so the call can be captured into a graph.  Work: K R^3 max_faces
+ * point-triangle pairs, brute force. */
+#define SDFR_MESH_SDF_SIGNED 0
+#define SDFR_MESH_SDF_UNSIGNED 1
+SDFR_API size_t sdfr_mesh_sdf_workspace_bytes(int K, long long total_faces, int max_faces, int R);   /* 0: invalid */
+SDFR_API int sdfr_mesh_sdf(const sdfr_sample_mesh* meshes, int K, long long total_faces, int max_faces, int R, int flags,
+                           float* sdf, int* triangle, float* winding, void* workspace, size_t workspace_bytes,
+                           int device, void* stream);
 
 #ifdef __cplusplus
 }

@@ -11,11 +11,13 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from .generated_views import sample_uniform_quaternions
-from .mesh import Mesh, render_mesh_depth, sample_points
+from .mesh import Mesh, extract_mesh, render_mesh_depth, sample_points
 from .metrics import evaluate_metrics
 from .pipeline import quaternion_apply, quaternion_invert, quaternion_multiply
+from .sdf_utils import mesh_to_sdf, normalized_mesh
 
-__all__ = ["view_poses", "generate_views", "evaluate_mesh", "evaluate_meshes", "metric_stats", "DEFAULT_METRICS"]
+__all__ = ["view_poses", "generate_views", "evaluate_mesh", "evaluate_meshes", "vae_reconstruction", "metric_stats",
+           "DEFAULT_METRICS"]
 
 # the ``metrics:`` mapping of the reference's estimation/configs/rendering_evaluation.yaml
 DEFAULT_METRICS = {
@@ -121,6 +123,35 @@ def evaluate_mesh(pipeline, gt_mesh: Mesh, num_views: int, camera_distance: floa
         return metrics, {"views": views, "estimate": (position, orientation, scale, latent), "mesh": out_mesh,
                          "gt_points": gt_pts, "points": out_pts}
     return metrics
+
+
+def vae_reconstruction(vae, gt_mesh: Mesh, samples: int, seed: int, metrics_config: Optional[dict] = None,
+                       level: float = 0.0, cells_per_dim: int = 64, padding: int = 0, return_details: bool = False):
+    """The shape prior's ceiling next to ``evaluate_mesh``: how well the VAE alone reproduces `gt_mesh`, with no views
+    and no optimisation.  ``mesh_to_sdf(gt_mesh, cells_per_dim, padding)`` (the reference's framing: the volume the
+    VAE was trained on) -> ``vae.prepare_input`` -> the encoder's means (no sample is drawn) -> ``vae.decode`` ->
+    ``extract_mesh(..., level, complete=True)`` -> `samples` points of the ground truth in that same normalised frame
+    (``normalized_mesh``) and of the reconstruction with one `seed` -> the metrics of `metrics_config` (default: that
+    of rendering_evaluation.yaml).  `cells_per_dim` must be the VAE's ``sdf_size``.
+
+    Returns ({name: float}, latent (1, latent_size)); with `return_details` also a dictionary of the input volume, the
+    decoded volume, the reconstructed mesh and both point sets."""
+    metrics_config = DEFAULT_METRICS if metrics_config is None else metrics_config
+    R = int(cells_per_dim)
+    with torch.no_grad():
+        grid = mesh_to_sdf(gt_mesh, R, padding).view(1, 1, R, R, R)
+        x = grid.clone() if return_details else grid
+        vae.prepare_input(x)
+        latent, _ = vae.encoder(x)
+        recon = vae.decode(latent)
+        out_mesh = extract_mesh(recon[0, 0], level, complete=True)
+    gt_pts = sample_points([normalized_mesh(gt_mesh, R, padding)], samples, seed)[0]
+    out_pts = sample_points([out_mesh], samples, seed)[0]
+    metrics = evaluate_metrics(gt_pts, out_pts, metrics_config)
+    if return_details:
+        return metrics, latent, {"sdf": grid[0, 0], "reconstruction": recon[0, 0], "mesh": out_mesh,
+                                 "gt_points": gt_pts, "points": out_pts}
+    return metrics, latent
 
 
 def metric_stats(metrics_list: List[Dict[str, float]]) -> Dict[str, Dict[str, float]]:

@@ -145,6 +145,13 @@ class Mesh:
                                 None if out is None else out.view((1,) + tuple(out.shape)))
         return (res[0][0], res[1][0]) if return_triangles else res[0]
 
+    def to_sdf(self, cells_per_dim: int = 64, padding: int = 0, normalize: bool = True, signed: bool = True,
+               return_triangles: bool = False, return_winding: bool = False, out: Optional[torch.Tensor] = None):
+        """The (R,R,R) SDF volume of this mesh (``sdf_utils.mesh_to_sdf`` for one mesh): exact distances, signed by
+        the generalised winding number, on the GPU."""
+        from .sdf_utils import mesh_to_sdf
+        return mesh_to_sdf(self, cells_per_dim, padding, normalize, signed, return_triangles, return_winding, out)
+
     @classmethod
     def from_file(cls, path: str, scale: float = 1, rel_scale: bool = False, center: bool = False,
                   device="cuda") -> "Mesh":
