@@ -1007,6 +1007,62 @@ SDFR_API int sdfr_mesh_sdf(const sdfr_sample_mesh* meshes, int K, long long tota
                            float* sdf, int* triangle, float* winding, void* workspace, size_t workspace_bytes,
                            int device, void* stream);
 
+/* ==== 10. VAE TRAINING ======================================================================== */
+/* ---- one iteration of the reference's trainer (sdfest/vae/scripts/train.py:195-287): forward with a tape, the loss
+ * and its gradient, the gradient of every parameter, Adam ------------------------------------------------------------
+ * A trainer handle describes the network only: the decoder as sdfr_decoder_create takes it, the encoder's op list as
+ * sdfr_encoder_create takes it (the same checks, the same messages).  It holds no parameters and no device memory;
+ * creation makes no HIP call.
+ * PARAMETERS live in one flat fp32 device buffer of sdfr_vae_trainer_param_count floats that the caller owns, in
+ * state_dict order and torch's layouts: sdfr_encoder_create's h_params followed by sdfr_decoder_create's h_params.
+ * The gradient and Adam's two moments are buffers of the same length and layout.
+ *   forward   x [N][D^3] (clamped IN PLACE to +-tsdf when post != 0 and tsdf > 0: prepare_input) -> means, log_var,
+ *             z [N][L] (z = eps * exp(0.5 log_var) + means, eps the stream of group 7: counter {i, j, 0, 0x56414531}),
+ *             recon [N][D^3] = decoder(z) without the tsdf clamp, and in `tape` every layer output the backward reads.
+ *   loss      train.py:208-229, :271-281.  post != 0 and tsdf > 0: recon is clamped to +-tsdf where |x| >= tsdf and
+ *             |recon| >= tsdf.  e1 = |recon - x|, e2 = e1^2, small = |x| < 0.1; terms [6] = {l2_small, l2_large,
+ *             l1_small, l1_large, kld, total} (sums, not means; kld = -0.5 sum(1 + log_var - means^2 - exp(log_var));
+ *             total = the four weighted terms + kld * (post ? w_kld : 0)).  g_recon [N][D^3] = d total / d recon (0
+ *             where the clamp cuts); g_means, g_log_var [N][L] = the KLD's direct share of d total / d means, log_var.
+ *   backward  the gradient of `total` w.r.t. every parameter into grads (every element is written): through the
+ *             decoder (Linear, ReLU, trilinear resize, Conv3d) to z, through z = eps exp(0.5 log_var) + means into the
+ *             heads, through the encoder (Linear, MaxPool3d with its argmax recomputed: the first maximum of a window,
+ *             ReLU, Conv3d; no gradient w.r.t. x).  Takes the x, seed, log_var, z, tape and recon of the forward.
+ * Every output element has one owner and a fixed summation order, no float atomics: the same inputs give the same
+ * bits on every run.  The long sums (the loss terms over N D^3 voxels, a convolution's weight and bias gradient over
+ * N S^3 positions) are two-stage: partial sums per workgroup in the workspace, then a combine in fixed order (in fp64).
+ * No allocation, no host synchronisation; kernels only, on the caller's stream.  1 <= N <= 65535. */
+typedef struct sdfr_vae_trainer sdfr_vae_trainer;
+SDFR_API int sdfr_vae_trainer_create(int latent, int n_fc, const int* fc_out, int n_conv, const int* conv_in_size,
+                                     const int* conv_cin, const int* conv_cout, const int* conv_k,
+                                     const int* conv_relu, int volume, float tsdf, int n_ops, const int* h_ops,
+                                     int device, sdfr_vae_trainer** out_handle);
+SDFR_API void sdfr_vae_trainer_destroy(sdfr_vae_trainer* trainer);
+/* floats of the flat parameter buffer, and of its encoder part (the decoder's parameters start there); 0: NULL */
+SDFR_API size_t sdfr_vae_trainer_param_count(const sdfr_vae_trainer* trainer);
+SDFR_API size_t sdfr_vae_trainer_encoder_param_count(const sdfr_vae_trainer* trainer);
+SDFR_API size_t sdfr_vae_trainer_tape_bytes(const sdfr_vae_trainer* trainer, int N);        /* 0: NULL or N < 1 */
+SDFR_API size_t sdfr_vae_trainer_workspace_bytes(const sdfr_vae_trainer* trainer, int N);   /* loss and backward */
+SDFR_API int sdfr_vae_trainer_forward(const sdfr_vae_trainer* trainer, const float* params, float* x, int N,
+                                      unsigned long long seed, int post, float* means, float* log_var, float* z,
+                                      float* recon, float* tape, size_t tape_bytes, void* stream);
+SDFR_API int sdfr_vae_trainer_loss(const sdfr_vae_trainer* trainer, const float* recon, const float* x,
+                                   const float* means, const float* log_var, int N, float w_l2_small,
+                                   float w_l2_large, float w_l1_small, float w_l1_large, float w_kld, int post,
+                                   float* terms, float* g_recon, float* g_means, float* g_log_var, void* workspace,
+                                   size_t workspace_bytes, void* stream);
+SDFR_API int sdfr_vae_trainer_backward(const sdfr_vae_trainer* trainer, const float* params, const float* x, int N,
+                                       unsigned long long seed, const float* log_var, const float* z,
+                                       const float* tape, const float* recon, const float* g_recon,
+                                       const float* g_means, const float* g_log_var, float* grads, void* workspace,
+                                       size_t workspace_bytes, void* stream);
+/* One torch.optim.Adam step (default betas 0.9 / 0.999, eps 1e-8, no weight decay, no amsgrad) over a flat buffer of n
+ * floats: exp_avg += (g - exp_avg) (1 - b1); exp_avg_sq = b2 exp_avg_sq + (1 - b2) g g; p += -(lr / (1 - b1^t)) exp_avg
+ * / (sqrt(exp_avg_sq) / sqrt(1 - b2^t) + eps), the bias corrections in fp64 as torch forms them.  step[0] (device int)
+ * is the number of steps taken so far and is incremented.  None of sdfr_adam_step's pose handling. */
+SDFR_API int sdfr_adam_flat(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int* step, size_t n,
+                            double lr, int device, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

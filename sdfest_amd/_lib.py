@@ -25,6 +25,7 @@ _lib = None
 _CTYPES = {
     "int": ctypes.c_int,
     "float": ctypes.c_float,
+    "double": ctypes.c_double,
     "size_t": ctypes.c_size_t,
     "long long": ctypes.c_longlong,
     "unsigned long long": ctypes.c_ulonglong,

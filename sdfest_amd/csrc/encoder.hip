@@ -51,7 +51,6 @@ constexpr int kMaxLatent = 512;
 constexpr int kChainThreads = 512;
 constexpr int kLayerThreads = 256;
 constexpr size_t kChainLdsMax = 152 * 1024;     // dynamic; + the heads' 4 KiB static row <= 160 KiB
-constexpr unsigned kNoiseStream = 0x56414531u;  // counter word 3: the encoder's stream ("VAE1"), apart from metrics.hip
 }  // namespace
 
 struct EncOp {
@@ -190,13 +189,6 @@ __device__ __forceinline__ void linear_rows(const float* __restrict__ src, float
     if (op.relu) r = fmaxf(r, 0.0f);
     if (lane == 0) dst[o] = r;
   }
-}
-
-__device__ __forceinline__ float normal_eps(unsigned long long seed, unsigned i, unsigned j) {
-  const U4 r = philox4x32_10(U4{i, j, 0u, kNoiseStream}, (unsigned)seed, (unsigned)(seed >> 32));
-  const double u1 = ((double)(r.x >> 5) * 67108864.0 + (double)(r.y >> 6)) * (1.0 / 9007199254740992.0);
-  const double u2 = ((double)(r.z >> 5) * 67108864.0 + (double)(r.w >> 6)) * (1.0 / 9007199254740992.0);
-  return (float)(sqrt(-2.0 * log(1.0 - u1)) * cos(6.283185307179586 * u2));
 }
 
 // ---- launches -----------------------------------------------------------------------------------------------------

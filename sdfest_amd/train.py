@@ -1,0 +1,297 @@
+"""Training of the SDF VAE on the GPU: host-side mirror of ``sdfest/vae/scripts/train.py`` (:128-381).
+
+``SDFVAETrainer`` owns the master parameters, their gradient and Adam's two moments as four flat fp32 device buffers in
+``state_dict`` order (all ``encoder.*``, then all ``decoder.*``, torch's layouts) and runs one iteration --
+forward with a tape, the loss, the gradient of every parameter, Adam -- in ``libsdfr_hip.so`` (csrc/vae_train.hip,
+include/sdfr.h group 10).  Inference handles (``SDFVAE``) are built from the trained state: ``vae()``.
+
+What the reference's iteration has and this one does not: the ``pc_weight`` term (a render of every target at a random
+pose per iteration; the reference's default weight is 0) -- a value other than 0 raises ``NotImplementedError``.
+"""
+import ctypes
+import glob
+import os
+from typing import Mapping, Optional
+
+import numpy as np
+import torch
+
+from . import _lib
+from .differentiable_renderer import _stream
+from .vae import ENC_CONV, ENC_LINEAR, SDFVAE, _check_grid, _seed, encoder_state_keys, parse_encoder_layers
+
+TERMS = ("l2_small", "l2_large", "l1_small", "l1_large", "kld", "total")
+_DEFAULTS = {"iterations": 100000, "batch_size": 8, "learning_rate": 1e-3, "l2_large_weight": 1.0,
+             "l2_small_weight": 1.0, "l1_large_weight": 0.0, "l1_small_weight": 0.0, "kld_weight": 1.0, "pc_weight": 0.0,
+             "warm_up_iterations": 1000, "tsdf": False, "sdf_size": 64}
+
+
+def parameter_shapes(config: Mapping) -> list:
+    """[(state-dict key, shape)] of the VAE `config` describes, in state_dict order = the flat buffers' order.  Raises
+    for layers the kernels do not implement, naming the layer (``parse_encoder_layers``); needs no GPU."""
+    plan = parse_encoder_layers(int(config.get("sdf_size", 64)), config["encoder"]["layer_infos"])
+    latent = int(config["latent_size"])
+    shapes = []
+    for op in plan["ops"]:
+        if op[0] == ENC_CONV:
+            shapes += [(op[2], op[1], op[3], op[3], op[3]), (op[2],)]
+        elif op[0] == ENC_LINEAR:
+            shapes += [(op[2], op[1]), (op[2],)]
+    shapes += [(latent, plan["features"]), (latent,)] * 2
+    out = list(zip(encoder_state_keys(plan), shapes))
+    width = latent
+    for i, l in enumerate(config["decoder"]["fc_layers"]):
+        out += [(f"decoder._fc_layers.{i}.weight", (int(l["out"]), width)), (f"decoder._fc_layers.{i}.bias", (int(l["out"]),))]
+        width = int(l["out"])
+    for i, l in enumerate(config["decoder"]["conv_layers"]):
+        k = int(l["kernel_size"])
+        out += [(f"decoder._conv_layers.{i}.weight", (int(l["out_channels"]), int(l["in_channels"]), k, k, k)),
+                (f"decoder._conv_layers.{i}.bias", (int(l["out_channels"]),))]
+    return out
+
+
+def check_config(config: Mapping) -> dict:
+    """The training config with the defaults filled in; raises for what is not implemented."""
+    cfg = dict(_DEFAULTS)
+    cfg.update(config)
+    for key in ("latent_size", "encoder", "decoder"):
+        if key not in cfg:
+            raise KeyError(f"the config has no {key!r}")
+    if float(cfg["pc_weight"] or 0.0) != 0.0:
+        raise NotImplementedError(f"pc_weight={cfg['pc_weight']!r}: the point cloud term of the reference's trainer is not "
+                                  "implemented (only pc_weight = 0, the reference's default)")
+    if cfg["tsdf"] is not False and not float(cfg["tsdf"]) > 0.0:
+        raise ValueError(f"tsdf={cfg['tsdf']!r} must be False or > 0")
+    return cfg
+
+
+def initial_state(config: Mapping, seed: int = 0) -> dict:
+    """torch's default initialisation of Linear / Conv3d, drawn on the host: weight and bias U(-b, b), b = 1 / sqrt(fan_in)"""
+    gen = torch.Generator().manual_seed(int(seed))
+    state, bound = {}, 0.0
+    for key, shape in parameter_shapes(config):
+        if len(shape) > 1:
+            bound = 1.0 / float(np.sqrt(np.prod(shape[1:])))
+        state[key] = (torch.rand(shape, generator=gen, dtype=torch.float64) * 2.0 - 1.0).mul_(bound).float()
+    return state
+
+
+def write_checkpoint(path: str, checkpoint: Mapping) -> None:
+    torch.save(dict(checkpoint), path)
+
+
+def read_checkpoint(path: str) -> dict:
+    ck = torch.load(path, map_location="cpu", weights_only=False)
+    for key in ("params", "exp_avg", "exp_avg_sq", "iteration", "seed", "config", "keys"):
+        if key not in ck:
+            raise ValueError(f"{path}: not a trainer checkpoint (no {key!r})")
+    return ck
+
+
+def load_volumes(folder: str) -> torch.Tensor:
+    """(M, D, D, D) float32 from ``folder/00000.npy, 00001.npy, ...`` (tools/process_meshes.py; the reference's SDFDataset)"""
+    files = sorted(glob.glob(os.path.join(folder, "*.npy")))
+    if not files:
+        raise FileNotFoundError(f"no .npy volumes in {folder}")
+    return torch.from_numpy(np.stack([np.load(f).astype(np.float32) for f in files]))
+
+
+class SDFVAETrainer:
+    """One VAE and its Adam state on the GPU.  ``config``: the reference's training + network keys (iterations,
+    batch_size, learning_rate, the five loss weights, pc_weight, latent_size, tsdf, encoder, decoder) plus
+    ``warm_up_iterations`` (1000, the reference's literal) and ``sdf_size`` (64)."""
+
+    def __init__(self, config: Mapping, state_dict: Optional[Mapping] = None, seed: int = 0, device="cuda"):
+        self.config = check_config(config)
+        cfg = self.config
+        self._shapes = parameter_shapes(cfg)          # raises for unsupported layers, before anything touches the GPU
+        self.seed = int(seed)
+        self.iteration = 0
+        self.sdf_size, self.latent_size = int(cfg["sdf_size"]), int(cfg["latent_size"])
+        plan = parse_encoder_layers(self.sdf_size, cfg["encoder"]["layer_infos"])
+        arr = lambda v: np.ascontiguousarray(v, dtype=np.int32)
+        fc, conv = cfg["decoder"]["fc_layers"], cfg["decoder"]["conv_layers"]
+        ops = arr(plan["ops"]).reshape(-1, _lib.ABI["SDFR_ENC_OP_INTS"])
+        self.device = torch.device(device)
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        L = _lib.lib()
+        P = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        handle = ctypes.c_void_p()
+        rc = L.sdfr_vae_trainer_create(
+            self.latent_size, len(fc), P(arr([l["out"] for l in fc])), len(conv), P(arr([l["in_size"] for l in conv])),
+            P(arr([l["in_channels"] for l in conv])), P(arr([l["out_channels"] for l in conv])),
+            P(arr([l["kernel_size"] for l in conv])), P(arr([1 if l["relu"] else 0 for l in conv])), self.sdf_size,
+            float(cfg["tsdf"]) if cfg["tsdf"] is not False else 0.0, ops.shape[0], P(ops), self.device.index,
+            ctypes.byref(handle))
+        _lib.check(rc, "sdfr_vae_trainer_create")
+        self._L, self._h = L, handle
+        count = L.sdfr_vae_trainer_param_count(handle)
+        assert count == sum(int(np.prod(s)) for _, s in self._shapes), "parameter layout differs from the library's"
+        f32 = dict(dtype=torch.float32, device=self.device)
+        self._params = torch.zeros(count, **f32)
+        self._grads = torch.zeros(count, **f32)
+        self._exp_avg = torch.zeros(count, **f32)
+        self._exp_avg_sq = torch.zeros(count, **f32)
+        self._step = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._terms = torch.zeros(6, **f32)
+        self._batch = {}       # N -> the buffers of an iteration
+        self.load_state_dict(initial_state(cfg, self.seed) if state_dict is None else state_dict)
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h:
+            self._L.sdfr_vae_trainer_destroy(h)
+            self._h = None
+
+    # ---- parameters --------------------------------------------------------------------------------------------------
+    def _views(self, flat: torch.Tensor) -> dict:
+        out, off = {}, 0
+        for key, shape in self._shapes:
+            n = int(np.prod(shape))
+            out[key] = flat[off:off + n].view(shape)
+            off += n
+        return out
+
+    def state_dict(self) -> dict:
+        """the reference's ``SDFVAE.state_dict()``: its keys, its order, copies on the device"""
+        return {k: v.clone() for k, v in self._views(self._params).items()}
+
+    def load_state_dict(self, state: Mapping) -> None:
+        if not any(k.startswith(("encoder.", "decoder.")) for k in state):
+            raise KeyError("the state dict has neither 'encoder.' nor 'decoder.' keys")
+        parts = []
+        for key, shape in self._shapes:
+            if key not in state:
+                raise KeyError(f"state dict has no {key!r}")
+            t = torch.as_tensor(np.asarray(state[key]) if not isinstance(state[key], torch.Tensor) else state[key])
+            if tuple(t.shape) != tuple(shape):
+                raise ValueError(f"{key}: shape {tuple(t.shape)}, the layers need {tuple(shape)}")
+            parts.append(t.detach().to(torch.float32).reshape(-1).cpu())
+        self._params.copy_(torch.cat(parts))
+
+    def vae(self) -> SDFVAE:
+        """inference handles of the current parameters"""
+        return SDFVAE.from_config(self.config, self.state_dict(), device=self.device, sdf_size=self.sdf_size)
+
+    # ---- checkpoints -------------------------------------------------------------------------------------------------
+    def save_checkpoint(self, path: str) -> None:
+        write_checkpoint(path, {"params": self._params.cpu(), "exp_avg": self._exp_avg.cpu(),
+                                "exp_avg_sq": self._exp_avg_sq.cpu(), "adam_step": int(self._step.item()),
+                                "iteration": self.iteration, "seed": self.seed, "config": dict(self.config),
+                                "keys": [k for k, _ in self._shapes]})
+
+    def load_checkpoint(self, path: str) -> None:
+        ck = read_checkpoint(path)
+        if ck["keys"] != [k for k, _ in self._shapes] or ck["params"].numel() != self._params.numel():
+            raise ValueError(f"{path}: the checkpoint is of another network")
+        self._params.copy_(ck["params"])
+        self._exp_avg.copy_(ck["exp_avg"])
+        self._exp_avg_sq.copy_(ck["exp_avg_sq"])
+        self._step.fill_(int(ck.get("adam_step", ck["iteration"])))
+        self.iteration, self.seed = int(ck["iteration"]), int(ck["seed"])
+
+    # ---- one iteration -----------------------------------------------------------------------------------------------
+    def _buffers(self, N: int) -> dict:
+        b = self._batch.get(N)
+        if b is None:
+            f32 = dict(dtype=torch.float32, device=self.device)
+            D, Ls = self.sdf_size, self.latent_size
+            b = {"x": torch.empty((N, 1, D, D, D), **f32), "recon": torch.empty((N, 1, D, D, D), **f32),
+                 "g_recon": torch.empty((N, 1, D, D, D), **f32)}
+            for name in ("means", "log_var", "z", "g_means", "g_log_var"):
+                b[name] = torch.empty((N, Ls), **f32)
+            b["tape"] = torch.empty(self._L.sdfr_vae_trainer_tape_bytes(self._h, N), dtype=torch.uint8, device=self.device)
+            b["ws"] = torch.empty(self._L.sdfr_vae_trainer_workspace_bytes(self._h, N), dtype=torch.uint8,
+                                  device=self.device)
+            self._batch = {N: b}     # one batch size at a time
+        return b
+
+    def _iteration_seed(self, seed: Optional[int]) -> int:
+        if seed is None:   # a function of (seed, iteration): a resumed run draws what the uninterrupted one does
+            return (self.seed * 0x9E3779B97F4A7C15 + self.iteration * 0xD1B54A32D192ED03 + 1) & 0xFFFFFFFFFFFFFFFF
+        return _seed(seed)
+
+    def _forward_backward(self, x: torch.Tensor, seed: int, iteration: int) -> dict:
+        _check_grid(x, self.sdf_size, self.device, "x")
+        N = x.shape[0]
+        b = self._buffers(N)
+        with torch.no_grad():
+            b["x"].copy_(x)
+        cfg, L, h, st = self.config, self._L, self._h, _stream(self.device)
+        post = 1 if iteration > int(cfg["warm_up_iterations"]) else 0
+        p = lambda name: b[name].data_ptr()
+        rc = L.sdfr_vae_trainer_forward(h, self._params.data_ptr(), p("x"), N, seed, post, p("means"), p("log_var"),
+                                        p("z"), p("recon"), p("tape"), b["tape"].numel(), st)
+        _lib.check(rc, "sdfr_vae_trainer_forward")
+        rc = L.sdfr_vae_trainer_loss(h, p("recon"), p("x"), p("means"), p("log_var"), N, float(cfg["l2_small_weight"]),
+                                     float(cfg["l2_large_weight"]), float(cfg["l1_small_weight"]),
+                                     float(cfg["l1_large_weight"]), float(cfg["kld_weight"]), post,
+                                     self._terms.data_ptr(), p("g_recon"), p("g_means"), p("g_log_var"), p("ws"),
+                                     b["ws"].numel(), st)
+        _lib.check(rc, "sdfr_vae_trainer_loss")
+        rc = L.sdfr_vae_trainer_backward(h, self._params.data_ptr(), p("x"), N, seed, p("log_var"), p("z"), p("tape"),
+                                         p("recon"), p("g_recon"), p("g_means"), p("g_log_var"), self._grads.data_ptr(),
+                                         p("ws"), b["ws"].numel(), st)
+        _lib.check(rc, "sdfr_vae_trainer_backward")
+        return b
+
+    def loss_and_grad(self, x: torch.Tensor, seed: Optional[int] = None, iteration: Optional[int] = None) -> dict:
+        """Forward, loss and backward at `iteration` (default: the trainer's own) without an update.  Returns the six
+        loss numbers (``TERMS``) as floats, ``grads``: name -> view of the gradient buffer, and clones of ``means``,
+        ``log_var``, ``z`` and ``recon``."""
+        it = self.iteration if iteration is None else int(iteration)
+        b = self._forward_backward(x, self._iteration_seed(seed), it)
+        out = dict(zip(TERMS, self._terms.tolist()))
+        out["grads"] = self._views(self._grads)
+        for name in ("means", "log_var", "z", "recon"):
+            out[name] = b[name].clone()
+        return out
+
+    def step(self, x: torch.Tensor, seed: Optional[int] = None) -> torch.Tensor:
+        """One iteration: forward, loss, backward, Adam; `x` is copied, not clamped.  Returns the six loss numbers
+        (``TERMS``) as a device tensor, without synchronising."""
+        self._forward_backward(x, self._iteration_seed(seed), self.iteration)
+        rc = self._L.sdfr_adam_flat(self._params.data_ptr(), self._grads.data_ptr(), self._exp_avg.data_ptr(),
+                                    self._exp_avg_sq.data_ptr(), self._step.data_ptr(), self._params.numel(),
+                                    float(self.config["learning_rate"]), self.device.index, _stream(self.device))
+        _lib.check(rc, "sdfr_adam_flat")
+        self.iteration += 1
+        return self._terms.clone()
+
+    def fit(self, volumes_or_folder, iterations: Optional[int] = None, log_every: int = 100, callback=None) -> int:
+        """The reference's loop (train.py:195-372): epochs over the volumes in a seeded shuffle, ``drop_last``, until
+        the trainer's iteration counter reaches `iterations` (default: the config's).  The loss terms are copied to
+        the host every `log_every` iterations only, and given to ``callback(iteration, terms: dict)`` (default: print).
+        Returns the number of epochs begun."""
+        data = load_volumes(volumes_or_folder) if isinstance(volumes_or_folder, (str, os.PathLike)) else \
+            torch.as_tensor(np.asarray(volumes_or_folder) if not isinstance(volumes_or_folder, torch.Tensor)
+                            else volumes_or_folder).detach().to(torch.float32).cpu()
+        D, bs = self.sdf_size, int(self.config["batch_size"])
+        if data.dim() == 5 and data.shape[1] == 1:
+            data = data[:, 0]
+        if data.dim() != 4 or tuple(data.shape[1:]) != (D, D, D):
+            raise ValueError(f"volumes must have shape (M, {D}, {D}, {D}), got {tuple(data.shape)}")
+        if data.shape[0] < bs:
+            raise ValueError(f"{data.shape[0]} volumes are fewer than one batch of {bs} (drop_last)")
+        total = int(self.config["iterations"]) if iterations is None else int(iterations)
+        per_epoch = data.shape[0] // bs
+        epochs = 0
+        while self.iteration < total:
+            epoch = self.iteration // per_epoch       # a function of the counter: a resumed run continues its epoch
+            gen = torch.Generator().manual_seed((self.seed * 1000003 + epoch) & 0x7FFFFFFFFFFFFFFF)
+            order = torch.randperm(data.shape[0], generator=gen)
+            epochs += 1
+            for j in range(self.iteration % per_epoch, per_epoch):
+                x = data[order[j * bs:(j + 1) * bs]][:, None].to(self.device)
+                terms = self.step(x)
+                if log_every and self.iteration % log_every == 0:
+                    named = dict(zip(TERMS, terms.tolist()))
+                    if callback is not None:
+                        callback(self.iteration, named)
+                    else:
+                        print(f"iteration {self.iteration}, epoch {epoch + 1}: " +
+                              ", ".join(f"{k} {v:.6g}" for k, v in named.items()), flush=True)
+                if self.iteration >= total:
+                    break
+        return epochs

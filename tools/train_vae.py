@@ -1,0 +1,65 @@
+#!/usr/bin/env python3
+"""Train the SDF VAE on the GPU: the reference's ``sdfest/vae/scripts/train.py`` without wandb / tensorboard.
+
+Reads a folder of ``00000.npy, 00001.npy, ...`` volumes as ``tools/process_meshes.py`` writes them, and a YAML config
+with the reference's keys (``vae/configs/default_training.yaml`` + a network config: iterations, batch_size,
+learning_rate, the five loss weights, pc_weight (must be 0), latent_size, tsdf, encoder, decoder; optional
+warm_up_iterations, sdf_size).  Writes ``{out}.pt`` (``torch.save`` of the state dict, the reference's keys) and
+``{out}.yaml`` (the model keys and ``model: ./{name}.pt``, as train.py:377-381), which ``SDFVAE.from_config`` and the
+reference load; ``{out}.ckpt`` holds the trainer's checkpoint (parameters, Adam's moments, the iteration) for
+``--checkpoint``.
+
+Usage:  python tools/train_vae.py --config cfg.yaml --dataset_path volumes/ --out models/mug [--iterations N]
+"""
+import argparse
+import os
+import sys
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+sys.path.insert(0, ROOT)
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--config", required=True, help="YAML with the reference's training and network keys")
+    ap.add_argument("--dataset_path", help="folder of .npy volumes (default: the config's dataset_path)")
+    ap.add_argument("--out", required=True, help="output path without extension")
+    ap.add_argument("--checkpoint", help="a trainer checkpoint to resume from")
+    ap.add_argument("--iterations", type=int)
+    ap.add_argument("--batch_size", type=int)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--log_every", type=int, default=100)
+    ap.add_argument("--device", default="cuda")
+    a = ap.parse_args(argv)
+
+    import torch
+    import yaml
+    from sdfest_amd.train import SDFVAETrainer
+    with open(a.config) as f:
+        config = yaml.safe_load(f)
+    for key in ("iterations", "batch_size", "dataset_path"):
+        if getattr(a, key) is not None:
+            config[key] = getattr(a, key)
+    if not config.get("dataset_path"):
+        ap.error("no dataset_path, neither on the command line nor in the config")
+    trainer = SDFVAETrainer(config, seed=a.seed, device=a.device)
+    if a.checkpoint:
+        trainer.load_checkpoint(a.checkpoint)
+    trainer.fit(config["dataset_path"], log_every=a.log_every)
+    torch.cuda.synchronize()
+
+    out_dir = os.path.dirname(os.path.abspath(a.out))
+    os.makedirs(out_dir, exist_ok=True)
+    name = os.path.basename(a.out)
+    torch.save({k: v.cpu() for k, v in trainer.state_dict().items()}, a.out + ".pt")
+    saved = {k: v for k, v in trainer.config.items()}
+    saved["model"] = os.path.join(".", name + ".pt")
+    with open(a.out + ".yaml", "w") as f:
+        yaml.safe_dump(saved, f, sort_keys=False)
+    trainer.save_checkpoint(a.out + ".ckpt")
+    print(f"wrote {a.out}.pt, {a.out}.yaml and {a.out}.ckpt after {trainer.iteration} iterations")
+
+
+if __name__ == "__main__":
+    main()
