@@ -866,7 +866,8 @@ typedef struct sdfr_sample_mesh {
   float factor;            /* uniform scale (the Mesh's _factor) */
   float quat[4];           /* (x, y, z, w) */
   float position[3];
-} sdfr_sample_mesh;        /* 72 bytes */
+} sdfr_sample_mesh;        /* 72 bytes; read on the device through csrc/mesh_record.hpp alone, written by mesh.py's
+                            * _MeshTable alone */
 SDFR_API size_t sdfr_sample_workspace_bytes(int K, long long total_faces, int max_faces);   /* 0: invalid */
 SDFR_API int sdfr_sample_points(const sdfr_sample_mesh* meshes, int K, long long total_faces, int max_faces, int n,
                                 unsigned long long seed, float* points, float* normals, int* triangles,

@@ -136,3 +136,15 @@ def check(rc: int, what: str) -> None:
     if rc != 0:
         msg = lib().sdfr_last_error().decode(errors="replace")
         raise RuntimeError(f"{what} failed (code {rc}): {msg}")
+
+
+def workspace(nbytes: int, what: str, device, given=None):
+    """The workspace of a call whose ``*_workspace_bytes`` function `what` returned `nbytes`: 0 means that it refused
+    the arguments, which raises as a failed call does; otherwise `given` (a buffer the caller made beforehand) or a new
+    uint8 device tensor of that size."""
+    if nbytes == 0:
+        check(ABI["SDFR_E_INVALID"], what)
+    if given is not None:
+        return given
+    import torch
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)

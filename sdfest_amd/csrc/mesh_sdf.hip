@@ -27,6 +27,7 @@
 #include <cmath>
 
 #include "common.hpp"
+#include "mesh_record.hpp"
 
 #pragma clang fp contract(off)
 
@@ -44,43 +45,6 @@ static_assert(sizeof(MeshSdfHead) == 16, "MeshSdfHead must stay 16 bytes");
 
 inline size_t mesh_sdf_head_bytes(int K) { return ((size_t)K * sizeof(MeshSdfHead) + 63) & ~(size_t)63; }
 
-// the faces of record r that may be read, or 0
-__device__ __forceinline__ int mesh_sdf_faces(const sdfr_sample_mesh& r, int max_faces) {
-  const bool ok = r.vertices && r.faces && r.num_vertices >= 1 && r.num_faces >= 1 && r.num_faces <= max_faces;
-  return ok ? r.num_faces : 0;
-}
-
-// P = M v + t with M = factor * R(quat): the pose as sdfr_mesh_depth applies it (raster.hip, raster_pose), in the
-// record's own frame
-struct MeshSdfPose {
-  float m[9];
-  float t[3];
-};
-
-__device__ __forceinline__ MeshSdfPose mesh_sdf_pose(const sdfr_sample_mesh& r) {
-  const float x = r.quat[0], y = r.quat[1], z = r.quat[2], w = r.quat[3];
-  const float f = r.factor;
-  MeshSdfPose p;
-  p.m[0] = f * (1.0f - 2.0f * (y * y + z * z));
-  p.m[1] = f * (2.0f * (x * y - w * z));
-  p.m[2] = f * (2.0f * (x * z + w * y));
-  p.m[3] = f * (2.0f * (x * y + w * z));
-  p.m[4] = f * (1.0f - 2.0f * (x * x + z * z));
-  p.m[5] = f * (2.0f * (y * z - w * x));
-  p.m[6] = f * (2.0f * (x * z - w * y));
-  p.m[7] = f * (2.0f * (y * z + w * x));
-  p.m[8] = f * (1.0f - 2.0f * (x * x + y * y));
-  p.t[0] = r.position[0], p.t[1] = r.position[1], p.t[2] = r.position[2];
-  return p;
-}
-
-__device__ __forceinline__ V3 mesh_sdf_vertex(const MeshSdfPose& p, const float* __restrict__ v) {
-  const float x = v[0], y = v[1], z = v[2];
-  return mk(fmaf(p.m[0], x, fmaf(p.m[1], y, fmaf(p.m[2], z, p.t[0]))),
-            fmaf(p.m[3], x, fmaf(p.m[4], y, fmaf(p.m[5], z, p.t[1]))),
-            fmaf(p.m[6], x, fmaf(p.m[7], y, fmaf(p.m[8], z, p.t[2]))));
-}
-
 // a x b in plain products and differences: common.hpp's `cross` is defined in front of this file's contraction pragma
 // and may be fused there; here two equal products must cancel exactly (three points on a line in one coordinate
 // pattern have zero area in fp32 too)
@@ -96,7 +60,7 @@ __global__ void __launch_bounds__(kSdfThreads) mesh_sdf_head_kernel(const sdfr_s
   const int chunk = (K + kSdfThreads - 1) / kSdfThreads;
   const int lo = min(K, (int)threadIdx.x * chunk), hi = min(K, lo + chunk);
   long long sum = 0;
-  for (int k = lo; k < hi; ++k) sum += mesh_sdf_faces(meshes[k], max_faces);
+  for (int k = lo; k < hi; ++k) sum += mesh_record_faces(meshes[k], max_faces);
   s_sum[threadIdx.x] = sum;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -110,7 +74,7 @@ __global__ void __launch_bounds__(kSdfThreads) mesh_sdf_head_kernel(const sdfr_s
   __syncthreads();
   long long off = s_sum[threadIdx.x];
   for (int k = lo; k < hi; ++k) {
-    const int F = mesh_sdf_faces(meshes[k], max_faces);
+    const int F = mesh_record_faces(meshes[k], max_faces);
     // records that would leave the workspace (the caller's total_faces is too small) are not written or read
     head[k].offset = off;
     head[k].faces = off + F <= total_faces ? F : 0;
@@ -134,18 +98,14 @@ __global__ void __launch_bounds__(kSdfThreads) mesh_sdf_setup_kernel(const sdfr_
   if (t >= h.faces) return;
   const sdfr_sample_mesh rec = meshes[k];
   float4* out = records + 4 * (h.offset + t);
-  int ia = rec.faces[3 * (long long)t], ib = rec.faces[3 * (long long)t + 1], ic = rec.faces[3 * (long long)t + 2];
-  float parity = 1.0f;
-  if (ia > ib) { const int s = ia; ia = ib; ib = s; parity = -parity; }
-  if (ib > ic) { const int s = ib; ib = ic; ic = s; parity = -parity; }
-  if (ia > ib) { const int s = ia; ia = ib; ib = s; parity = -parity; }
-  const unsigned nv = (unsigned)rec.num_vertices;
+  int ia, ib, ic;
+  const float parity = mesh_sorted_face(rec.faces, t, rec.num_vertices, ia, ib, ic);
   float4 r0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), r1 = r0, r2 = r0, r3 = r0;
-  if ((unsigned)ia < nv && (unsigned)ib < nv && (unsigned)ic < nv && ia != ib && ib != ic) {   // nothing else is read
-    const MeshSdfPose pose = mesh_sdf_pose(rec);
-    const V3 a = mesh_sdf_vertex(pose, rec.vertices + 3 * (long long)ia);
-    const V3 b = mesh_sdf_vertex(pose, rec.vertices + 3 * (long long)ib);
-    const V3 c = mesh_sdf_vertex(pose, rec.vertices + 3 * (long long)ic);
+  if (parity != 0.0f) {   // nothing else is read
+    const MeshPose pose = mesh_pose(rec, 1.0f);   // the record's own frame
+    const V3 a = mesh_posed_vertex(pose, rec.vertices + 3 * (long long)ia);
+    const V3 b = mesh_posed_vertex(pose, rec.vertices + 3 * (long long)ib);
+    const V3 c = mesh_posed_vertex(pose, rec.vertices + 3 * (long long)ic);
     const float sum = (a.x + a.y + a.z) + (b.x + b.y + b.z) + (c.x + c.y + c.z);
     const V3 ab = b - a, ac = c - a;
     const V3 n = mesh_sdf_cross(ab, ac);
@@ -260,10 +220,7 @@ __global__ void __launch_bounds__(kSdfThreads) mesh_sdf_kernel(const MeshSdfHead
 }
 
 inline int mesh_sdf_check(const char* fn, int K, long long total_faces, int max_faces, int R) {
-  if (K < 1 || K > 65535) return fail(SDFR_E_INVALID, "%s: K=%d out of range [1,65535]", fn, K);
-  if (total_faces < 1) return fail(SDFR_E_INVALID, "%s: total_faces=%lld must be >= 1", fn, total_faces);
-  if (max_faces < 1 || max_faces > total_faces)
-    return fail(SDFR_E_INVALID, "%s: max_faces=%d out of range [1,total_faces=%lld]", fn, max_faces, total_faces);
+  if (int rc = mesh_table_check(fn, K, total_faces, max_faces)) return rc;
   if (R < 2 || R > 256) return fail(SDFR_E_INVALID, "%s: R=%d out of range [2,256]", fn, R);
   return 0;
 }

@@ -30,6 +30,7 @@
 
 #include "common.hpp"
 #include "philox.hpp"
+#include "mesh_record.hpp"
 
 // the CPU twin (tests/metrics_twin.py) evaluates every expression in this file operation by operation
 #pragma clang fp contract(off)
@@ -47,9 +48,8 @@ constexpr int kNNMinSlice = 256;          // reference points per workgroup, at 
 constexpr int kNNTargetBlocks = 1024;     // the slicing aims at this many workgroups (4 per CU)
 constexpr int kReduceThreads = 256;
 
-static_assert(sizeof(sdfr_sample_mesh) == 72, "sdfr_sample_mesh layout is part of the ABI");
-
-// the record's face count, or 0 when its CDF range would leave the workspace (such a mesh's samples are NaN)
+// the record's face count, or 0 when its CDF range would leave the workspace (such a mesh's samples are NaN): the
+// sampler's own rule, not mesh_record_faces -- it guards the workspace; the pointers are the caller's to keep valid
 __device__ __forceinline__ int sample_faces(const sdfr_sample_mesh& m, long long total_faces, int max_faces) {
   const bool ok = m.num_faces >= 1 && m.num_faces <= max_faces && m.cdf_offset >= 0 &&
                   m.cdf_offset + m.num_faces <= total_faces;
@@ -401,14 +401,6 @@ void nn_dispatch(float p, const float* q, const long long* qoff, long long total
     nn_launch<kLP, kFar>(q, qoff, total_q, max_q, r, roff, total_r, max_r, K, p, dist, index, keys, st);
 }
 
-inline int sample_check(const char* fn, int K, long long total_faces, int max_faces) {
-  if (K < 1 || K > 65535) return fail(SDFR_E_INVALID, "%s: K=%d out of range [1,65535]", fn, K);
-  if (total_faces < 1) return fail(SDFR_E_INVALID, "%s: total_faces=%lld must be >= 1", fn, total_faces);
-  if (max_faces < 1 || max_faces > total_faces)
-    return fail(SDFR_E_INVALID, "%s: max_faces=%d out of range [1,total_faces=%lld]", fn, max_faces, total_faces);
-  return 0;
-}
-
 inline int nn_check(const char* fn, int K, long long total_q, int max_q, long long total_r, int max_r) {
   if (K < 1 || K > 65535) return fail(SDFR_E_INVALID, "%s: K=%d out of range [1,65535]", fn, K);
   if (max_q < 1 || total_q < max_q)
@@ -425,14 +417,14 @@ inline int nn_check(const char* fn, int K, long long total_q, int max_q, long lo
 using namespace sdfr;
 
 extern "C" size_t sdfr_sample_workspace_bytes(int K, long long total_faces, int max_faces) {
-  if (sample_check("sdfr_sample_workspace_bytes", K, total_faces, max_faces)) return 0;
+  if (mesh_table_check("sdfr_sample_workspace_bytes", K, total_faces, max_faces)) return 0;
   return (size_t)total_faces * sizeof(double);
 }
 
 extern "C" int sdfr_sample_points(const sdfr_sample_mesh* meshes, int K, long long total_faces, int max_faces, int n,
                                   unsigned long long seed, float* points, float* normals, int* triangles,
                                   void* workspace, size_t workspace_bytes, int device, void* stream) {
-  if (int rc = sample_check("sdfr_sample_points", K, total_faces, max_faces)) return rc;
+  if (int rc = mesh_table_check("sdfr_sample_points", K, total_faces, max_faces)) return rc;
   if (n < 1) return fail(SDFR_E_INVALID, "sdfr_sample_points: n=%d must be >= 1", n);
   if (!meshes || !points || !workspace)
     return fail(SDFR_E_NULL, "sdfr_sample_points: NULL pointer argument (only normals and triangles may be NULL)");

@@ -32,6 +32,7 @@
 #include <cmath>
 
 #include "common.hpp"
+#include "mesh_record.hpp"
 
 #pragma clang fp contract(off)
 
@@ -44,45 +45,10 @@ constexpr int kTileH = 8;
 static_assert(kTileW * kTileH == kRasterThreads, "one lane per pixel of the tile");
 constexpr int kRectFaces = 4 * kRasterThreads;     // triangles per workgroup of the rectangle kernel
 
-// the image's pose, uniform over the workgroup: P = M v + t with M = factor * R(quat), rows 1 and 2 negated for the
-// OpenGL frame (internal frame: the camera looks along +z, y down)
-struct RasterPose {
-  float m[9];
-  float t[3];
-};
-
-__device__ __forceinline__ RasterPose raster_pose(const sdfr_sample_mesh& r, int flags) {
-  const float x = r.quat[0], y = r.quat[1], z = r.quat[2], w = r.quat[3];
-  const float f = r.factor;
-  const float s = (flags & SDFR_MESH_DEPTH_OPEN3D) ? 1.0f : -1.0f;
-  RasterPose p;
-  // the rotation matrix of a quaternion as pipeline.quaternion_apply applies it (v + 2 w (u x v) + 2 u x (u x v))
-  p.m[0] = f * (1.0f - 2.0f * (y * y + z * z));
-  p.m[1] = f * (2.0f * (x * y - w * z));
-  p.m[2] = f * (2.0f * (x * z + w * y));
-  p.m[3] = s * f * (2.0f * (x * y + w * z));
-  p.m[4] = s * f * (1.0f - 2.0f * (x * x + z * z));
-  p.m[5] = s * f * (2.0f * (y * z - w * x));
-  p.m[6] = s * f * (2.0f * (x * z - w * y));
-  p.m[7] = s * f * (2.0f * (y * z + w * x));
-  p.m[8] = s * f * (1.0f - 2.0f * (x * x + y * y));
-  p.t[0] = r.position[0];
-  p.t[1] = s * r.position[1];
-  p.t[2] = s * r.position[2];
-  return p;
-}
-
-__device__ __forceinline__ V3 raster_vertex(const RasterPose& p, const float* v) {
-  const float x = v[0], y = v[1], z = v[2];
-  return mk(fmaf(p.m[0], x, fmaf(p.m[1], y, fmaf(p.m[2], z, p.t[0]))),
-            fmaf(p.m[3], x, fmaf(p.m[4], y, fmaf(p.m[5], z, p.t[1]))),
-            fmaf(p.m[6], x, fmaf(p.m[7], y, fmaf(p.m[8], z, p.t[2]))));
-}
-
-// the faces of record r that may be read, or 0 (the record then draws nothing)
-__device__ __forceinline__ int raster_faces(const sdfr_sample_mesh& r, int max_faces) {
-  const bool ok = r.vertices && r.faces && r.num_vertices >= 1 && r.num_faces >= 1 && r.num_faces <= max_faces;
-  return ok ? r.num_faces : 0;
+// the record's pose in the internal frame (the camera looks along +z, y down): an OpenGL-frame pose has its y and z
+// negated
+__device__ __forceinline__ MeshPose raster_pose(const sdfr_sample_mesh& r, int flags) {
+  return mesh_pose(r, (flags & SDFR_MESH_DEPTH_OPEN3D) ? 1.0f : -1.0f);
 }
 
 // n = p x (q - p) of the edge between vertices a and b (indices ia != ib), walked a -> b by the triangle: from the
@@ -119,17 +85,10 @@ __device__ __forceinline__ RasterFetch raster_fetch(const float* __restrict__ ve
   RasterFetch r;
   r.ok = false;
   if (!in_range) return r;
-  int ia = faces[3 * (long long)t], ib = faces[3 * (long long)t + 1], ic = faces[3 * (long long)t + 2];
   // the vertices in index order: every number below depends on the SET of the three indices alone, so triangles over
   // the same three vertices, in whatever order or winding, give bitwise equal depths (both faces count anyway)
-  if (ia > ib) { const int s = ia; ia = ib; ib = s; }
-  if (ib > ic) { const int s = ib; ib = ic; ic = s; }
-  if (ia > ib) { const int s = ia; ia = ib; ib = s; }
-  if ((unsigned)ia >= (unsigned)num_vertices || (unsigned)ib >= (unsigned)num_vertices ||
-      (unsigned)ic >= (unsigned)num_vertices)
-    return r;
-  if (ia == ib || ib == ic || ia == ic) return r;
-  r.ia = ia, r.ib = ib, r.ic = ic;
+  if (mesh_sorted_face(faces, t, num_vertices, r.ia, r.ib, r.ic) == 0.0f) return r;
+  const int ia = r.ia, ib = r.ib, ic = r.ic;
 #pragma unroll
   for (int j = 0; j < 3; ++j) {
     r.a[j] = vertices[3 * (long long)ia + j];
@@ -142,9 +101,9 @@ __device__ __forceinline__ RasterFetch raster_fetch(const float* __restrict__ ve
 
 // The posed vertices; false: the triangle covers nothing (an index outside [0, num_vertices), a repeated index, a
 // non-finite vertex, zero area, or every vertex at or behind the camera plane)
-__device__ __forceinline__ bool raster_posed(const RasterPose& pose, const RasterFetch& r, V3& A, V3& B, V3& C) {
+__device__ __forceinline__ bool raster_posed(const MeshPose& pose, const RasterFetch& r, V3& A, V3& B, V3& C) {
   if (!r.ok) return false;
-  A = raster_vertex(pose, r.a), B = raster_vertex(pose, r.b), C = raster_vertex(pose, r.c);
+  A = mesh_posed_vertex(pose, r.a), B = mesh_posed_vertex(pose, r.b), C = mesh_posed_vertex(pose, r.c);
   const float sum = (A.x + A.y + A.z) + (B.x + B.y + B.z) + (C.x + C.y + C.z);
   if (!(fabsf(sum) < INFINITY)) return false;   // a NaN or an infinity somewhere
   if (!(fmaxf(A.z, fmaxf(B.z, C.z)) > 0.0f)) return false;   // a hit has 0 < depth <= the largest vertex depth
@@ -206,10 +165,10 @@ __global__ void __launch_bounds__(kRasterThreads) raster_rect_kernel(const sdfr_
                                                                       int* __restrict__ rect) {
   const int k = blockIdx.y;
   const sdfr_sample_mesh rec = meshes[k];
-  const int F = raster_faces(rec, max_faces);
+  const int F = mesh_record_faces(rec, max_faces);
   const long long first = (long long)blockIdx.x * kRectFaces;
   if (first >= F) return;   // uniform over the workgroup
-  const RasterPose pose = raster_pose(rec, flags);
+  const MeshPose pose = raster_pose(rec, flags);
   int x0 = W, y0 = H, x1 = -1, y1 = -1;
 #pragma unroll
   for (int u = 0; u < kRectFaces / kRasterThreads; ++u) {
@@ -264,9 +223,9 @@ __global__ void __launch_bounds__(kRasterThreads) raster_tile_kernel(const sdfr_
   float best = INFINITY;
   int best_t = -1;
   const sdfr_sample_mesh rec = meshes[k];
-  const int F = raster_faces(rec, max_faces);
+  const int F = mesh_record_faces(rec, max_faces);
   if (F > 0 && rx0 <= tx1 && rx1 >= tx0 && ry0 <= ty1 && ry1 >= ty0) {   // uniform over the workgroup
-    const RasterPose pose = raster_pose(rec, flags);
+    const MeshPose pose = raster_pose(rec, flags);
     const float dx = ((float)col + 0.5f - cx) / fx, dy = ((float)row + 0.5f - cy) / fy;
     // the tile's rays, with half a pixel to spare on every side (far more than the rounding of these four numbers and
     // of the tests on them can move a plane)
@@ -324,10 +283,7 @@ __global__ void __launch_bounds__(kRasterThreads) raster_tile_kernel(const sdfr_
 }
 
 inline int raster_check(const char* fn, int K, long long total_faces, int max_faces, int W, int H) {
-  if (K < 1 || K > 65535) return fail(SDFR_E_INVALID, "%s: K=%d out of range [1,65535]", fn, K);
-  if (total_faces < 1) return fail(SDFR_E_INVALID, "%s: total_faces=%lld must be >= 1", fn, total_faces);
-  if (max_faces < 1 || max_faces > total_faces)
-    return fail(SDFR_E_INVALID, "%s: max_faces=%d out of range [1,total_faces=%lld]", fn, max_faces, total_faces);
+  if (int rc = mesh_table_check(fn, K, total_faces, max_faces)) return rc;
   if (W < 1 || H < 1 || W > 16384 || H > 16384)
     return fail(SDFR_E_INVALID, "%s: image size W=%d, H=%d out of range [1,16384]", fn, W, H);
   return 0;

@@ -182,8 +182,8 @@ class Mesh:
                 f"rel_scale={self.rel_scale})")
 
 
-def _ptr(t: torch.Tensor) -> int:
-    return t.data_ptr()
+def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
+    return None if t is None else t.data_ptr()
 
 
 def extract_mesh(sdf: torch.Tensor, level: float, complete: bool = False,
@@ -211,16 +211,13 @@ def extract_mesh(sdf: torch.Tensor, level: float, complete: bool = False,
     dev = sdf.device
     L = _lib.lib()
     cpl = 1 if complete else 0
-    ws_bytes = L.sdfr_mesh_workspace_bytes(N, R, cpl)
-    if ws_bytes == 0:
-        _lib.check(_lib.ABI["SDFR_E_INVALID"], "sdfr_mesh_workspace_bytes")
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    ws = _lib.workspace(L.sdfr_mesh_workspace_bytes(N, R, cpl), "sdfr_mesh_workspace_bytes", dev)
     totals = torch.empty((N, 4), dtype=torch.int32, device=dev)
     stream = torch.cuda.current_stream(dev).cuda_stream
     lvl = float(np.float32(level))
     with torch.cuda.device(dev):
-        _lib.check(L.sdfr_mesh_count(_ptr(sdf), N, R, cpl, lvl, _ptr(totals), _ptr(ws), ws_bytes, dev.index, stream),
-                   "sdfr_mesh_count")
+        _lib.check(L.sdfr_mesh_count(_ptr(sdf), N, R, cpl, lvl, _ptr(totals), _ptr(ws), ws.numel(), dev.index,
+                                     stream), "sdfr_mesh_count")
         h = totals.cpu().numpy()
     lo, hi = h[:, 2].copy().view(np.float32), h[:, 3].copy().view(np.float32)
     bad = np.nonzero(~((lo <= lvl) & (lvl <= hi)))[0]
@@ -235,9 +232,8 @@ def extract_mesh(sdf: torch.Tensor, level: float, complete: bool = False,
     nrm = torch.empty((max(V, 1), 3), dtype=torch.float32, device=dev) if normals else None
     if V:
         with torch.cuda.device(dev):
-            _lib.check(L.sdfr_mesh_emit(_ptr(sdf), N, R, cpl, lvl, _ptr(totals), _ptr(verts),
-                                        _ptr(nrm) if nrm is not None else None, _ptr(faces), _ptr(ws), ws_bytes,
-                                        dev.index, stream), "sdfr_mesh_emit")
+            _lib.check(L.sdfr_mesh_emit(_ptr(sdf), N, R, cpl, lvl, _ptr(totals), _ptr(verts), _ptr(nrm), _ptr(faces),
+                                        _ptr(ws), ws.numel(), dev.index, stream), "sdfr_mesh_emit")
     vo = np.concatenate([[0], np.cumsum(nv)])
     fo = np.concatenate([[0], np.cumsum(nf)])
     meshes = [Mesh(verts[vo[n]:vo[n + 1]], faces[fo[n]:fo[n + 1]],
@@ -250,6 +246,85 @@ _SAMPLE_RECORD = np.dtype({"names": ["vertices", "faces", "normals", "cdf_offset
                                      "factor", "quat", "position"],
                            "formats": ["<u8", "<u8", "<u8", "<i8", "<i4", "<i4", "<f4", ("<f4", 4), ("<f4", 3)],
                            "offsets": [0, 8, 16, 24, 32, 36, 40, 44, 60], "itemsize": 72})
+# the float32 words of a record that hold a float field (or an array of them)
+_FLOATS = {name: slice(_SAMPLE_RECORD.fields[name][1] // 4,
+                       (_SAMPLE_RECORD.fields[name][1] + _SAMPLE_RECORD.fields[name][0].itemsize) // 4)
+           for name in ("factor", "quat", "position")}
+
+
+class _MeshTable:
+    """The device table of K ``sdfr_sample_mesh`` records that ``sdfr_sample_points``, ``sdfr_mesh_depth`` and
+    ``sdfr_mesh_sdf`` read (csrc/mesh_record.hpp), record k for ``meshes[k]``: the one place that writes the format.
+
+    Every record gets the mesh's buffers, its scale (``_factor``) and the identity pose; ``factor`` (K,), ``quat`` (K,4)
+    and ``position`` (K,3) are float32 views of those columns of the device table, to be rewritten in place -- from
+    device tensors nothing is read back -- and ``set_poses`` fills the pose from tensors or from the meshes.  A mesh
+    that occurs several times is converted once and its record written once (the repeats are one array copy).
+    verb: what the caller does, for the error texts.  normals: every mesh must have vertex normals, and the records
+    point to them.  empty: the rest of the error for a mesh without faces, or None: such a mesh gets a record with
+    ``num_faces = 0``.
+
+    table: the device tensor, (K, 18) float32 words of which only those columns hold floats, or None when no record
+    has a face (there is nothing to launch, and nothing is uploaded); total_faces, max_faces: the sum and the largest of
+    the records' face counts (record k's ``cdf_offset`` is the sum over the records before it); vertices: record k's
+    float32 vertices as the kernels read them (None for an empty mesh); keep: the tensors the table points to, to be
+    held until the launches that read them are on the stream."""
+
+    def __init__(self, meshes: List[Mesh], verb: str, normals: bool = False, empty: Optional[str] = None) -> None:
+        if not meshes:
+            raise ValueError(f"no meshes to {verb}")
+        faces = [int(m.faces.shape[0]) if m.vertices.shape[0] else 0 for m in meshes]
+        if empty is not None and 0 in faces:
+            raise ValueError(f"mesh {faces.index(0)} {empty}")
+        dev = meshes[0].vertices.device
+        if dev.type != "cuda":
+            raise TypeError("meshes must live on a CUDA device (sdfest_amd has no CPU path)")
+        rec = np.zeros(len(meshes), dtype=_SAMPLE_RECORD)
+        first, again, starts, total = {}, [], [], 0
+        self._converted = {}     # id(mesh) -> its (vertices, faces, normals) as the kernels read them
+        for k, (m, F) in enumerate(zip(meshes, faces)):
+            if m.vertices.device != dev:
+                raise ValueError("all meshes must live on one device")
+            if normals and m.normals is None:
+                raise ValueError(f"mesh {k} has no vertex normals (extract_mesh(..., normals=True))")
+            starts.append(total if F else 0)
+            total += F
+            if first.setdefault(id(m), k) != k:
+                again.append(k)     # a mesh seen before: its record is copied below, nothing is converted or written
+                continue
+            r = rec[k]
+            r["factor"], r["quat"] = m._factor, (0.0, 0.0, 0.0, 1.0)
+            if F == 0:
+                continue
+            v = m.vertices.detach().to(torch.float32).contiguous()
+            f = m.faces.detach().to(torch.int32).contiguous()
+            nr = m.normals.detach().to(torch.float32).contiguous() if normals else None
+            self._converted[id(m)] = (v, f, nr)
+            r["vertices"], r["faces"], r["num_vertices"], r["num_faces"] = v.data_ptr(), f.data_ptr(), v.shape[0], F
+            r["cdf_offset"] = starts[k]
+            if normals:
+                r["normals"] = nr.data_ptr()
+        if again:     # 256 poses of one mesh: two array assignments, not 255 records field by field
+            rec[again] = rec[[first[id(meshes[k])] for k in again]]
+            rec["cdf_offset"] = starts
+        self.meshes, self.device, self.total_faces, self.max_faces = meshes, dev, total, max(faces)
+        self.keep = list(self._converted.values())
+        self.table = None
+        if total:
+            words = rec.view(np.float32).reshape(len(meshes), -1)     # pointers and counts are opaque bits in here
+            self.table = torch.from_numpy(words).pin_memory().to(dev, non_blocking=True)
+
+    vertices = property(lambda self: [self._converted.get(id(m), (None,))[0] for m in self.meshes])
+    factor = property(lambda self: self.table[:, _FLOATS["factor"].start])
+    quat = property(lambda self: self.table[:, _FLOATS["quat"]])
+    position = property(lambda self: self.table[:, _FLOATS["position"]])
+
+    def set_poses(self, quat: Optional[torch.Tensor] = None, position: Optional[torch.Tensor] = None) -> None:
+        """the records' poses from (K,4) / (K,3) tensors; None: every mesh's own orientation / position"""
+        for name, given, own in (("quat", quat, "orientation"), ("position", position, "position")):
+            if given is None:
+                given = torch.stack([getattr(m, own).detach().to(self.device, torch.float32) for m in self.meshes])
+            self.table[:, _FLOATS[name]] = given.detach().to(self.device, torch.float32)
 
 
 def _sample(meshes: List[Mesh], n: int, seed: int, transformed: bool, normals: bool):
@@ -258,55 +333,24 @@ def _sample(meshes: List[Mesh], n: int, seed: int, transformed: bool, normals: b
     n = int(n)
     if n < 1:
         raise ValueError(f"number_of_points={n} must be >= 1")
-    if not meshes:
-        raise ValueError("no meshes to sample")
     if not 0 <= int(seed) < 2 ** 64:
         raise ValueError(f"seed={seed} must be in [0, 2^64)")
-    dev = meshes[0].vertices.device
-    if dev.type != "cuda":
-        raise TypeError("meshes must live on a CUDA device (sdfest_amd has no CPU path)")
-    K = len(meshes)
-    rec = np.zeros(K, dtype=_SAMPLE_RECORD)
-    keep = []
-    off = 0
-    for k, m in enumerate(meshes):
-        if m.vertices.device != dev:
-            raise ValueError("all meshes must live on one device")
-        F = int(m.faces.shape[0])
-        if F == 0 or m.vertices.shape[0] == 0:
-            raise ValueError(f"mesh {k} has no faces to sample")
-        if normals and m.normals is None:
-            raise ValueError(f"mesh {k} has no vertex normals (extract_mesh(..., normals=True))")
-        v = m.vertices.detach().to(torch.float32).contiguous()
-        f = m.faces.detach().to(torch.int32).contiguous()
-        nr = m.normals.detach().to(torch.float32).contiguous() if (normals and m.normals is not None) else None
-        keep += [v, f, nr]
-        rec[k]["vertices"], rec[k]["faces"] = v.data_ptr(), f.data_ptr()
-        rec[k]["normals"] = nr.data_ptr() if nr is not None else 0
-        rec[k]["cdf_offset"], rec[k]["num_vertices"], rec[k]["num_faces"] = off, v.shape[0], F
-        rec[k]["factor"] = m._factor
-        rec[k]["quat"] = (0.0, 0.0, 0.0, 1.0)
-        off += F
-    max_f = max(int(m.faces.shape[0]) for m in meshes)
+    tab = _MeshTable(meshes, "sample", normals=normals, empty="has no faces to sample")
+    if transformed:
+        tab.set_poses()
+    dev, K = tab.device, len(meshes)
     L = _lib.lib()
-    ws_bytes = L.sdfr_sample_workspace_bytes(K, off, max_f)
-    if ws_bytes == 0:
-        _lib.check(_lib.ABI["SDFR_E_INVALID"], "sdfr_sample_workspace_bytes")
-    table = torch.from_numpy(rec.view(np.uint8)).pin_memory().to(dev, non_blocking=True)
-    if transformed:   # the poses stay on the device: floats 11..14 and 15..17 of each record
-        tab = table.view(torch.float32).view(K, _SAMPLE_RECORD.itemsize // 4)
-        tab[:, 11:15] = torch.stack([m.orientation.detach().to(dev, torch.float32) for m in meshes])
-        tab[:, 15:18] = torch.stack([m.position.detach().to(dev, torch.float32) for m in meshes])
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    ws = _lib.workspace(L.sdfr_sample_workspace_bytes(K, tab.total_faces, tab.max_faces),
+                        "sdfr_sample_workspace_bytes", dev)
     pts = torch.empty((K, n, 3), dtype=torch.float32, device=dev)
     nrm = torch.empty((K, n, 3), dtype=torch.float32, device=dev) if normals else None
     tri = torch.empty((K, n), dtype=torch.int32, device=dev)
     stream = torch.cuda.current_stream(dev).cuda_stream
     with torch.cuda.device(dev):
-        _lib.check(L.sdfr_sample_points(_ptr(table), K, off, max_f, n, int(seed), _ptr(pts),
-                                        _ptr(nrm) if nrm is not None else None, _ptr(tri), _ptr(ws), ws_bytes,
-                                        dev.index, stream), "sdfr_sample_points")
-    del keep   # freed tensors are reused only by later work on this stream: the launches read them first
+        _lib.check(L.sdfr_sample_points(_ptr(tab.table), K, tab.total_faces, tab.max_faces, n, int(seed), _ptr(pts),
+                                        _ptr(nrm), _ptr(tri), _ptr(ws), ws.numel(), dev.index, stream),
+                   "sdfr_sample_points")
+    del tab   # freed tensors are reused only by later work on this stream: the launches read them first
     return pts, nrm, tri
 
 
@@ -439,11 +483,6 @@ def render_mesh_depth(meshes: Union[Mesh, List[Mesh]], camera, positions: Option
     if not (0.0 <= near < float("inf")):
         raise ValueError(f"near={near} must be >= 0 and finite")
     meshes = [meshes] if isinstance(meshes, Mesh) else list(meshes)
-    if not meshes:
-        raise ValueError("no meshes to render")
-    dev = meshes[0].vertices.device
-    if dev.type != "cuda":
-        raise TypeError("meshes must live on a CUDA device (sdfest_amd has no CPU path)")
     for name, t, w in (("positions", positions, 3), ("orientations", orientations, 4)):
         if t is not None and (t.dim() != 2 or t.shape[1] != w):
             raise ValueError(f"{name} of shape {tuple(t.shape)}: (V,{w}) expected")
@@ -454,7 +493,8 @@ def render_mesh_depth(meshes: Union[Mesh, List[Mesh]], camera, positions: Option
         meshes = meshes * V
     elif V is not None and V != len(meshes):
         raise ValueError(f"{V} poses for {len(meshes)} meshes (one pose per mesh, or one mesh)")
-    K = len(meshes)
+    tab = _MeshTable(meshes, "render")     # a mesh without faces: num_faces = 0, the kernel stores an image of zeros
+    dev, K = tab.device, len(meshes)
     W, H = int(camera.width), int(camera.height)
     if out is not None:
         if tuple(out.shape) != (K, H, W) or out.dtype != torch.float32 or out.device != dev or not out.is_contiguous():
@@ -463,42 +503,15 @@ def render_mesh_depth(meshes: Union[Mesh, List[Mesh]], camera, positions: Option
     else:
         depth = torch.empty((K, H, W), dtype=torch.float32, device=dev)
     tri = torch.empty((K, H, W), dtype=torch.int32, device=dev) if return_triangles else None
-
-    rec = np.zeros(K, dtype=_SAMPLE_RECORD)
-    keep, cache, total, max_f = [], {}, 0, 0
-    for k, m in enumerate(meshes):
-        if m.vertices.device != dev:
-            raise ValueError("all meshes must live on one device")
-        F = int(m.faces.shape[0]) if m.vertices.shape[0] else 0
-        rec[k]["factor"], rec[k]["quat"] = m._factor, (0.0, 0.0, 0.0, 1.0)
-        if F == 0:
-            continue     # num_faces = 0: the kernel stores an image of zeros
-        if id(m) not in cache:
-            cache[id(m)] = (m.vertices.detach().to(torch.float32).contiguous(),
-                            m.faces.detach().to(torch.int32).contiguous())
-            keep.append(cache[id(m)])
-        v, f = cache[id(m)]
-        rec[k]["vertices"], rec[k]["faces"] = v.data_ptr(), f.data_ptr()
-        rec[k]["cdf_offset"], rec[k]["num_vertices"], rec[k]["num_faces"] = total, v.shape[0], F
-        total += F
-        max_f = max(max_f, F)
-    if total == 0:
+    if tab.total_faces == 0:
         depth.zero_()
         if tri is not None:
             tri.fill_(-1)
         return (depth, tri) if return_triangles else depth
-    table = torch.from_numpy(rec.view(np.uint8)).pin_memory().to(dev, non_blocking=True)
-    tab = table.view(torch.float32).view(K, _SAMPLE_RECORD.itemsize // 4)   # poses: floats 11..14 and 15..17
-    if orientations is not None:
-        tab[:, 11:15] = orientations.detach().to(dev, torch.float32)
-    else:
-        tab[:, 11:15] = torch.stack([m.orientation.detach().to(dev, torch.float32) for m in meshes])
-    if positions is not None:
-        tab[:, 15:18] = positions.detach().to(dev, torch.float32)
-    else:
-        tab[:, 15:18] = torch.stack([m.position.detach().to(dev, torch.float32) for m in meshes])
-    _mesh_depth_launch(table, total, max_f, (cx, cy, fx, fy), near, _lib.ABI[_CONVENTIONS[convention]], depth, tri)
-    del keep   # as in _sample: freed tensors are reused only by later work on this stream
+    tab.set_poses(orientations, positions)
+    _mesh_depth_launch(tab.table, tab.total_faces, tab.max_faces, (cx, cy, fx, fy), near,
+                       _lib.ABI[_CONVENTIONS[convention]], depth, tri)
+    del tab   # as in _sample: freed tensors are reused only by later work on this stream
     return (depth, tri) if return_triangles else depth
 
 
@@ -512,15 +525,12 @@ def _mesh_depth_launch(table: torch.Tensor, total_faces: int, max_faces: int, in
     K, H, W = (int(x) for x in depth.shape)
     cx, cy, fx, fy = intrinsics
     L = _lib.lib()
-    ws_bytes = L.sdfr_mesh_depth_workspace_bytes(K, total_faces, max_faces, W, H)
-    if ws_bytes == 0:
-        _lib.check(_lib.ABI["SDFR_E_INVALID"], "sdfr_mesh_depth_workspace_bytes")
-    ws = workspace if workspace is not None else torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    ws = _lib.workspace(L.sdfr_mesh_depth_workspace_bytes(K, total_faces, max_faces, W, H),
+                        "sdfr_mesh_depth_workspace_bytes", dev, workspace)
     with torch.cuda.device(dev):
         _lib.check(L.sdfr_mesh_depth(_ptr(table), K, total_faces, max_faces, W, H, cx, cy, fx, fy, near, flags,
-                                     _ptr(depth), _ptr(triangles) if triangles is not None else None, _ptr(ws),
-                                     ws.numel(), dev.index, torch.cuda.current_stream(dev).cuda_stream),
-                   "sdfr_mesh_depth")
+                                     _ptr(depth), _ptr(triangles), _ptr(ws), ws.numel(), dev.index,
+                                     torch.cuda.current_stream(dev).cuda_stream), "sdfr_mesh_depth")
 
 
 def draw_depth_geometry(obj: Mesh, camera) -> torch.Tensor:

@@ -58,17 +58,14 @@ def _nn(q, qoff, qsizes, r, roff, rsizes, p: float, farthest: bool, dev: torch.d
     L = _lib.lib()
     K, total_q, total_r = len(qsizes), int(q.shape[0]), int(r.shape[0])
     max_q, max_r = int(qsizes.max()), int(rsizes.max())
-    ws_bytes = L.sdfr_nn_workspace_bytes(K, total_q, max_q)
-    if ws_bytes == 0:
-        _lib.check(_lib.ABI["SDFR_E_INVALID"], "sdfr_nn_workspace_bytes")
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    ws = _lib.workspace(L.sdfr_nn_workspace_bytes(K, total_q, max_q), "sdfr_nn_workspace_bytes", dev)
     dist = torch.empty(total_q, dtype=torch.float64, device=dev)
     stream = torch.cuda.current_stream(dev).cuda_stream
     with torch.cuda.device(dev):
         _lib.check(L.sdfr_nn_query(q.data_ptr(), qoff.data_ptr(), total_q, max_q, r.data_ptr(), roff.data_ptr(),
                                    total_r, max_r, K, float(p), int(farthest), dist.data_ptr(),
                                    index.data_ptr() if index is not None else None, ws.data_ptr(),
-                                   ws_bytes, dev.index, stream), "sdfr_nn_query")
+                                   ws.numel(), dev.index, stream), "sdfr_nn_query")
     return dist
 
 

@@ -8,11 +8,10 @@ direction, the reference's ``mesh_from_sdf``, is ``sdfest_amd.extract_mesh``.
 """
 from typing import List, Optional, Tuple, Union
 
-import numpy as np
 import torch
 
 from . import _lib
-from .mesh import _SAMPLE_RECORD, Mesh, _ptr
+from .mesh import Mesh, _MeshTable, _ptr
 
 __all__ = ["mesh_to_sdf", "normalization", "normalized_mesh"]
 
@@ -46,41 +45,14 @@ def normalized_mesh(mesh: Mesh, cells_per_dim: int = 64, padding: int = 0) -> Me
 
 def _mesh_sdf_table(meshes: List[Mesh], normalize: bool, cells_per_dim: int, padding: int):
     """(device table of K sdfr_sample_mesh records, total faces, largest face count, the tensors the table points to)"""
-    if not meshes:
-        raise ValueError("no meshes to convert")
-    for k, m in enumerate(meshes):
-        if m.faces.shape[0] == 0 or m.vertices.shape[0] == 0:
-            raise ValueError(f"mesh {k} has no faces")
-    dev = meshes[0].vertices.device
-    if dev.type != "cuda":
-        raise TypeError("meshes must live on a CUDA device (sdfest_amd has no CPU path)")
-    K = len(meshes)
-    rec = np.zeros(K, dtype=_SAMPLE_RECORD)
-    keep, cache, total, max_f = [], {}, 0, 0
-    for k, m in enumerate(meshes):
-        if m.vertices.device != dev:
-            raise ValueError("all meshes must live on one device")
-        F = int(m.faces.shape[0])
-        if id(m) not in cache:
-            cache[id(m)] = (m.vertices.detach().to(torch.float32).contiguous(),
-                            m.faces.detach().to(torch.int32).contiguous())
-            keep.append(cache[id(m)])
-        v, f = cache[id(m)]
-        rec[k]["vertices"], rec[k]["faces"] = v.data_ptr(), f.data_ptr()
-        rec[k]["cdf_offset"], rec[k]["num_vertices"], rec[k]["num_faces"] = total, v.shape[0], F
-        rec[k]["factor"], rec[k]["quat"] = m._factor, (0.0, 0.0, 0.0, 1.0)
-        total += F
-        max_f = max(max_f, F)
-    table = torch.from_numpy(rec.view(np.uint8)).pin_memory().to(dev, non_blocking=True)
-    tab = table.view(torch.float32).view(K, _SAMPLE_RECORD.itemsize // 4)   # factor: float 10; pose: 11..14, 15..17
+    tab = _MeshTable(meshes, "convert", empty="has no faces")
     if normalize:   # the framing stays on the device: nothing is read back, the vertices are not copied
-        frames = [normalization(cache[id(m)][0], cells_per_dim, padding) for m in meshes]
-        tab[:, 10] = torch.stack([s for s, _ in frames])
-        tab[:, 15:18] = torch.stack([t for _, t in frames])
+        frames = [normalization(v, cells_per_dim, padding) for v in tab.vertices]
+        tab.factor[:] = torch.stack([s for s, _ in frames])
+        tab.position[:] = torch.stack([t for _, t in frames])
     else:
-        tab[:, 11:15] = torch.stack([m.orientation.detach().to(dev, torch.float32) for m in meshes])
-        tab[:, 15:18] = torch.stack([m.position.detach().to(dev, torch.float32) for m in meshes])
-    return table, total, max_f, keep
+        tab.set_poses()
+    return tab.table, tab.total_faces, tab.max_faces, tab.keep
 
 
 def _mesh_sdf_launch(table: torch.Tensor, total_faces: int, max_faces: int, flags: int, sdf: torch.Tensor,
@@ -92,14 +64,11 @@ def _mesh_sdf_launch(table: torch.Tensor, total_faces: int, max_faces: int, flag
     dev = sdf.device
     K, R = int(sdf.shape[0]), int(sdf.shape[1])
     L = _lib.lib()
-    ws_bytes = L.sdfr_mesh_sdf_workspace_bytes(K, total_faces, max_faces, R)
-    if ws_bytes == 0:
-        _lib.check(_lib.ABI["SDFR_E_INVALID"], "sdfr_mesh_sdf_workspace_bytes")
-    ws = workspace if workspace is not None else torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    ws = _lib.workspace(L.sdfr_mesh_sdf_workspace_bytes(K, total_faces, max_faces, R), "sdfr_mesh_sdf_workspace_bytes",
+                        dev, workspace)
     with torch.cuda.device(dev):
-        _lib.check(L.sdfr_mesh_sdf(_ptr(table), K, total_faces, max_faces, R, flags, _ptr(sdf),
-                                   _ptr(triangles) if triangles is not None else None,
-                                   _ptr(winding) if winding is not None else None, _ptr(ws), ws.numel(), dev.index,
+        _lib.check(L.sdfr_mesh_sdf(_ptr(table), K, total_faces, max_faces, R, flags, _ptr(sdf), _ptr(triangles),
+                                   _ptr(winding), _ptr(ws), ws.numel(), dev.index,
                                    torch.cuda.current_stream(dev).cuda_stream), "sdfr_mesh_sdf")
 
 

@@ -248,15 +248,12 @@ def test_replay_inside_a_captured_graph():
     s = all_scenes()["a_sphere_160"]
     cam = s["camera"]
     W, H, fx, fy, cx, cy = rt.camera_params(cam)
-    v, f = T(s["mesh"][0]), T(s["mesh"][1], torch.int32)
-    K, F = 2, int(f.shape[0])
-    rec = np.zeros(K, dtype=mesh_mod._SAMPLE_RECORD)
-    for k in range(K):
-        rec[k]["vertices"], rec[k]["faces"] = v.data_ptr(), f.data_ptr()
-        rec[k]["num_vertices"], rec[k]["num_faces"], rec[k]["cdf_offset"] = v.shape[0], F, k * F
-        rec[k]["factor"], rec[k]["quat"], rec[k]["position"] = s["pose"][0], (0, 0, 0, 1), (0, 0, -0.5)
-    table = torch.from_numpy(rec.view(np.uint8).copy()).cuda()
-    tab = table.view(torch.float32).view(K, 18)
+    m = gpu_mesh(s["mesh"], s["pose"][0], position=(0, 0, -0.5))
+    K, F = 2, len(s["mesh"][1])
+    tab = mesh_mod._MeshTable([m] * K, "render")
+    tab.set_poses()
+    table = tab.table
+    assert (tab.total_faces, tab.max_faces) == (K * F, F)
     ws = torch.empty(_lib.lib().sdfr_mesh_depth_workspace_bytes(K, K * F, F, W, H), dtype=torch.uint8, device="cuda")
     depth = torch.zeros((K, H, W), device="cuda")
     launch = lambda: mesh_mod._mesh_depth_launch(table, K * F, F, (cx, cy, fx, fy), 0.0, 0, depth, None, ws)
@@ -272,7 +269,7 @@ def test_replay_inside_a_captured_graph():
     # new poses written in place, one replay
     quats = T([s["pose"][1], (0.0, 0.0, 0.0, 1.0)])
     pos = T([s["pose"][2], (0.01, 0.0, -0.45)])
-    tab[:, 11:15], tab[:, 15:18] = quats, pos
+    tab.quat[:], tab.position[:] = quats, pos
     depth.fill_(3.0)
     graph.replay()
     torch.cuda.synchronize()
