@@ -50,7 +50,8 @@
  *        sdfr_decoder_create / _destroy / _forward / _workspace_bytes / _tape_bytes,
  *        sdfr_decoder_backward_latent[_workspace_bytes], sdfr_decoder_set_option
  *   2. [unstable] BATCHED / STEP forms of the same arithmetic (fewer launches, fewer bytes; same results)
- *        sdfr_render_step_forward[_counted] / _step_backward / _step_workspace_bytes, sdfr_render_sync_offset,
+ *        sdfr_render_step_forward[_counted|_resident] / _step_backward / _step_workspace_bytes, sdfr_render_sync_offset,
+ *        sdfr_render_forward_resident, sdfr_render_resident_state_bytes,
  *        sdfr_render_partials_offset, sdfr_render_fixed_volume_offset, sdfr_fixed_to_float
  *        sdfr_render_forward_l1[_workspace_bytes], sdfr_render_backward_l1, sdfr_render_step_forward_l1,
  *        sdfr_render_step_backward_l1, sdfr_render_backward_l1_pc, sdfr_render_step_backward_l1_pc,
@@ -242,6 +243,36 @@ SDFR_API int sdfr_render_step_forward_counted(const float* sdf, int R, long long
                                      float cy, float fx, float fy, float threshold, float* depth, float* g_sdf,
                                      long long g_sdf_view_stride, void* workspace, size_t workspace_bytes,
                                      unsigned long long* close_views_word, int device, void* stream);
+/* RESIDENT DEPTH: sdfr_render_forward / sdfr_render_step_forward_counted for a depth buffer that the caller renders
+ * into call after call (a render-and-compare loop: the poses move a little per iteration).  Most of a batch's pixels
+ * lie outside every view's may-hit region, and the plain calls store those zeros again in every call -- 74 % of the
+ * benchmark's 315 MB.  With a RESIDENT STATE the library remembers, per view and band of 8 rows, which columns its
+ * last forward into the buffer may have left non-zero, and a culled tile stores zeros only where that reaches.
+ *   resident_state  caller-owned device memory, sdfr_render_resident_state_bytes(B, H) bytes, 128-byte aligned, that
+ *                   goes with ONE depth buffer and one (B, W, H).  It needs no initialisation (zero-filled, 0xff-filled
+ *                   and random bytes all read as "no previous call").  Only these two calls read or write it: no other
+ *                   call's workspace scratch can reach it.  NULL: exactly the plain call.
+ *   depth_resident  non-zero: the caller vouches that `depth` holds, byte for byte, what the previous call WITH THIS
+ *                   STATE left there (nothing else has written it since, through any API).  0: no promise -- every
+ *                   pixel is stored, as by the plain call, and the state is brought up to date for the next call.
+ * The hand-over from one call to the next happens on the device (a sequence number in the state that the image
+ * kernel advances, and two tag words per row): a captured step can be replayed with changing poses and grids.  A row
+ * that was not written by the immediately preceding call with this state does not validate, and every culled tile of
+ * that view stores its zeros.  depth is bit for bit what the plain call writes.  Applies to the batch forms over the
+ * packed grid (shared SDF, B >= 17, R <= 128, W <= 65535); elsewhere the call stores every pixel and only advances
+ * the sequence number.  No launch more than the plain call. */
+SDFR_API size_t sdfr_render_resident_state_bytes(int B, int H);
+SDFR_API int sdfr_render_forward_resident(const float* sdf, int R, long long sdf_view_stride, const float* pos,
+                                 const float* quat, const float* inv_scale, int B, int W, int H, float cx, float cy,
+                                 float fx, float fy, float threshold, float* depth, void* workspace,
+                                 size_t workspace_bytes, void* resident_state, size_t resident_state_bytes,
+                                 int depth_resident, int device, void* stream);
+SDFR_API int sdfr_render_step_forward_resident(const float* sdf, int R, long long sdf_view_stride, const float* pos,
+                                      const float* quat, const float* inv_scale, int B, int W, int H, float cx,
+                                      float cy, float fx, float fy, float threshold, float* depth, float* g_sdf,
+                                      long long g_sdf_view_stride, void* workspace, size_t workspace_bytes,
+                                      unsigned long long* close_views_word, void* resident_state,
+                                      size_t resident_state_bytes, int depth_resident, int device, void* stream);
 /* The same pair for the loss-fused forms (below): sdfr_render_step_forward_l1 = sdfr_render_forward_l1 that also
  * zero-fills g_sdf and leaves the view records; sdfr_render_step_backward_l1_pc = sdfr_render_backward_l1_pc without
  * its prologue launch.  For a few views of the plain grid the forward has no prologue launch either (every

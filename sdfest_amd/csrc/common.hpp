@@ -164,6 +164,27 @@ inline size_t scratch_offset_bytes(int B, int H) {
   return spans_offset_bytes(B) + (size_t)(B > 0 ? B : 0) * (H > 0 ? span_stride_words(H) : 0) * 4;
 }
 
+// The RESIDENT-DEPTH state (include/sdfr.h, sdfr_render_forward_resident): a caller-owned buffer that goes with ONE depth
+// buffer and remembers, per view and band, which columns the last forward into that buffer may have left non-zero,
+// so that a culled tile stores its zeros only where something has to be cleared.  Not part of any workspace layout:
+// nothing a call does with its workspace can reach it.
+//   header, kResidentHeaderWords words: word 0 = the state's sequence number (+1 per forward that was given the state)
+//   B rows of resident_stride_words(H) words, written by the view's set-up wave, read by the view's tiles:
+//     word 2k      band k's span of THIS call (x0 | x1 << 16): what the tiles cull with
+//     word 2k + 1  the columns a culled tile of band k has to clear: band k's span of the PREVIOUS call, or
+//                  kResidentClearAll when the caller does not vouch for the buffer or the row does not validate
+//     last two     the sequence number the row was written at and ~(that number ^ resident_key(B, W, H)): a row is
+//                  the previous call's only if both words say so (foreign bytes: 2^-64)
+constexpr int kResidentHeaderWords = 32;
+constexpr unsigned kResidentClearAll = 0xffff0000u;   // columns [0, 65535): overlaps every tile (W <= 65535)
+__host__ __device__ constexpr int resident_stride_words(int H) { return (2 * span_bands(H) + 2 + 31) & ~31; }
+__host__ __device__ constexpr unsigned resident_key(int B, int W, int H) {
+  return (unsigned)W * 0x9E3779B1u ^ (unsigned)H * 0x85EBCA6Bu ^ (unsigned)B * 0xC2B2AE35u;
+}
+inline size_t resident_state_bytes(int B, int H) {
+  return ((size_t)kResidentHeaderWords + (size_t)(B > 0 ? B : 0) * (H > 0 ? resident_stride_words(H) : 0)) * 4;
+}
+
 
 // Device-side fill / copy as ordinary kernels.  The entry points are captured into hipGraphs
 // (FusedRenderAndCompare); with hipMemsetAsync / hipMemcpyAsync nodes in the captured sequence,

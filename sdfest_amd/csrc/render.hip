@@ -93,10 +93,18 @@ __device__ __forceinline__ void setup_pose(int b, const float* __restrict__ pos,
 // grid part: the may-hit box from the plane minima (nullable), its screen rectangle, the slab planes.
 // WAVE: the 64 lanes of a wave share the work of one view (all lanes end up with the same record).
 // spans (WAVE only, nullable): this view's row of the band-span array (common.hpp): lane k writes band k.
+// A view's row of the caller's resident-depth state (common.hpp, kResidentHeaderWords), WAVE only:
+struct ResidentRow {
+  unsigned* row = nullptr;   // nullptr: the call has no such state
+  unsigned seq = 0u;         // the state's sequence number as the previous forward left it
+  unsigned key = 0u;         // resident_key(B, W, H)
+  bool prev_ok = false;      // the caller vouches for the depth buffer AND the row is the previous forward's
+  unsigned prev0 = 0u;       // word 2 * lane of the row as the previous forward left it (bands 0 .. 63)
+};
 template <bool WAVE>
 __device__ __forceinline__ void setup_box(ViewSetup& s, int R, int W, int H, float cx, float cy, float fx,
                                           float fy, const float* __restrict__ plane_min, float threshold,
-                                          unsigned* __restrict__ spans = nullptr) {
+                                          unsigned* __restrict__ spans = nullptr, ResidentRow rr = ResidentRow{}) {
   const V3 p = mk(s.p[0], s.p[1], s.p[2]);
   const float scale = s.scale, isc = s.isc;
   const float h = 0.5f * (float)(R - 1);
@@ -203,7 +211,13 @@ __device__ __forceinline__ void setup_box(ViewSetup& s, int R, int W, int H, flo
 #pragma unroll
     for (int c = 0; c < 8; ++c) sane = sane && (cu[c] == cu[c]) && (cv[c] == cv[c]);   // (fmaxf drops a NaN)
     s.spans = sane ? 1 : 0;
-    if (sane) {
+    // Resident depth: the row takes, per band, the columns this call's tiles cull with -- the span, or the rectangle's
+    // columns in the rectangle's bands for a view without valid spans (nothing for an empty view) -- and beside them
+    // what the PREVIOUS call's row held there, which is what its live tiles may have left non-zero: a culled tile
+    // clears only that.  The previous row counts only if the caller vouches for the buffer and the row's two tag
+    // words say it was written at the sequence number the previous forward left.
+    const int rstride = resident_stride_words(H);
+    if (sane || rr.row) {
       const float mx = 2.0f + 1e-5f * fabsf(fx), my = 2.0f + 1e-5f * fabsf(fy);
       const int nb = span_bands(H);
       // per edge, once: du/dv (an edge along the rows: +-inf or NaN, harmless below)
@@ -242,12 +256,26 @@ __device__ __forceinline__ void setup_box(ViewSetup& s, int R, int W, int H, flo
               ++e;
             }
         int sx0 = 0, sx1 = 0;
-        if (xmin <= xmax && 8 * k < y1 && 8 * k + 8 > y0) {
+        if (!sane) {   // (wave-uniform) the rectangle's columns in the rectangle's bands
+          if (x1 > x0 && 8 * k < y1 && 8 * k + 8 > y0) { sx0 = x0; sx1 = x1; }
+        } else if (xmin <= xmax && 8 * k < y1 && 8 * k + 8 > y0) {
           sx0 = max(x0, (int)fminf(fmaxf(floorf(xmin - 0.5f - mx), 0.0f), (float)W));
           sx1 = min(x1, (int)fminf(fmaxf(ceilf(xmax - 0.5f + mx) + 1.0f, 0.0f), (float)W));
           if (sx1 <= sx0) sx0 = sx1 = 0;
         }
-        if (k < nb) spans[k] = (unsigned)sx0 | ((unsigned)sx1 << 16);
+        const unsigned word = (unsigned)sx0 | ((unsigned)sx1 << 16);
+        if (k < nb) {
+          if (sane) spans[k] = word;
+          if (rr.row) {   // (lane k reads word 2k of the previous call before it writes this call's)
+            const unsigned prev = !rr.prev_ok ? kResidentClearAll : (k0 == 0 ? rr.prev0 : rr.row[2 * k]);
+            rr.row[2 * k] = word;
+            rr.row[2 * k + 1] = prev;
+          }
+        }
+      }
+      if (rr.row && lane == 0) {
+        rr.row[rstride - 2] = rr.seq + 1u;
+        rr.row[rstride - 1] = ~((rr.seq + 1u) ^ rr.key);
       }
     }
   }
@@ -266,11 +294,12 @@ __device__ __forceinline__ void compute_view_setup(int b, const float* __restric
                                                    float cx, float cy, float fx, float fy,
                                                    ViewSetup* __restrict__ out,
                                                    const float* __restrict__ plane_min = nullptr,
-                                                   float threshold = 0.0f, unsigned* __restrict__ spans = nullptr) {
+                                                   float threshold = 0.0f, unsigned* __restrict__ spans = nullptr,
+                                                   ResidentRow rr = ResidentRow{}) {
   ViewSetup s;
   setup_pose(b, pos, quat, inv_scale, R, fx, fy, s);
   setup_box<WAVE>(s, R, W, H, cx, cy, fx, fy, plane_min, threshold,
-                  spans ? spans + (size_t)b * span_stride_words(H) : nullptr);
+                  spans ? spans + (size_t)b * span_stride_words(H) : nullptr, rr);
   if (!WAVE || (threadIdx.x & 63) == 0) out[b] = s;
 }
 
@@ -297,15 +326,36 @@ __device__ __forceinline__ void count_close_view(unsigned* __restrict__ sync, in
   if (word) __hip_atomic_store(word, ((unsigned long long)seq << 32) | c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+// view b's row of the resident-depth state `rstate` (nullable), called by every lane of the view's set-up wave.  The
+// sequence number is read here, by the set-up launch: the image kernel behind it advances it (render_forward_kernel),
+// as it does the workspace's epoch.  All that the set-up needs of the previous call's row is loaded here, at once --
+// the one-launch prologue calls this before it waits for the plane minima, so the loads cost it nothing.
+__device__ __forceinline__ ResidentRow resident_row(unsigned* __restrict__ rstate, int vouched, int b, int B, int W,
+                                                    int H) {
+  ResidentRow rr;
+  if (rstate) {
+    const int stride = resident_stride_words(H), lane = threadIdx.x & 63;
+    rr.row = rstate + kResidentHeaderWords + (size_t)b * stride;
+    rr.seq = rstate[0];
+    rr.key = resident_key(B, W, H);
+    const unsigned tag = rr.row[stride - 2], check = rr.row[stride - 1];
+    rr.prev0 = lane < span_bands(H) ? rr.row[2 * lane] : 0u;
+    rr.prev_ok = vouched != 0 && tag == rr.seq && check == ~(rr.seq ^ rr.key);
+  }
+  return rr;
+}
+
 __global__ void view_setup_kernel(const float* __restrict__ pos, const float* __restrict__ quat,
                                   const float* __restrict__ inv_scale, int B, int R, int W, int H,
                                   float cx, float cy, float fx, float fy,
                                   ViewSetup* __restrict__ out, const float* __restrict__ plane_min,
-                                  float threshold, unsigned* __restrict__ spans) {
+                                  float threshold, unsigned* __restrict__ spans, unsigned* __restrict__ rstate,
+                                  int depth_resident) {
   // one wave per view (the wave shares the scan of the plane minima, lane 0 writes the record)
   const int b = blockIdx.x;
   if (b < B)
-    compute_view_setup<true>(b, pos, quat, inv_scale, R, W, H, cx, cy, fx, fy, out, plane_min, threshold, spans);
+    compute_view_setup<true>(b, pos, quat, inv_scale, R, W, H, cx, cy, fx, fy, out, plane_min, threshold, spans,
+                             resident_row(rstate, depth_resident, b, B, W, H));
 }
 
 // The plane minima reach the set-up waves of the SAME launch (forward_prologue_kernel) as tagged entries: 16 bytes
@@ -488,7 +538,7 @@ __global__ __launch_bounds__(256) void forward_prologue_kernel(
     unsigned* __restrict__ sync, const float* __restrict__ pos, const float* __restrict__ quat,
     const float* __restrict__ inv_scale, int B, int W, int H, float cx, float cy, float fx, float fy,
     ViewSetup* __restrict__ out, float threshold, float* __restrict__ g_zero, size_t n_zero, int default_polls,
-    unsigned* __restrict__ spans) {
+    unsigned* __restrict__ spans, unsigned* __restrict__ rstate, int depth_resident) {
   const unsigned tag = sync[0] + 1u;  // the epoch the last forward on this workspace left, + 1
   PlaneEntry* ent = reinterpret_cast<PlaneEntry*>(sync + kSyncHeaderWords);
   int blk = (int)blockIdx.x;
@@ -503,7 +553,11 @@ __global__ __launch_bounds__(256) void forward_prologue_kernel(
     // the pose part of this wave's view first: its loads and arithmetic run while the plane blocks work
     const int b = blk * 4 + (tid >> 6);
     ViewSetup s;
-    if (b < B) setup_pose(b, pos, quat, inv_scale, R, fx, fy, s);
+    ResidentRow rr;
+    if (b < B) {
+      setup_pose(b, pos, quat, inv_scale, R, fx, fy, s);
+      rr = resident_row(rstate, depth_resident, b, B, W, H);
+    }
     bool ready = false;
     const int max_polls = sync[6] == SDFR_SYNC_POLLS_MAGIC ? (int)sync[7] : default_polls;   // (workgroup-uniform)
     for (int poll = 0; poll < max_polls; ++poll) {
@@ -525,7 +579,7 @@ __global__ __launch_bounds__(256) void forward_prologue_kernel(
     }
     if (b < B) {
       setup_box<true>(s, R, W, H, cx, cy, fx, fy, ready ? pm_s : nullptr, threshold,
-                      spans + (size_t)b * span_stride_words(H));
+                      spans + (size_t)b * span_stride_words(H), rr);
       if ((tid & 63) == 0) {
         out[b] = s;
         if (!ready) atomicAdd(&sync[1], 1u);
@@ -615,32 +669,23 @@ __device__ __forceinline__ Ray ray_setup(const ViewSetup& s, int row, int col, b
   return r;
 }
 
-template <int RT, bool PACKED, int SX, int SY, bool LOSS, bool TIGHT, int NW>
+// RES: the call keeps a resident-depth state (rrows); without it the tile is the plain one, instruction for instruction
+template <int RT, bool PACKED, int SX, int SY, bool LOSS, bool TIGHT, int NW, bool RES = false>
 __device__ __forceinline__ void forward_tile(
     int tile_x, int tile_y, int ntx, int nty, int b, const float* __restrict__ src, int R,
     long long src_view_stride, const ViewSetup& s, int W, int H, float cx, float cy,
     float rfx, float rfy, float threshold, int vec_ok, float* __restrict__ depth,
-    const float* __restrict__ target, float* __restrict__ loss_part, const unsigned* __restrict__ spans) {
+    const float* __restrict__ target, float* __restrict__ loss_part, const unsigned* __restrict__ spans,
+    const unsigned* __restrict__ rrows = nullptr) {
   constexpr int kSubs = SX * SY, kTileW = SX * kSubW, kTileH = SY * kSubH;
   static_assert(kTileH == 8, "a forward tile is one band of the span array");
   constexpr int kThreads = NW * 64;  // NW waves walk the tile's 4 * kSubs 8x8 patches
   using PF = Patch<kPatchWFwd>;
   const int px0 = tile_x * kTileW, py0 = tile_y * kTileH;
-  Rect rc{s.rect[0], s.rect[1], s.rect[2], s.rect[3]};
-  const bool in_rect = overlaps(rc, px0, py0, kTileW, kTileH);
-  // the band's column span of the projected may-hit box (one scalar load): tighter than the rectangle's columns
-  if (s.spans) {
-    const unsigned sp = spans[(size_t)b * span_stride_words(H) + tile_y];
-    rc.x0 = (int)(sp & 0xffffu);
-    rc.x1 = (int)(sp >> 16);
-  }
   float* img = depth + (size_t)b * H * W;
   const int tid = threadIdx.x;
-
-  if (!overlaps(rc, px0, py0, kTileW, kTileH)) {
-    // nothing of the cube projects here: stream zeros.  (LOSS: the view's reduce sums the records of every tile of
-    // the rectangle, also of those the band span leaves out)
-    if (LOSS && in_rect && tid < kLossRec) loss_part[(((size_t)b * nty + tile_y) * ntx + tile_x) * kLossRec + tid] = 0.0f;
+  // a culled tile's zeros
+  auto zero_fill = [&]() {
     typedef float f32x4 __attribute__((ext_vector_type(4)));
     const f32x4 zero4 = {0.0f, 0.0f, 0.0f, 0.0f};
     if (vec_ok) {
@@ -657,6 +702,37 @@ __device__ __forceinline__ void forward_tile(
         if (row < H && col < W) img[(size_t)row * W + col] = 0.0f;
       }
     }
+  };
+  // rrows (nullable): the rows of the caller's resident-depth state (common.hpp): per band the columns this call's
+  // tiles cull with (the span; the rectangle's columns for a view without valid spans; nothing in a band outside the
+  // rectangle's rows) and, in the same 8-byte scalar load, the columns a culled tile still has to clear.  The word's
+  // address does not depend on the view's record, so a culled tile leaves after ONE scalar load behind its kernel
+  // arguments instead of two dependent ones (record, then span), most of them without a store.
+  uint2 band = make_uint2(0u, kResidentClearAll);
+  if (RES && rrows) {
+    band = *reinterpret_cast<const uint2*>(rrows + (size_t)b * resident_stride_words(H) + 2 * tile_y);
+    if (!LOSS && !(px0 < (int)(band.x >> 16) && px0 + kTileW > (int)(band.x & 0xffffu))) {
+      if (px0 < (int)(band.y >> 16) && px0 + kTileW > (int)(band.y & 0xffffu)) zero_fill();
+      return;
+    }
+  }
+  Rect rc{s.rect[0], s.rect[1], s.rect[2], s.rect[3]};
+  const bool in_rect = overlaps(rc, px0, py0, kTileW, kTileH);
+  // the band's column span of the projected may-hit box (one scalar load): tighter than the rectangle's columns
+  if (RES && rrows) {
+    rc.x0 = (int)(band.x & 0xffffu);
+    rc.x1 = (int)(band.x >> 16);
+  } else if (s.spans) {
+    const unsigned sp = spans[(size_t)b * span_stride_words(H) + tile_y];
+    rc.x0 = (int)(sp & 0xffffu);
+    rc.x1 = (int)(sp >> 16);
+  }
+
+  if (!overlaps(rc, px0, py0, kTileW, kTileH)) {
+    // nothing of the cube projects here: stream zeros.  (LOSS: the view's reduce sums the records of every tile of
+    // the rectangle, also of those the band span leaves out)
+    if (LOSS && in_rect && tid < kLossRec) loss_part[(((size_t)b * nty + tile_y) * ntx + tile_x) * kLossRec + tid] = 0.0f;
+    if (px0 < (int)(band.y >> 16) && px0 + kTileW > (int)(band.y & 0xffffu)) zero_fill();
     return;
   }
 
@@ -750,14 +826,17 @@ struct InlineSetup {
   float* g_zero;
   size_t n_zero;
 };
-template <int RT, bool PACKED, int SX, int SY, bool LOSS, int NW, bool INLINE = false>
+template <int RT, bool PACKED, int SX, int SY, bool LOSS, int NW, bool INLINE = false, bool RES = false>
 __global__ __launch_bounds__(NW * 64) void render_forward_kernel(
     const float* __restrict__ src, int R, long long src_view_stride,
     const ViewSetup* __restrict__ setup, int W, int H, int ntx, int nty, float cx, float cy,
     float rfx, float rfy, float threshold, int vec_ok, float* __restrict__ depth,
     const float* __restrict__ target, float* __restrict__ loss_part, unsigned* __restrict__ epoch,
     const unsigned* __restrict__ spans, InlineSetup in, unsigned* __restrict__ count_sync,
-    unsigned long long* __restrict__ close_word) {
+    unsigned long long* __restrict__ close_word, const unsigned* __restrict__ rrows, unsigned* __restrict__ rseq) {
+  // rseq (nullable): the caller's resident-depth state.  Its sequence number advances once per forward that was given
+  // the state, whatever form the launch takes -- rows that this call did not rewrite are stale for the next one.
+  // (Behind the tile, like everything else that only one workgroup does: nothing in front of a culled tile's exit.)
   if (INLINE) {
     const int b = blockIdx.z;
     ViewSetup s;
@@ -770,11 +849,13 @@ __global__ __launch_bounds__(NW * 64) void render_forward_kernel(
     forward_tile<RT, PACKED, SX, SY, LOSS, PACKED, NW>(blockIdx.x, blockIdx.y, ntx, nty, b, src, R, src_view_stride,
                                                        s, W, H, cx, cy, rfx, rfy, threshold, vec_ok, depth, target,
                                                        loss_part, spans);
+    if (rseq && (blockIdx.x | blockIdx.y | blockIdx.z) == 0 && threadIdx.x == 0) rseq[0] += 1u;
     return;
   }
-  forward_tile<RT, PACKED, SX, SY, LOSS, PACKED, NW>(blockIdx.x, blockIdx.y, ntx, nty, blockIdx.z, src, R,
+  forward_tile<RT, PACKED, SX, SY, LOSS, PACKED, NW, RES>(blockIdx.x, blockIdx.y, ntx, nty, blockIdx.z, src, R,
                                          src_view_stride, setup[blockIdx.z], W, H, cx, cy, rfx, rfy, threshold,
-                                         vec_ok, depth, target, loss_part, spans);
+                                         vec_ok, depth, target, loss_part, spans, rrows);
+  if (rseq && (blockIdx.x | blockIdx.y | blockIdx.z) == 0 && threadIdx.x == 0) rseq[0] += 1u;
   if (count_sync && (blockIdx.x | blockIdx.y) == 0 && threadIdx.x == 0)
     count_close_view(count_sync, (int)gridDim.z, setup[blockIdx.z].bwd_big != 0, close_word);
   // The workspace's epoch advances once per forward call, after its prologue launch (forward_prologue_kernel), and
@@ -1084,7 +1165,6 @@ __device__ __forceinline__ void backward_tile(
                              : dense ? (float)(1 << kDenseBits)
                                      : (HashIs32<Hash>::value ? (float)(1 << (kHashBits < 30 ? kHashBits : 30)) : Hash::kWeightLimit);
   // dense addressing: word = (ix * ny + iy) * nz + iz - c0, formed in float (exact: < 2^24)
-  const float f_nz = (float)nz, f_nynz = (float)(ny * nz);
   const int c0 = (bx0 * ny + by0) * nz + bz0;
   const int rel_max = nvox - (ny * nz + nz + 1) - 1;   // last word a cell's corner 000 may take
   float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -1115,7 +1195,9 @@ __device__ __forceinline__ void backward_tile(
 
     const float adz = fabsf(d.z);
     const float f = scale * adz;   // cu:372
-    const float sg = isc * h;      // s = inv_scale / grid_size (cu:391)
+    float isc_s = isc;             // (formed per pass from its scalar register, like the dense strides below)
+    asm volatile("" : "+s"(isc_s));
+    const float sg = isc_s * h;    // s = inv_scale / grid_size (cu:391)
     const float kf = f * sg * go;  // common factor of the pose terms, times upstream grad
     // position: dc/dp_j = -s * R[j][:]
     const V3 RG = rot_f(s, G);
@@ -1160,6 +1242,12 @@ __device__ __forceinline__ void backward_tile(
       if (dense) {
         // word of corner 000 (the clamp cannot act -- the bounds pass saw this very cell -- and keeps every
         // access inside the box whatever happens)
+        // (the two strides are converted from their scalar registers HERE, in every pass: as values of the whole
+        // tile they were kept in vector registers, spilled under the 64-VGPR cap and reloaded from scratch in front
+        // of the eight adds of every sub-tile pass)
+        int s_nz = nz, s_nynz = ny * nz;
+        asm volatile("" : "+s"(s_nz), "+s"(s_nynz));
+        const float f_nz = (float)s_nz, f_nynz = (float)s_nynz;
         int rel = (int)fmaf(c.bx, f_nynz, fmaf(c.by, f_nz, c.bz)) - c0;
         rel = min(max(rel, 0), rel_max);
         int* p0 = lds.dense + rel;
@@ -1284,8 +1372,14 @@ __device__ __forceinline__ void backward_dispatch(
 
 // grid: (tiles x, rows, views): BATCH: the 64 x 8 tiling's columns x backward_batch_rows(H); else the 32 x 8 tiling
 // 8 waves per SIMD for the backward: the register allocator is held to 64 VGPRs (it takes 67 on its own: 7 waves
-// per SIMD; the price is 8 bytes of scratch): stand-alone backward 134.6 -> 129.3 us, a step's 117.8 -> 116.6 us at the
-// benchmark, mug-sized objects unchanged.  0: the compiler's own choice (timing experiments).
+// per SIMD; the price is 8 - 12 bytes of scratch in the one-tile forms): stand-alone backward 134.6 -> 129.3 us, a
+// step's 117.8 -> 116.6 us at the benchmark, mug-sized objects unchanged.  0: the compiler's own choice (timing
+// experiments).  The half-grid form (PAIR: the 32 x 32 tile and the loop over two 64 x 8 tiles in one kernel) keeps
+// more tile-uniform values alive and spills more of them, 96 bytes at R = 64 -- what matters is WHERE: values the
+// per-pixel passes need (the dense box's strides, inv_scale * h) are formed from scalar registers inside the pass
+// (backward_tile), so that the 32 x 32 tile's four passes touch no scratch (with two reloads in front of the eight
+// adds of every pass the benchmark's backward kernel took 95.5 us, without 92.8); the spills left are in the
+// two-tile loop's set-up.
 // (The single-view tiling's workgroups hold 21 KB of LDS each: seven of them, 7 waves per SIMD, is what a CU takes
 // whatever the registers -- there the target is 7, which the compiler's own 67 VGPRs meet without a spill; asking for
 // 8 only earned "failed to meet occupancy target" from every such instantiation of a clean build.)
@@ -1572,6 +1666,7 @@ size_t packed_bytes(int R) { return (size_t)R * record_slab(R) * 4 * sizeof(floa
 // (between the sync region and the call's scratch: the band spans, common.hpp)
 size_t sync_offset(int B) { return setup_bytes(B); }
 size_t scratch_offset(int B, int H) { return scratch_offset_bytes(B, H); }
+size_t resident_state_bytes_needed(int B, int H) { return resident_state_bytes(B, H); }
 size_t cells_bytes(int R) { return (R >= 2 && R <= kPackedMaxR) ? packed_bytes(R) : 0; }
 size_t step_partials_offset(int R, int B, int H) { return scratch_offset(B, H) + cells_bytes(R); }
 // deterministic d/dSDF: a 64-bit fixed-point volume behind the tile partials (grids up to kDetMaxR)
@@ -1666,7 +1761,9 @@ int forward_impl(const char* fn, const float* sdf, int R, long long sdf_view_str
                  const float* quat, const float* inv_scale, int B, int W, int H, float cx, float cy,
                  float fx, float fy, float threshold, float* depth, const float* target, float* loss,
                  float* loss_stats, void* workspace, size_t workspace_bytes, size_t need, const ForwardLayout& lay,
-                 float* g_zero, size_t n_zero, int device, void* stream, unsigned long long* close_word = nullptr) {
+                 float* g_zero, size_t n_zero, int device, void* stream, unsigned long long* close_word = nullptr,
+                 void* resident_state = nullptr, size_t resident_state_bytes = 0, int depth_resident = 0) {
+  // resident_state (nullable; sdfr_render_forward_resident): the caller's state of THIS depth buffer (common.hpp)
   const bool with_loss = target != nullptr;
   if (int rc = check_common(R, B, W, H, fx, fy)) return rc;
   if (sdf_view_stride != 0 && sdf_view_stride < (long long)R * R * R)
@@ -1684,6 +1781,10 @@ int forward_impl(const char* fn, const float* sdf, int R, long long sdf_view_str
     return fail(SDFR_E_WORKSPACE, "%s: workspace %zu < %zu bytes", fn, workspace_bytes, need);
   if ((uintptr_t)workspace % alignof(ViewSetup))
     return fail(SDFR_E_INVALID, "workspace must be %zu-byte aligned", alignof(ViewSetup));
+  if (resident_state && resident_state_bytes < resident_state_bytes_needed(B, H))
+    return fail(SDFR_E_WORKSPACE, "%s: resident state %zu < %zu bytes", fn, resident_state_bytes,
+                resident_state_bytes_needed(B, H));
+  if ((uintptr_t)resident_state % 128) return fail(SDFR_E_INVALID, "%s: resident state must be 128-byte aligned", fn);
   SDFR_HIP_TRY(hipSetDevice(device));
   hipStream_t st = (hipStream_t)stream;
   ViewSetup* setup = lay.setup;
@@ -1694,6 +1795,12 @@ int forward_impl(const char* fn, const float* sdf, int R, long long sdf_view_str
   // (small tiles: the set-up each workgroup repeats is amortised over one 32 x 8 tile, so only where launches are
   // what a call costs)
   const bool inline_setup = g_zero && !packed && geom.sx * geom.sy == 1 && B <= kInlineSetupMaxViews;
+  // Resident depth: the forms whose views are set up by a wave each over the packed grid (both prologues below) keep
+  // the state's rows and their culled tiles clear only what the rows say; every other form stores all its zeros as
+  // before and only advances the state's sequence number, which makes the rows it did not write stale.
+  unsigned* rseq = (unsigned*)resident_state;
+  unsigned* rstate = (rseq && packed && !with_loss && W <= 65535) ? rseq : nullptr;
+  const unsigned* rrows = rstate ? rstate + kResidentHeaderWords : nullptr;
   unsigned* epoch = nullptr;
   // (the one-launch prologue reads the grid with 16-byte loads: other grids take the two-launch form)
   if (packed && (R & 3) == 0 && ((uintptr_t)sdf & 15) == 0) {
@@ -1701,7 +1808,7 @@ int forward_impl(const char* fn, const float* sdf, int R, long long sdf_view_str
     hipLaunchKernelGGL(forward_prologue_kernel, dim3(3 * R + n_setup + n_pack), dim3(256), 0, st, sdf, R,
                        (float4*)cells, 3 * R, n_setup, lay.sync, pos, quat, inv_scale, B, W, H, cx, cy, fx, fy,
                        setup, threshold, g_zero, n_zero, kPrologueMaxPolls,
-                       lay.spans);
+                       lay.spans, rstate, depth_resident);
     epoch = lay.sync;
   } else if (g_zero && !packed && inline_setup) {
     // a step over a few views of the plain grid: no prologue launch at all (render_forward_kernel, INLINE)
@@ -1721,7 +1828,8 @@ int forward_impl(const char* fn, const float* sdf, int R, long long sdf_view_str
                          (float4*)cells, n_pack, plane_min);
     }
     hipLaunchKernelGGL(view_setup_kernel, dim3(B), dim3(64), 0, st, pos, quat, inv_scale, B, R,
-                       W, H, cx, cy, fx, fy, setup, plane_min, threshold, lay.spans);
+                       W, H, cx, cy, fx, fy, setup, plane_min, threshold, lay.spans, packed ? rstate : nullptr,
+                       depth_resident);
   }
   const bool macro = geom.sx * geom.sy > 1;
   const int ntx = geom.nx(W), nty = geom.ny(H);
@@ -1730,11 +1838,17 @@ int forward_impl(const char* fn, const float* sdf, int R, long long sdf_view_str
   // a step's forward over a batch counts its close views (count_close_view): what the backward's half-grid hint needs
   unsigned* count_sync = (g_zero && !inline_setup && macro) ? lay.sync : nullptr;
   const int vec_ok = (W % 4 == 0) && ((uintptr_t)depth % 16 == 0);
-#define SDFR_LAUNCH_FWD_L(RT, PK, SRC, STRIDE, SX, SY, LOSS)                                          \
-  hipLaunchKernelGGL((render_forward_kernel<RT, PK, SX, SY, LOSS, (SX * SY > 1 && SX < 4 ? kFwdWaves : 4)>), grid_tile, \
-                     dim3((SX * SY > 1 && SX < 4 ? kFwdWaves : 4) * 64), 0, st, \
+#define SDFR_LAUNCH_FWD_R(RT, PK, SRC, STRIDE, SX, SY, LOSS, RES)                                     \
+  hipLaunchKernelGGL((render_forward_kernel<RT, PK, SX, SY, LOSS, (SX * SY > 1 && SX < 4 ? kFwdWaves : 4), false, RES>), \
+                     grid_tile, dim3((SX * SY > 1 && SX < 4 ? kFwdWaves : 4) * 64), 0, st, \
                      SRC, R, STRIDE, setup, W, H, ntx, nty, cx, cy, rfx, rfy, threshold, vec_ok,      \
-                     depth, target, loss_part, epoch, lay.spans, InlineSetup{}, count_sync, close_word)
+                     depth, target, loss_part, epoch, lay.spans, InlineSetup{}, count_sync, close_word, rrows, rseq)
+  // (rows are kept only over the packed grid and without the loss: the other instantiations have no resident form)
+#define SDFR_LAUNCH_FWD_L(RT, PK, SRC, STRIDE, SX, SY, LOSS)                                          \
+  do {                                                                                               \
+    if (rrows) SDFR_LAUNCH_FWD_R(RT, PK, SRC, STRIDE, SX, SY, LOSS, (PK && !LOSS));                  \
+    else SDFR_LAUNCH_FWD_R(RT, PK, SRC, STRIDE, SX, SY, LOSS, false);                                \
+  } while (0)
 #define SDFR_LAUNCH_FWD_G(RT, PK, SRC, STRIDE, SX, SY)                                               \
   do {                                                                                               \
     if (with_loss) SDFR_LAUNCH_FWD_L(RT, PK, SRC, STRIDE, SX, SY, true);                             \
@@ -1751,7 +1865,8 @@ int forward_impl(const char* fn, const float* sdf, int R, long long sdf_view_str
 #define SDFR_LAUNCH_INLINE(RT, LOSS)                                                                              \
   hipLaunchKernelGGL((render_forward_kernel<RT, false, 1, 1, LOSS, 4, true>), grid_tile, dim3(256), 0, st, sdf, R, \
                      sdf_view_stride, setup, W, H, ntx, nty, cx, cy, rfx, rfy, threshold, vec_ok, depth, target,  \
-                     loss_part, epoch, lay.spans, in, (unsigned*)nullptr, (unsigned long long*)nullptr)
+                     loss_part, epoch, lay.spans, in, (unsigned*)nullptr, (unsigned long long*)nullptr,             \
+                     (const unsigned*)nullptr, rseq)
     if (R == 64) { if (with_loss) SDFR_LAUNCH_INLINE(64, true); else SDFR_LAUNCH_INLINE(64, false); }
     else { if (with_loss) SDFR_LAUNCH_INLINE(0, true); else SDFR_LAUNCH_INLINE(0, false); }
 #undef SDFR_LAUNCH_INLINE
@@ -1763,6 +1878,7 @@ int forward_impl(const char* fn, const float* sdf, int R, long long sdf_view_str
 #undef SDFR_LAUNCH_FWD
 #undef SDFR_LAUNCH_FWD_G
 #undef SDFR_LAUNCH_FWD_L
+#undef SDFR_LAUNCH_FWD_R
   if (with_loss && loss)   // (loss == NULL: a step whose backward reduces the records, LossTiles)
     hipLaunchKernelGGL(loss_reduce_kernel, dim3(B), dim3(64), 0, st, loss_part, setup, ntx, nty, geom.w(),
                        geom.h(), loss, loss_stats);
@@ -1780,6 +1896,20 @@ extern "C" int sdfr_render_forward(const float* sdf, int R, long long sdf_view_s
                       cy, fx, fy, threshold, depth, nullptr, nullptr, nullptr, workspace,
                       workspace_bytes, sdfr_render_forward_workspace_bytes(R, B, W, H),
                       plain_forward_layout(workspace, R, B, W, H), nullptr, 0, device, stream);
+}
+
+extern "C" size_t sdfr_render_resident_state_bytes(int B, int H) { return resident_state_bytes(B, H); }
+
+extern "C" int sdfr_render_forward_resident(const float* sdf, int R, long long sdf_view_stride, const float* pos,
+                                            const float* quat, const float* inv_scale, int B, int W, int H, float cx,
+                                            float cy, float fx, float fy, float threshold, float* depth,
+                                            void* workspace, size_t workspace_bytes, void* resident_state,
+                                            size_t resident_state_bytes, int depth_resident, int device,
+                                            void* stream) {
+  return forward_impl("sdfr_render_forward_resident", sdf, R, sdf_view_stride, pos, quat, inv_scale, B, W, H, cx, cy,
+                      fx, fy, threshold, depth, nullptr, nullptr, nullptr, workspace, workspace_bytes,
+                      sdfr_render_forward_workspace_bytes(R, B, W, H), plain_forward_layout(workspace, R, B, W, H),
+                      nullptr, 0, device, stream, nullptr, resident_state, resident_state_bytes, depth_resident);
 }
 
 extern "C" int sdfr_render_forward_l1(const float* sdf, int R, long long sdf_view_stride,
@@ -1980,6 +2110,18 @@ extern "C" int sdfr_render_step_forward_counted(const float* sdf, int R, long lo
                                                 float* g_sdf, long long g_sdf_view_stride, void* workspace,
                                                 size_t workspace_bytes, unsigned long long* close_views_word,
                                                 int device, void* stream) {
+  return sdfr_render_step_forward_resident(sdf, R, sdf_view_stride, pos, quat, inv_scale, B, W, H, cx, cy, fx, fy,
+                                           threshold, depth, g_sdf, g_sdf_view_stride, workspace, workspace_bytes,
+                                           close_views_word, nullptr, 0, 0, device, stream);
+}
+
+extern "C" int sdfr_render_step_forward_resident(const float* sdf, int R, long long sdf_view_stride, const float* pos,
+                                                 const float* quat, const float* inv_scale, int B, int W, int H,
+                                                 float cx, float cy, float fx, float fy, float threshold, float* depth,
+                                                 float* g_sdf, long long g_sdf_view_stride, void* workspace,
+                                                 size_t workspace_bytes, unsigned long long* close_views_word,
+                                                 void* resident_state, size_t resident_state_bytes,
+                                                 int depth_resident, int device, void* stream) {
   const char* fn = "sdfr_render_step_forward";
   if ((uintptr_t)close_views_word % 8) return fail(SDFR_E_INVALID, "%s: close_views_word must be 8-byte aligned", fn);
   const long long vox = (long long)R * R * R;
@@ -1999,7 +2141,7 @@ extern "C" int sdfr_render_step_forward_counted(const float* sdf, int R, long lo
   return forward_impl(fn, sdf, R, sdf_view_stride, pos, quat, inv_scale, B, W, H, cx, cy, fx, fy, threshold, depth,
                       nullptr, nullptr, nullptr, workspace, workspace_bytes,
                       sdfr_render_step_workspace_bytes(R, B, W, H), lay, g_sdf, g_words, device, stream,
-                      close_views_word);
+                      close_views_word, resident_state, resident_state_bytes, depth_resident);
 }
 
 extern "C" int sdfr_render_step_forward_l1(const float* sdf, int R, long long sdf_view_stride, const float* pos,

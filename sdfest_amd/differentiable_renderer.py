@@ -456,6 +456,19 @@ class BatchRenderPlan:
     This is how a production loop drives the C ABI: every output and the workspace are
     allocated once, each step is a fixed sequence of launches on one stream, so the step can
     be captured into a hipGraph (``capture()``).
+
+    **Resident depth.**  ``forward`` renders into the same buffer call after call, and most of a batch's pixels lie
+    outside every view's may-hit region: zeros that were already there after the previous call.  The plan therefore
+    keeps a small device-side state per destination buffer (``sdfr_render_forward_resident``, include/sdfr.h) and
+    tells the library that the buffer still holds what the plan's previous ``forward`` left there -- culled tiles then
+    store zeros only where the previous call's live region has to be cleared -- when all of this holds: the same
+    destination tensor, with the same ``data_ptr()`` and ``_version`` as after that forward; ``workspace._version``
+    unchanged; and no other method of the plan called since, apart from that step's own ``backward``.  Anything else
+    (``forward_l1``, the fused step, a stand-alone ``backward``, ``ring_reset``, another ``out=``, the first call)
+    costs one call that stores every pixel.  A torch in-place write into ``plan.depth`` (or into ``out``) is seen by
+    the version counter; a write through a raw pointer is not (``tensor.data``, a kernel of the caller's, the replay of
+    a graph that writes it): **treat the depth buffer as read-only for such writers**.  The images are bit for bit
+    what they are without the state.
     """
 
     def __init__(self, R: int, B: int, camera: Camera, device="cuda", per_view_sdf: bool = False,
@@ -515,6 +528,11 @@ class BatchRenderPlan:
         self._g_sdf_next = 0
         self._g_sdf_index = grad_volumes - 1   # which volume of the ring self.g_sdf is
         self._step = None   # what the last forward prepared: (tensor ids / versions, depth tensor)
+        # resident depth (class docstring): the state of the buffer the last forward rendered into, and what that
+        # buffer and the workspace looked like afterwards -- None whenever the next forward must store every pixel
+        self._resident_state = torch.zeros(L.sdfr_render_resident_state_bytes(B, self.H), dtype=torch.uint8,
+                                           device=self.device)
+        self._resident = None
         self._fixed_layout = None   # deterministic mode: which workspace layout holds the last int64 volume
         self._step_l1 = None        # the volume a forward_l1(prepare_backward=True) zero-filled
         self.partials_offset = 0    # where the last backward_l1_pc left its tile partials (sdfr_loop_tail)
@@ -563,6 +581,7 @@ class BatchRenderPlan:
         self._g_sdf_next = 0
         self._step = None
         self._step_l1 = None
+        self._resident = None
 
     def close_views_seen(self):
         """(forwards counted so far, close views of the latest counted one) as the pinned word holds them right now
@@ -622,24 +641,31 @@ class BatchRenderPlan:
                                 or not out.is_contiguous() or out.device != self.depth.device):
             raise RuntimeError("out must be a contiguous float32 tensor of shape (B, H, W) on the plan's device")
         self._step_l1 = None   # a forward_l1(prepare_backward=True) whose backward never came: its view records are gone
+        # resident depth (class docstring): is `dst` still what this plan's previous forward left in it?
+        seen, self._resident = self._resident, None
+        resident = int(seen is not None and seen[0] is dst
+                       and seen[1:] == (dst.data_ptr(), dst._version, self.workspace._version))
+        state = self._resident_state
         if prepare_backward:
             nxt = self._g_sdf_ring[self._g_sdf_next]
-            rc = self._L.sdfr_render_step_forward_counted(
+            rc = self._L.sdfr_render_step_forward_resident(
                 sdf.data_ptr(), self.R, self.sdf_stride, pos.data_ptr(), quat.data_ptr(),
                 inv_scale.data_ptr(), self.B, self.W, self.H, self.cx, self.cy, self.fx, self.fy,
                 threshold, dst.data_ptr(), nxt.data_ptr(), self.sdf_stride, self.workspace.data_ptr(),
                 self.workspace.numel(), self._close_word.data_ptr() if self._close_auto else None,
-                self.device.index, _stream(self.device))
+                state.data_ptr(), state.numel(), resident, self.device.index, _stream(self.device))
             _lib.check(rc, "sdfr_render_step_forward")
             self._step = (self._key(sdf, pos, quat, inv_scale), dst, nxt)
+            self._resident = (dst, dst.data_ptr(), dst._version, self.workspace._version)
             return dst
         self._step = None
-        rc = self._L.sdfr_render_forward(
+        rc = self._L.sdfr_render_forward_resident(
             sdf.data_ptr(), self.R, self.sdf_stride, pos.data_ptr(), quat.data_ptr(),
             inv_scale.data_ptr(), self.B, self.W, self.H, self.cx, self.cy, self.fx, self.fy,
             threshold, dst.data_ptr(), self.workspace.data_ptr(), self.workspace.numel(),
-            self.device.index, _stream(self.device))
+            state.data_ptr(), state.numel(), resident, self.device.index, _stream(self.device))
         _lib.check(rc, "sdfr_render_forward")
+        self._resident = (dst, dst.data_ptr(), dst._version, self.workspace._version)
         return dst
 
     def backward(self, grad_depth, sdf, pos, quat, inv_scale, defer_pose: bool = False):
@@ -675,6 +701,7 @@ class BatchRenderPlan:
             self._g_sdf_next = (self._g_sdf_next + 1) % len(self._g_sdf_ring)
             self._fixed_layout = 1
             return self.g_sdf, self.g_pos, self.g_quat, self.g_inv_scale
+        self._resident = None   # (a stand-alone backward: not the step's own)
         depth = self.depth
         if step is not None:
             # a prepared step whose backward cannot run as such (other tensors, or deferred pose sums): the
@@ -718,6 +745,7 @@ class BatchRenderPlan:
         by the step's backward instead (same bits; include/sdfr.h, "DEFERRED LOSS").  The caller promises that the
         step's backward follows, on the same tensors."""
         self._step = None   # the workspace is about to be re-used
+        self._resident = None
         self._check(sdf, pos, quat, inv_scale, target=target)
         if defer_loss and not prepare_backward:
             raise ValueError("defer_loss goes with prepare_backward")
@@ -748,6 +776,7 @@ class BatchRenderPlan:
         """gradients of sum_b weight * loss_grad[b] * loss[b] (after ``forward_l1``); ``defer_pose`` as in
         ``backward``."""
         self._step = None   # the workspace is about to be re-used
+        self._resident = None
         prepared, self._step_l1 = self._step_l1, None
         self._check(sdf, pos, quat, inv_scale, target=target)
         if loss_grad is not None:
@@ -808,6 +837,7 @@ class BatchRenderPlan:
         ``sdfr_loop_tail_fused``).  Returns the depth images."""
         self._step = None
         self._step_l1 = None
+        self._resident = None
         self._check(sdf, pos, quat, inv_scale, target=target)
         rc = self._L.sdfr_render_step_fused_l1_pc(
             sdf.data_ptr(), self.R, self.sdf_stride, pos.data_ptr(), quat.data_ptr(), inv_scale.data_ptr(),
@@ -840,6 +870,7 @@ class BatchRenderPlan:
         (``sdfr_render_backward_l1_pc``): g_sdf holds both terms, the pose gradients stay deferred in
         ``self.workspace`` and ``pc_workspace`` for ``sdfr_views_to_pose_grad_deferred``."""
         self._step = None   # the workspace is about to be re-used
+        self._resident = None
         self._check(sdf, pos, quat, inv_scale, target=target)
         dev = self.device
         if not (scale.device == dev and scale.dtype is torch.float32 and scale.shape == self._shape_isc

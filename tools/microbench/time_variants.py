@@ -39,11 +39,15 @@ def main():
     if mode == "offscreen":
         pos = pos.clone(); pos[:, 0] += 100.0
     libs = []
+    states = {}
     for path in sys.argv[1:]:
         L = load(path)
         nb = max(L.sdfr_render_forward_workspace_bytes(64, B, W, H), L.sdfr_render_backward_workspace_bytes(64, B, W, H))
         if hasattr(L, "sdfr_render_step_workspace_bytes"): nb = max(nb, L.sdfr_render_step_workspace_bytes(64, B, W, H))
         libs.append((path, L, torch.empty(nb + 256, dtype=torch.uint8, device=dev)))
+        # the resident-depth state of `depth` (include/sdfr.h, sdfr_render_forward_resident), one per build that has it
+        if hasattr(L, "sdfr_render_resident_state_bytes"):
+            states[path] = torch.zeros(L.sdfr_render_resident_state_bytes(B, H), dtype=torch.uint8, device=dev)
     st = torch.cuda.current_stream().cuda_stream
     def fwd(L, ws):
         rc = L.sdfr_render_forward(sdf.data_ptr(), 64, 0, pos.data_ptr(), quat.data_ptr(), isc.data_ptr(), B, W, H,
@@ -64,10 +68,24 @@ def main():
                                          gs2.data_ptr(), 0, gp.data_ptr(), gq.data_ptr(), gi.data_ptr(), ws.data_ptr(),
                                          ws.numel(), 0, st)
         assert rc == 0, L.sdfr_last_error()
+    # the resident forms: the first call of a run does not vouch for `depth` (the other forms wrote it), the timed ones do
+    def rfwd(L, ws, path, vouch):
+        s8 = states[path]
+        rc = L.sdfr_render_forward_resident(sdf.data_ptr(), 64, 0, pos.data_ptr(), quat.data_ptr(), isc.data_ptr(), B, W, H,
+                                            cxx, cyy, f, f, thr, depth.data_ptr(), ws.data_ptr(), ws.numel(), s8.data_ptr(),
+                                            s8.numel(), vouch, 0, st)
+        assert rc == 0, L.sdfr_last_error()
+    def rsfwd(L, ws, path, vouch):
+        s8 = states[path]
+        rc = L.sdfr_render_step_forward_resident(sdf.data_ptr(), 64, 0, pos.data_ptr(), quat.data_ptr(), isc.data_ptr(), B,
+                                                 W, H, cxx, cyy, f, f, thr, depth.data_ptr(), gs2.data_ptr(), 0, ws.data_ptr(),
+                                                 ws.numel(), None, s8.data_ptr(), s8.numel(), vouch, 0, st)
+        assert rc == 0, L.sdfr_last_error()
     def pair(L, ws): fwd(L, ws); bwd(L, ws)
     def step(L, ws): sfwd(L, ws); sbwd(L, ws)
     rounds = int(os.environ.get("ROUNDS", 7))
-    res = {path: {"fwd": [], "bwd": [], "pair": [], "step": [], "sfwd": []} for path, _, _ in libs}
+    res = {path: {"fwd": [], "bwd": [], "pair": [], "step": [], "sfwd": [], "rfwd": [], "rsfwd": [], "rstep": []}
+           for path, _, _ in libs}
     with_step = os.environ.get("STEP", "1") == "1"
     for r in range(rounds + 1):
         for path, L, ws in libs:
@@ -76,8 +94,17 @@ def main():
                 fns.append(("pair", pair))
                 if hasattr(L, "sdfr_render_step_forward"):
                     fns += [("sfwd", sfwd), ("step", step)]
+            if path in states:
+                fns.append(("rfwd", lambda L, ws, v=1, p=path: rfwd(L, ws, p, v)))
+                if with_step:
+                    fns.append(("rsfwd", lambda L, ws, v=1, p=path: rsfwd(L, ws, p, v)))
+                    fns.append(("rstep", lambda L, ws, v=1, p=path: (rsfwd(L, ws, p, v), sbwd(L, ws))))
             for name, fn in fns:
-                fn(L, ws); torch.cuda.synchronize()
+                if name.startswith("r"):
+                    fn(L, ws, 0)
+                else:
+                    fn(L, ws)
+                torch.cuda.synchronize()
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 n = 10
                 e0.record()
