@@ -36,6 +36,7 @@
 
 #include "common.hpp"
 #include "decoder_fc.hpp"
+#include "decoder_host.hpp"
 
 struct sdfr_decoder {
   int device;
@@ -55,6 +56,9 @@ struct sdfr_decoder {
   // transposed-resize tables of the fused VJP stages (vjp_stage_kernel): for the resize in FRONT of layer l (conv_prev[l]
   // -> conv_in_size[l]), a row of 16 words per coarse index: first source (int), taps (int), 12 weights; 0: none
   std::vector<size_t> rs_tab_off;
+  // source ranges of every resize of the decoder (in front of a layer, and the final one to the volume), one entry per
+  // distinct (n_in, n_out): see resize_sources_of
+  std::vector<sdfr::ResizeSources> rs_src;
   // z-grouped contraction for layers with few output channels (see conv3d_mfma_kernel): per layer,
   // forward and data-gradient
   struct ZPlan {
@@ -1743,16 +1747,28 @@ using namespace sdfr;
 
 namespace {
 // conv3d_mfma_kernel's split-K form: for launches with so few tiles that a wave's K loop is the critical path
-#ifndef SDFR_SPLITK_MAX_TILES
-#define SDFR_SPLITK_MAX_TILES 2048
-#endif
 int use_split_k(bool zgrp, int n_tiles, int co_tiles, int N, int kpad) {
   // (the choice does not depend on N up to 16 samples: small batches decode bit-identically to single latents)
   return (!zgrp && (long long)n_tiles * co_tiles <= SDFR_SPLITK_MAX_TILES && N <= SDFR_SPLITK_MAX_LATENTS && kpad >= 128) ? 1 : 0;
 }
 
-// The direct convolution is for batches (enough tiles to fill the chip); returns false when the
-// layer / batch does not qualify and the caller falls back to the MFMA kernel.
+// A kernel's dynamic-LDS limit (MaxDynamicSharedMemorySize) raised to `bytes` once -- above 64 KiB it must be; `bytes` +
+// the kernel's static LDS <= 160 KiB.  false: the runtime refused, and the caller takes its other form.
+// Keyed by the kernel alone: the first answer holds for every device of the process.  (Per-device keying is a
+// change to this key -- the pair (device, fn) -- and to nothing else.)
+bool raise_lds_limit(const void* fn, size_t bytes) {
+  static std::map<const void*, bool> done;
+  static std::mutex mu;
+  std::lock_guard<std::mutex> lock(mu);
+  auto it = done.find(fn);
+  if (it == done.end()) {
+    const bool ok = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess;
+    if (!ok) (void)hipGetLastError();   // (not an error of the call that asked: it takes the other form)
+    it = done.emplace(fn, ok).first;
+  }
+  return it->second;
+}
+
 // conv3d_mfma_kernel in the form the layer / batch takes (plain, z-grouped, split-K, input resident in LDS)
 void launch_mfma(const float* src, const float* w, const int* tab, const float* bias, float* dst, int cin, int cout,
                  int n, int m, int kp, int relu, int nt, int co_tiles, int zg, int split, int N, hipStream_t st) {
@@ -1761,20 +1777,17 @@ void launch_mfma(const float* src, const float* w, const int* tab, const float* 
   // (resident: the whole grid is then N * co_tiles workgroups -- only where that still fills the chip)
   const bool resident = !split && zg == 1 && N * co_tiles >= 128 && nt >= 8 && nt <= 64 && lds_res <= 120 * 1024 &&
                         (in_floats & 3) == 0 && ((uintptr_t)src & 15) == 0;
-  if (resident) {
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3d_mfma_kernel<true>),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024);
-    if (attr == hipSuccess) {
-      hipLaunchKernelGGL(conv3d_mfma_kernel<true>, dim3(1, co_tiles, N), dim3(256), lds_res, st, src, w, tab, bias, dst,
-                         cin, cout, n, m, kp, relu, 1, 1, 0);
-      return;
-    }
+  if (resident && raise_lds_limit(reinterpret_cast<const void*>(&conv3d_mfma_kernel<true>), 120 * 1024)) {
+    hipLaunchKernelGGL(conv3d_mfma_kernel<true>, dim3(1, co_tiles, N), dim3(256), lds_res, st, src, w, tab, bias, dst,
+                       cin, cout, n, m, kp, relu, 1, 1, 0);
+    return;
   }
   hipLaunchKernelGGL(conv3d_mfma_kernel<false>, dim3(split ? nt : (nt + 4 * tw - 1) / (4 * tw), co_tiles, N), dim3(256),
                      (size_t)kp * 17 * sizeof(float) + (split ? 4096 : 0), st, src, w, tab, bias, dst, cin, cout, n, m,
                      kp, relu, tw, zg, split);
 }
 
+// The direct convolution is for batches (enough tiles to fill the chip).
 // Does a layer / batch qualify for it?  (n: input size, m: output size)
 bool direct_ok(size_t w_off, int n, int m, int N, int* tx = nullptr, int* ty = nullptr, int* zc = nullptr) {
   if (w_off == 0 || n > 64 || m < 4) return false;
@@ -1805,6 +1818,7 @@ bool direct_ok(size_t w_off, int n, int m, int N, int* tx = nullptr, int* ty = n
   if (zc) *zc = zc_pow;
   return true;
 }
+// Returns false when the layer / batch does not qualify and the caller falls back to the MFMA kernel.
 // pz: floats between the z-rows of src (n, or more: the padded tensors of the backward pass)
 // mix_*: the 1x1x1 layer applied in the epilogue (conv3d_direct_kernel), or mix_out == NULL
 bool launch_direct(const sdfr_decoder* d, size_t w_off, const float* src, const float* bias, float* dst,
@@ -1822,13 +1836,13 @@ bool launch_direct(const sdfr_decoder* d, size_t w_off, const float* src, const 
   // 16-byte loads: runs start and end on 16-byte boundaries, offsets and channel fit the packed word of the prefetch
   const bool vec4 = (pz & 3) == 0 && ((uintptr_t)src & 15) == 0 && (size_t)CK * n * n * pz < 0xffffff && CK < 127;
   if (!vec4 && pz != n) return false;   // (the scalar-load form takes dense rows only; callers pad rows only to 16 bytes)
-#define SDFR_DIRECT(CO)                                                                                          \
-  if (vec4) hipLaunchKernelGGL((conv3d_direct_kernel<CO, true>), grid, dim3(256), lds, st, src, w, bias, dst,   \
-                               cin, n, pz, m, relu, TX, TY, ZC, CK, mix_w, mix_b, mix_co, mix_out);             \
-  else hipLaunchKernelGGL((conv3d_direct_kernel<CO, false>), grid, dim3(256), lds, st, src, w, bias, dst, cin,  \
-                          n, pz, m, relu, TX, TY, ZC, CK, mix_w, mix_b, mix_co, mix_out)
-  if (cout == 4) { SDFR_DIRECT(4); } else if (cout == 8) { SDFR_DIRECT(8); } else { SDFR_DIRECT(16); }
-#undef SDFR_DIRECT
+  dispatch_int_else_last<4, 8, 16>(cout, [&](auto co) {
+    constexpr int CO = decltype(co)::value;
+    if (vec4) hipLaunchKernelGGL((conv3d_direct_kernel<CO, true>), grid, dim3(256), lds, st, src, w, bias, dst, cin, n, pz, m,
+                                 relu, TX, TY, ZC, CK, mix_w, mix_b, mix_co, mix_out);
+    else hipLaunchKernelGGL((conv3d_direct_kernel<CO, false>), grid, dim3(256), lds, st, src, w, bias, dst, cin, n, pz, m,
+                            relu, TX, TY, ZC, CK, mix_w, mix_b, mix_co, mix_out);
+  });
   return true;
 }
 
@@ -1849,24 +1863,7 @@ bool launch_direct_up(const sdfr_decoder* d, size_t w_off, const float* src, int
   const int IX = TX + 2, IY = TY + 2;
   if (IX > 34 || IY > 34) return false;
   // coarse columns under a patch, worst tile (the kernel's float arithmetic)
-  const float ratio = (float)ni / (float)n;
-  auto first_last = [&](int dd, int& i0, int& i1) {
-    float sp = fmaf(ratio, (float)dd + 0.5f, -0.5f);
-    sp = sp < 0.0f ? 0.0f : sp;
-    i0 = std::min((int)sp, ni - 1);
-    i1 = i0 + (i0 < ni - 1 ? 1 : 0);
-  };
-  auto span = [&](int T, int I) {
-    int worst = 0;
-    for (int t0 = 0; t0 < m; t0 += T) {
-      int lo, hi, tmp;
-      first_last(t0, lo, tmp);
-      first_last(std::min(t0 + I, n) - 1, tmp, hi);
-      worst = std::max(worst, hi - lo + 1);
-    }
-    return worst;
-  };
-  const int max_cols = span(TX, IX) * span(TY, IY);
+  const int max_cols = host_resize_span(ni, n, m, TX, IX) * host_resize_span(ni, n, m, TY, IY);
   const int per_ch = IX * IY * n;
   int CK = std::max(1, std::min(cin, (24 * 1024 / 4) / per_ch));
   CK = std::min(CK, 2048 / (max_cols * ni));      // <= 8 prefetched values per thread
@@ -1878,40 +1875,25 @@ bool launch_direct_up(const sdfr_decoder* d, size_t w_off, const float* src, int
   const int tiles = ((m + TX - 1) / TX) * ((m + TY - 1) / TY);
   const dim3 grid(tiles, 1, N);
   const float* w = d->d_params + w_off;
-#define SDFR_DIRECT_UP(CO)                                                                                           \
-  hipLaunchKernelGGL((conv3d_direct_up_kernel<CO>), grid, dim3(256), lds, st, src, ni, w, bias, dst, cin, n, log_n, \
-                     m, relu, TX, TY, ZC, CK, max_cols)
-  if (cout == 4) { SDFR_DIRECT_UP(4); } else if (cout == 8) { SDFR_DIRECT_UP(8); } else if (cout == 16) { SDFR_DIRECT_UP(16); }
-  else return false;
-#undef SDFR_DIRECT_UP
-  return true;
+  return dispatch_int<4, 8, 16>(cout, [&](auto co) {
+    hipLaunchKernelGGL((conv3d_direct_up_kernel<decltype(co)::value>), grid, dim3(256), lds, st, src, ni, w, bias, dst, cin,
+                       n, log_n, m, relu, TX, TY, ZC, CK, max_cols);
+  });
 }
 
 // ---- few latents: layer pairs as one launch each (decoder_fused.hpp) --------------------------------------------------
 constexpr size_t kFusedLdsMax = 150 * 1024;
 
-// the kernel's dynamic-LDS limit raised once (above 64 KiB it must be; `bytes` + the kernel's static LDS <= 160 KiB);
-// false: the runtime refused, take the unfused form
-bool fused_lds_limit(const void* fn, size_t bytes = kFusedLdsMax) {
-  static std::map<const void*, bool> done;
-  static std::mutex mu;
-  std::lock_guard<std::mutex> lock(mu);
-  auto it = done.find(fn);
-  if (it == done.end()) {
-    const bool ok = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess;
-    if (!ok) (void)hipGetLastError();   // (not an error of the call that asked: it takes the other form)
-    it = done.emplace(fn, ok).first;
-  }
-  return it->second;
+// the source ranges of the resize n_in -> n_out: kept per decoder at creation; any other pair is computed into `local`
+const ResizeSources* find_resize_sources(const sdfr_decoder* d, int n_in, int n_out) {
+  for (const ResizeSources& r : d->rs_src)
+    if (r.n_in == n_in && r.n_out == n_out) return &r;
+  return nullptr;
 }
-
-// resize_axis on the host (the kernels' float arithmetic)
-void host_resize_axis(int dd, float ratio, int ni, int& i0, int& i1, float& l1) {
-  float sp = fmaf(ratio, (float)dd + 0.5f, -0.5f);
-  sp = sp < 0.0f ? 0.0f : sp;
-  i0 = std::min((int)sp, ni - 1);
-  i1 = i0 + (i0 < ni - 1 ? 1 : 0);
-  l1 = sp - (float)i0;
+const ResizeSources& resize_sources_of(const sdfr_decoder* d, int n_in, int n_out, ResizeSources& local) {
+  if (const ResizeSources* r = find_resize_sources(d, n_in, n_out)) return *r;
+  local = host_resize_sources(n_in, n_out);
+  return local;
 }
 
 // resize ni -> n + the 3x3x3 convolution n -> m behind it in one launch (conv3d_mfma_up_kernel): true if launched.
@@ -1923,35 +1905,18 @@ bool launch_mfma_up(const sdfr_decoder* d, size_t direct_off, const float* src, 
   if (ni > n || ni < 1 || m != n - 2 || m < 1 || direct_ok(direct_off, n, m, N)) return false;
   const int co_tiles = (cout + 15) / 16, ZT = (m + 15) / 16;
   if (ZT > 4 || !use_split_k(false, (m * m * m + 15) / 16, co_tiles, N, kpad)) return false;
-  // columns per workgroup: the smallest tile that gives every workgroup a CU of its own (<= 16 MFMA tiles each)
-  static const int kShapes[][2] = {{1, 1}, {1, 2}, {2, 2}, {2, 3}, {3, 3}, {2, 4}, {3, 4}, {4, 4}};
-  int TX = 1, TY = 1;
-  for (const auto& sh : kShapes) {
-    if (sh[0] * sh[1] * ZT > 16) break;
-    TX = sh[0]; TY = sh[1];
-    if ((long long)((m + TX - 1) / TX) * ((m + TY - 1) / TY) * co_tiles * N <= 256) break;
-  }
+  int TX, TY;   // columns per workgroup
+  few_latent_tile(m, ZT, (long long)co_tiles * N, TX, TY);
   const int tiles = TX * TY * ZT, wpt = 4 * tiles <= 16 ? 4 : 1;
   const int threads = std::max(256, 64 * wpt * tiles);
   const int IX = TX + 2, IY = TY + 2;
-  const float ratio = (float)ni / (float)n;
-  int CX = 1;
-  for (int pass = 0; pass < 2; ++pass) {
-    const int T = pass ? TY : TX, I = pass ? IY : IX;
-    for (int t0 = 0; t0 < m; t0 += T) {
-      int lo, hi, t;
-      float f;
-      host_resize_axis(t0, ratio, ni, lo, t, f);
-      host_resize_axis(std::min(t0 + I, n) - 1, ratio, ni, t, hi, f);
-      CX = std::max(CX, hi - lo + 1);
-    }
-  }
+  const int CX = std::max({1, host_resize_span(ni, n, m, TX, IX), host_resize_span(ni, n, m, TY, IY)});
   const int PZ = 16 * ZT + 2, patch_n = cin * IX * IY * PZ;
   const size_t zc_n = (size_t)cin * CX * CX * PZ;
   if (zc_n >= 65536 || patch_n >= 65536 || threads / PZ < 1 || threads / (IX * IY) < 1) return false;   // (reciprocal divisions)
   const size_t lds = ((size_t)kpad * 17 + (wpt == 4 ? 4 * threads : 0) + ((patch_n + 3) & ~3) + zc_n) * sizeof(float);
   const void* fn = wpt == 4 ? reinterpret_cast<const void*>(&conv3d_mfma_up_kernel<4>) : reinterpret_cast<const void*>(&conv3d_mfma_up_kernel<1>);
-  if (lds > kFusedLdsMax || (lds > 64 * 1024 && !fused_lds_limit(fn))) return false;
+  if (lds > kFusedLdsMax || (lds > 64 * 1024 && !raise_lds_limit(fn, kFusedLdsMax))) return false;
   const dim3 grid(((m + TX - 1) / TX) * ((m + TY - 1) / TY), co_tiles, N);
   if (mix_out && co_tiles != 1) return false;
   if (wpt == 4) hipLaunchKernelGGL(conv3d_mfma_up_kernel<4>, grid, dim3(threads), lds, st, src, ni, w, bias, dst, cin, cout, n,
@@ -1977,7 +1942,7 @@ bool launch_fc_conv(const sdfr_decoder* d, const FcDesc& fd, const float* z, flo
   while (threads < 1024 && threads < items) threads *= 2;
   const size_t lds = ((size_t)kpad * 17 + 4 * threads + patch_n) * sizeof(float);
   const void* fn = reinterpret_cast<const void*>(&fc_conv_kernel);
-  if (lds > 100 * 1024 || (lds > 38 * 1024 && !fused_lds_limit(fn, 100 * 1024))) return false;   // (+ 25 KB static)
+  if (lds > 100 * 1024 || (lds > 38 * 1024 && !raise_lds_limit(fn, 100 * 1024))) return false;   // (+ 25 KB static)
   hipLaunchKernelGGL(fc_conv_kernel, dim3(m * m, co_tiles, N), dim3(threads), lds, st, d->d_params, fd, z, fc_out, w, bias,
                      dst, cin, cout, n, m, kpad, relu, ZT);
   return true;
@@ -2015,35 +1980,11 @@ VjpPlan vjp_stage_plan(const sdfr_decoder* d, int lc, int C, int n_in, int n_out
   if (!split && zp.zg > 1 && (long long)nc * nc * (nc / zp.zg) * N >= kZGroupMinRows) return p;
   p.ZT = (nc + 15) / 16;
   if (p.ZT > 4) return p;
-  // source ranges (resize_sources / resize_weight on the host)
-  const float ratio = (float)n_in / (float)n_out, inv = (float)n_out / (float)n_in;
-  auto weight = [&](int dd, int i) {
-    int i0, i1;
-    float l1;
-    host_resize_axis(dd, ratio, n_in, i0, i1, l1);
-    return (i0 == i ? 1.0f - l1 : 0.0f) + (i1 == i ? l1 : 0.0f);
-  };
-  std::vector<int> lo(n_in), hi(n_in);
-  int max_taps = 1, max_span = 1;
-  for (int i = 0; i < n_in; ++i) {
-    int d0 = std::max((int)floorf(((float)i - 0.5f) * inv - 0.5f) - 1, 0);
-    int d1 = std::min((int)ceilf(((float)i + 1.5f) * inv - 0.5f) + 1, n_out - 1);
-    max_span = std::max(max_span, d1 - d0 + 1);
-    while (d0 <= d1 && weight(d0, i) == 0.0f) ++d0;
-    while (d1 >= d0 && weight(d1, i) == 0.0f) --d1;
-    if (d0 > d1) return p;
-    lo[i] = d0; hi[i] = d1;
-    max_taps = std::max(max_taps, d1 - d0 + 1);
-  }
-  if (max_span > 16 || max_taps > kBtTaps) return p;
-  p.taps = max_taps <= 6 ? 6 : 12;
-  // columns per workgroup: the smallest tile that gives every workgroup a CU of its own
-  static const int kShapes[][2] = {{1, 1}, {1, 2}, {2, 2}, {2, 3}, {3, 3}, {2, 4}, {3, 4}, {4, 4}};
-  for (const auto& sh : kShapes) {
-    if (sh[0] * sh[1] * p.ZT > 16) break;
-    p.TX = sh[0]; p.TY = sh[1];
-    if ((long long)((nc + p.TX - 1) / p.TX) * ((nc + p.TY - 1) / p.TY) * ci_tiles * N <= 256) break;
-  }
+  ResizeSources local;
+  const ResizeSources& rs = resize_sources_of(d, n_in, n_out, local);
+  if (rs.empty || rs.max_span > 16 || rs.max_taps > kBtTaps) return p;
+  p.taps = rs.max_taps <= 6 ? 6 : 12;
+  few_latent_tile(nc, p.ZT, (long long)ci_tiles * N, p.TX, p.TY);   // columns per workgroup
 #ifdef SDFR_VJP_TUNE   // timing experiments: tile shape and workgroup size from the environment
   if (const char* e = getenv("SDFR_VJP_TX")) p.TX = atoi(e);
   if (const char* e = getenv("SDFR_VJP_TY")) p.TY = atoi(e);
@@ -2055,7 +1996,7 @@ VjpPlan vjp_stage_plan(const sdfr_decoder* d, int lc, int C, int n_in, int n_out
   for (int pass = 0; pass < 2; ++pass) {
     const int T = pass ? p.TY : p.TX, I = pass ? IY : IX;
     for (int t0 = 0; t0 < nc; t0 += T)
-      p.FX = std::max(p.FX, hi[std::min(t0 - pad + I - 1, n_in - 1)] - lo[std::max(t0 - pad, 0)] + 1);
+      p.FX = std::max(p.FX, rs.hi[std::min(t0 - pad + I - 1, n_in - 1)] - rs.lo[std::max(t0 - pad, 0)] + 1);
   }
   // channels per round and workgroup size: the whole tensor in one round where the LDS allows
   const int PZ = 16 * p.ZT + 2, patch_n = CP * IX * IY * PZ, RL = zin ? n_out : n_in;
@@ -2106,23 +2047,26 @@ bool launch_vjp_stage(const sdfr_decoder* d, const VjpPlan& p, int lc, const flo
     s.g2 = sg->g2; s.cnt = sg->cnt; s.weight = sg->weight;
   }
   const dim3 grid(((nc + p.TX - 1) / p.TX) * ((nc + p.TY - 1) / p.TY), ci_tiles, N), block(p.threads);
-#define SDFR_VS(CO, TAPS, MODE, ZIN)                                                               \
-  do {                                                                                           \
-    const void* fn = reinterpret_cast<const void*>(&vjp_stage_kernel<CO, TAPS, MODE, ZIN>);      \
-    if (p.lds > 56 * 1024 && !fused_lds_limit(fn, kFusedLdsMax - 8 * 1024)) return false;        \
-    hipLaunchKernelGGL((vjp_stage_kernel<CO, TAPS, MODE, ZIN>), grid, block, p.lds, st, s);      \
-  } while (0)
-#define SDFR_VS_M(CO, TAPS, ZIN) { if (p.mode == 0) SDFR_VS(CO, TAPS, 0, ZIN); else if (p.mode == 4) SDFR_VS(CO, TAPS, 4, ZIN); else SDFR_VS(CO, TAPS, 1, ZIN); }
-#define SDFR_VS_T(CO, ZIN) { if (p.taps == 6) SDFR_VS_M(CO, 6, ZIN) else SDFR_VS_M(CO, 12, ZIN) }
-  if (mix_cout == 0) { if (p.zin) SDFR_VS_T(0, true) else SDFR_VS_T(0, false) }
-  else if (mix_cout == 1) SDFR_VS_T(1, true)
-  else if (mix_cout == 2) SDFR_VS_T(2, true)
-  else if (mix_cout == 3) SDFR_VS_T(3, true)
-  else SDFR_VS_T(4, true)
-#undef SDFR_VS_T
-#undef SDFR_VS_M
-#undef SDFR_VS
-  return true;
+  bool launched = false;
+  auto launch = [&](auto co, auto taps, auto mode, auto zin) {
+    const auto kernel =
+        &vjp_stage_kernel<decltype(co)::value, decltype(taps)::value, decltype(mode)::value, decltype(zin)::value>;
+    if (p.lds > 56 * 1024 && !raise_lds_limit(reinterpret_cast<const void*>(kernel), kFusedLdsMax - 8 * 1024)) return;
+    hipLaunchKernelGGL(kernel, grid, block, p.lds, st, s);
+    launched = true;
+  };
+  // (only the stage without a channel mix has a form that starts behind its producer's z pass)
+  dispatch_int_else_last<0, 1, 2, 3, 4>(mix_cout, [&](auto co) {
+    dispatch_int_else_last<6, 12>(p.taps, [&](auto taps) {
+      dispatch_int_else_last<0, 4, 1>(p.mode, [&](auto mode) {
+        if constexpr (decltype(co)::value == 0) {
+          if (!p.zin) return launch(co, taps, mode, std::false_type{});
+        }
+        launch(co, taps, mode, std::true_type{});
+      });
+    });
+  });
+  return launched;
 }
 }  // namespace
 
@@ -2198,6 +2142,25 @@ extern "C" int sdfr_decoder_create(const float* h_params, size_t n_params, int l
   // tap tables, biases
   std::vector<float> img;
   auto align = [&]() { while (img.size() % 64) img.push_back(0.0f); };
+  static_assert(sizeof(int) == sizeof(float), "tap tables are stored in the float image");
+  auto push_int = [&](int v) {
+    float f;
+    memcpy(&f, &v, sizeof(f));
+    img.push_back(f);
+  };
+  // a matrix [tile][kpad][16] of value(kk, col), zero where kk >= K or col >= cols
+  auto push_matrix16 = [&](int tiles, int kpad, int K, int cols, auto value) {
+    for (int ct = 0; ct < tiles; ++ct)
+      for (int kk = 0; kk < kpad; ++kk)
+        for (int j = 0; j < 16; ++j) img.push_back((kk < K && ct * 16 + j < cols) ? value(kk, ct * 16 + j) : 0.0f);
+  };
+  // the tap table of such a matrix: row kk's offset into a tensor of n^3 voxels per channel, 0 where kk >= K
+  auto push_taps = [&](int kpad, int K, int k, int kz, int n) {
+    for (int kk = 0; kk < kpad; ++kk) {
+      const Tap t = tap_of(kk, k, kz);
+      push_int(kk < K ? t.ch * n * n * n + (t.a * n + t.b) * n + t.c : 0);
+    }
+  };
   const float* p = h_params;
   width = latent;
   for (int l = 0; l < n_fc; ++l) {
@@ -2218,39 +2181,35 @@ extern "C" int sdfr_decoder_create(const float* h_params, size_t n_params, int l
     d->max_act = std::max(d->max_act, (size_t)wo);
     width = wo;
   }
+  // (p is past the Linear parameters now) every convolution layer's parameters, as its two contractions read them
+  std::vector<ConvWeights> conv_w(n_conv);
+  for (int l = 0; l < n_conv; ++l) {
+    const size_t n_w = (size_t)conv_cout[l] * conv_cin[l] * conv_k[l] * conv_k[l] * conv_k[l];
+    conv_w[l].W = p;
+    conv_w[l].bias = p + n_w;
+    conv_w[l].ci_n = conv_cin[l];
+    conv_w[l].k = conv_k[l];
+    p += n_w + conv_cout[l];
+  }
   for (int l = 0; l < n_conv; ++l) {
     // a swapped 1x1 layer convolves the tensor as it arrives (size conv_prev), before the resize
+    const ConvWeights& w = conv_w[l];
     const int k = conv_k[l], ci_n = conv_cin[l], co_n = conv_cout[l];
     const int n = d->conv_swap[l] ? d->conv_prev[l] : conv_in_size[l];
     const int K = ci_n * k * k * k, kpad = (K + 3) / 4 * 4, co_tiles = (co_n + 15) / 16;
     d->conv_kpad.push_back(kpad);
     align();
     d->conv_w_off.push_back(img.size());
-    for (int ct = 0; ct < co_tiles; ++ct)
-      for (int kk = 0; kk < kpad; ++kk)
-        for (int j = 0; j < 16; ++j) {
-          const int co = ct * 16 + j;
-          img.push_back((kk < K && co < co_n) ? p[(size_t)co * K + kk] : 0.0f);
-        }
-    p += (size_t)co_n * K;
+    push_matrix16(co_tiles, kpad, K, co_n, [&](int kk, int co) {
+      const Tap t = tap_of(kk, k, k);
+      return w.corr(co, t.ch, t.a, t.b, t.c);
+    });
     align();
     d->conv_b_off.push_back(img.size());
-    img.insert(img.end(), p, p + co_n);
-    p += co_n;
+    img.insert(img.end(), w.bias, w.bias + co_n);
     align();
     d->conv_tab_off.push_back(img.size());
-    for (int kk = 0; kk < kpad; ++kk) {
-      int off = 0;
-      if (kk < K) {
-        const int ci = kk / (k * k * k), r = kk % (k * k * k);
-        const int a = r / (k * k), b = (r / k) % k, c = r % k;
-        off = ci * n * n * n + (a * n + b) * n + c;
-      }
-      float f;
-      static_assert(sizeof(int) == sizeof(float), "tap table is stored in the float image");
-      memcpy(&f, &off, sizeof(f));
-      img.push_back(f);
-    }
+    push_taps(kpad, K, k, k, n);
     const int m = conv_in_size[l] - k + 1;
     d->max_act = std::max(d->max_act, (size_t)ci_n * n * n * n);
     d->max_act = std::max(d->max_act, (size_t)co_n * n * n * n);
@@ -2260,9 +2219,6 @@ extern "C" int sdfr_decoder_create(const float* h_params, size_t n_params, int l
   // backward: data-gradient of conv l = valid conv of the zero-padded output gradient with
   //   Wb[kk = co*k^3 + (a*k+b)*k + c][ci] = W[co][ci][k-1-a][k-1-b][k-1-c]
   {
-    const float* q = h_params;
-    int wdt = latent;
-    for (int l = 0; l < n_fc; ++l) { q += (size_t)fc_out[l] * wdt + fc_out[l]; wdt = fc_out[l]; }
     int prev_n = conv_in_size[0];
     d->max_bwd = (size_t)volume * volume * volume;
     size_t tape = 0;
@@ -2281,30 +2237,13 @@ extern "C" int sdfr_decoder_create(const float* h_params, size_t n_params, int l
       d->bwd_kpad.push_back(kpad);
       align();
       d->bwd_w_off.push_back(img.size());
-      for (int ct = 0; ct < ci_tiles; ++ct)
-        for (int kk = 0; kk < kpad; ++kk)
-          for (int j = 0; j < 16; ++j) {
-            const int ci = ct * 16 + j;
-            float v = 0.0f;
-            if (kk < Kb && ci < ci_n) {
-              const int co = kk / k3, r = kk % k3, a = r / (k * k), b = (r / k) % k, c = r % k;
-              v = q[(((size_t)co * ci_n + ci) * k + (k - 1 - a)) * k * k + (size_t)(k - 1 - b) * k + (k - 1 - c)];
-            }
-            img.push_back(v);
-          }
+      push_matrix16(ci_tiles, kpad, Kb, ci_n, [&](int kk, int ci) {
+        const Tap t = tap_of(kk, k, k);   // (t.ch: the channel of the output gradient)
+        return conv_w[l].grad(ci, t.ch, t.a, t.b, t.c);
+      });
       align();
       d->bwd_tab_off.push_back(img.size());
-      for (int kk = 0; kk < kpad; ++kk) {
-        int off = 0;
-        if (kk < Kb) {
-          const int co = kk / k3, r = kk % k3, a = r / (k * k), b = (r / k) % k, c = r % k;
-          off = co * np * np * np + (a * np + b) * np + c;
-        }
-        float f;
-        memcpy(&f, &off, sizeof(f));
-        img.push_back(f);
-      }
-      q += (size_t)co_n * ci_n * k3 + co_n;
+      push_taps(kpad, Kb, k, k, np);
       d->max_bwd = std::max(d->max_bwd, (size_t)co_n * np * np * ((np + 3) & ~3));   // (z pitch padded to 16 bytes)
       d->max_bwd = std::max(d->max_bwd, (size_t)co_n * n * n * n);
       d->max_bwd = std::max(d->max_bwd, (size_t)ci_n * n * n * n);
@@ -2321,37 +2260,29 @@ extern "C" int sdfr_decoder_create(const float* h_params, size_t n_params, int l
     for (int l = 0; l < n_conv; ++l) max_c = std::max(max_c, conv_cin[l]);
     img.insert(img.end(), (size_t)max_c, 0.0f);
   }
+  // the source ranges of the decoder's resizes: in front of a layer, and the final one to the volume
+  for (int l = 0; l <= n_conv; ++l) {
+    const int n_in = l < n_conv ? d->conv_prev[l] : conv_in_size[n_conv - 1] - conv_k[n_conv - 1] + 1;
+    const int n_out = l < n_conv ? conv_in_size[l] : volume;
+    if (n_in != n_out && !find_resize_sources(d, n_in, n_out)) d->rs_src.push_back(host_resize_sources(n_in, n_out));
+  }
   // transposed-resize tables (resize_row16's results, the kernels' float arithmetic): see rs_tab_off
   d->rs_tab_off.assign(n_conv, 0);
   for (int l = 1; l < n_conv; ++l) {
     const int n_in = d->conv_prev[l], n_out = conv_in_size[l];
     if (n_in == n_out || n_in > n_out || n_in > 64) continue;
-    const float ratio = (float)n_in / (float)n_out, inv = (float)n_out / (float)n_in;
-    auto weight = [&](int dd, int i) {
-      float sp = fmaf(ratio, (float)dd + 0.5f, -0.5f);
-      sp = sp < 0.0f ? 0.0f : sp;
-      const int i0 = std::min((int)sp, n_in - 1), i1 = i0 + (i0 < n_in - 1 ? 1 : 0);
-      const float l1 = sp - (float)i0;
-      return (i0 == i ? 1.0f - l1 : 0.0f) + (i1 == i ? l1 : 0.0f);
-    };
-    std::vector<float> tab((size_t)n_in * 16, 0.0f);
-    bool ok = true;
-    for (int i = 0; i < n_in && ok; ++i) {
-      int d0 = std::max((int)floorf(((float)i - 0.5f) * inv - 0.5f) - 1, 0);
-      int d1 = std::min((int)ceilf(((float)i + 1.5f) * inv - 0.5f) + 1, n_out - 1);
-      if (d1 - d0 + 1 > 16) ok = false;
-      while (d0 <= d1 && weight(d0, i) == 0.0f) ++d0;
-      while (d1 >= d0 && weight(d1, i) == 0.0f) --d1;
-      const int nt = d1 - d0 + 1;
-      if (nt < 1 || nt > 12) { ok = false; break; }
-      memcpy(&tab[(size_t)i * 16], &d0, sizeof(int));
-      memcpy(&tab[(size_t)i * 16 + 1], &nt, sizeof(int));
-      for (int kk = 0; kk < nt; ++kk) tab[(size_t)i * 16 + 2 + kk] = weight(d0 + kk, i);
-    }
-    if (!ok) continue;
+    ResizeSources local;
+    const ResizeSources& rs = resize_sources_of(d, n_in, n_out, local);
+    if (rs.empty || rs.max_span > 16 || rs.max_taps > 12) continue;
     align();
     d->rs_tab_off[l] = img.size();
-    img.insert(img.end(), tab.begin(), tab.end());
+    const float ratio = (float)n_in / (float)n_out;
+    for (int i = 0; i < n_in; ++i) {   // a row of 16 words: first source, taps, the weights, zeros
+      const int nt = rs.hi[i] - rs.lo[i] + 1;
+      push_int(rs.lo[i]);
+      push_int(nt);
+      for (int kk = 0; kk < 14; ++kk) img.push_back(kk < nt ? host_resize_weight(rs.lo[i] + kk, i, ratio, n_in) : 0.0f);
+    }
   }
   // z-grouped plans.  wfun(co, ci, a, b, c): weight of input channel ci at tap (a,b,c) for output
   // channel co, in the correlation sense out[x] = sum w(a,b,c) in[x + (a,b,c)].
@@ -2367,47 +2298,26 @@ extern "C" int sdfr_decoder_create(const float* h_params, size_t n_params, int l
     if ((size_t)zp.kpad * 17 * sizeof(float) > 64 * 1024) { zp.zg = 1; return zp; }
     align();
     zp.w_off = img.size();
-    for (int kk = 0; kk < zp.kpad; ++kk)
-      for (int j = 0; j < 16; ++j) {
-        float v = 0.0f;
-        if (kk < K) {
-          const int ci = kk / (k * k * kz), r = kk % (k * k * kz);
-          const int a = r / (k * kz), b = (r / kz) % k, cz = r % kz;
-          const int dz = j / cout, co = j % cout, c = cz - dz;
-          if (dz < zp.zg && c >= 0 && c < k) v = wfun(co, ci, a, b, c);
-        }
-        img.push_back(v);
-      }
+    push_matrix16(1, zp.kpad, K, 16, [&](int kk, int j) {   // column j: output dz of the group, channel co
+      const Tap t = tap_of(kk, k, kz);
+      const int dz = j / cout, co = j % cout, c = t.c - dz;
+      return (dz < zp.zg && c >= 0 && c < k) ? wfun(co, t.ch, t.a, t.b, c) : 0.0f;
+    });
     align();
     zp.tab_off = img.size();
-    for (int kk = 0; kk < zp.kpad; ++kk) {
-      int off = 0;
-      if (kk < K) {
-        const int ci = kk / (k * k * kz), r = kk % (k * k * kz);
-        const int a = r / (k * kz), b = (r / kz) % k, cz = r % kz;
-        off = ci * n * n * n + (a * n + b) * n + cz;
-      }
-      float f;
-      memcpy(&f, &off, sizeof(f));
-      img.push_back(f);
-    }
+    push_taps(zp.kpad, K, k, kz, n);
     return zp;
   };
   {
-    const float* q = h_params;
-    int wdt = latent;
-    for (int l = 0; l < n_fc; ++l) { q += (size_t)fc_out[l] * wdt + fc_out[l]; wdt = fc_out[l]; }
     for (int l = 0; l < n_conv; ++l) {
       const int k = conv_k[l], ci_n = conv_cin[l], co_n = conv_cout[l], n = conv_in_size[l];
-      const int k3 = k * k * k, m = n - k + 1;
-      const float* W = q;  // [co][ci][k][k][k]
-      d->fwd_z.push_back(plan_z(ci_n, co_n, k, n, [&](int co, int ci, int a, int b, int c) {
-        return W[((size_t)co * ci_n + ci) * k3 + (a * k + b) * k + c];
-      }));
-      // data gradient: channels swap roles, taps are flipped, the input is the zero-padded gradient
-      d->bwd_z.push_back(plan_z(co_n, ci_n, k, m + 2 * (k - 1), [&](int co, int ci, int a, int b, int c) {
-        return W[((size_t)ci * ci_n + co) * k3 + ((k - 1 - a) * k + (k - 1 - b)) * k + (k - 1 - c)];
-      }));
+      const int m = n - k + 1;
+      const ConvWeights& w = conv_w[l];
+      const auto corr = [&](int co, int ci, int a, int b, int c) { return w.corr(co, ci, a, b, c); };
+      const auto grad = [&](int co, int ci, int a, int b, int c) { return w.grad(co, ci, a, b, c); };
+      d->fwd_z.push_back(plan_z(ci_n, co_n, k, n, corr));
+      // (data gradient: the input is the zero-padded gradient)
+      d->bwd_z.push_back(plan_z(co_n, ci_n, k, m + 2 * (k - 1), grad));
       // direct-convolution weights [ci][a][b][c][co] (k = 3, 4 / 8 / 16 output channels)
       auto direct = [&](int cin, int cout, auto wfun) -> size_t {
         if (k != 3 || !(cout == 4 || cout == 8 || cout == 16)) return 0;
@@ -2420,13 +2330,8 @@ extern "C" int sdfr_decoder_create(const float* h_params, size_t n_params, int l
                 for (int co = 0; co < cout; ++co) img.push_back(wfun(co, ci, a, b, c));
         return off;
       };
-      d->fwd_direct_off.push_back(direct(ci_n, co_n, [&](int co, int ci, int a, int b, int c) {
-        return W[((size_t)co * ci_n + ci) * k3 + (a * k + b) * k + c];
-      }));
-      d->bwd_direct_off.push_back(direct(co_n, ci_n, [&](int co, int ci, int a, int b, int c) {
-        return W[((size_t)ci * ci_n + co) * k3 + ((k - 1 - a) * k + (k - 1 - b)) * k + (k - 1 - c)];
-      }));
-      q += (size_t)co_n * ci_n * k3 + co_n;
+      d->fwd_direct_off.push_back(direct(ci_n, co_n, corr));
+      d->bwd_direct_off.push_back(direct(co_n, ci_n, grad));
     }
   }
   hipError_t e = hipSetDevice(device);
@@ -2482,13 +2387,7 @@ int decoder_forward_impl(const sdfr_decoder* d, const float* z, int N, int enfor
   int cur = 0;
 
   FcDesc fd;
-  fd.n_fc = d->n_fc;
-  fd.width[0] = d->latent;
-  for (int l = 0; l < d->n_fc; ++l) {
-    fd.width[l + 1] = d->fc_out[l];
-    fd.w_off[l] = (long long)d->fc_w_off[l];
-    fd.b_off[l] = (long long)d->fc_b_off[l];
-  }
+  decoder_fc_desc(d, &fd, nullptr, nullptr);
   const int last = d->fc_out[d->n_fc - 1];
   // with a tape, every ReLU'd layer output goes to its own slot (and is read from there)
   const float* act_in;
@@ -2543,21 +2442,8 @@ int decoder_forward_impl(const sdfr_decoder* d, const float* z, int N, int enfor
   if (l_first == 1) { c = d->conv_cout[0]; n = d->conv_in_size[0] - d->conv_k[0] + 1; }
   const size_t vox = (size_t)d->volume * d->volume * d->volume;
   auto resize = [&](const float* src, int C, int ni, int no, int relu, float clamp, float* dst) {
-    // input columns under an 8 x 8 output patch, worst tile (same float arithmetic as the kernel)
-    int max_r = 0;
-    const float ratio = (float)ni / (float)no;
-    auto first_last = [&](int dd, int& i0, int& i1) {
-      float sp = fmaf(ratio, (float)dd + 0.5f, -0.5f);
-      sp = sp < 0.0f ? 0.0f : sp;
-      i0 = std::min((int)sp, ni - 1);
-      i1 = i0 + (i0 < ni - 1 ? 1 : 0);
-    };
-    for (int t0 = 0; t0 < no; t0 += kResizeTile) {
-      int lo, hi, tmp;
-      first_last(t0, lo, tmp);
-      first_last(std::min(t0 + kResizeTile, no) - 1, tmp, hi);
-      max_r = std::max(max_r, hi - lo + 1);
-    }
+    // input columns under an 8 x 8 output patch, worst tile
+    const int max_r = host_resize_span(ni, no, no, kResizeTile, kResizeTile);
     const size_t lds = ((size_t)max_r * max_r * (ni + no) + 3) * sizeof(float);   // (+3: the second array starts 16-byte aligned)
     const int tiles = (no + kResizeTile - 1) / kResizeTile;
     const bool pow2 = no >= 16 && no <= 128 && (no & (no - 1)) == 0;
@@ -2571,20 +2457,41 @@ int decoder_forward_impl(const sdfr_decoder* d, const float* z, int N, int enfor
       const int ipw = std::max((int)std::max<long long>(1, std::min<long long>(4, tile_items / 2048)), (items + 65534) / 65535);
       const dim3 grid(tiles * tiles, (items + ipw - 1) / ipw, 1);
       const bool vec = ((uintptr_t)dst & 15) == 0;
-#define SDFR_RESIZE_T(LOG)                                                                                              \
-  do {                                                                                                                  \
-    if (vec) hipLaunchKernelGGL((resize3_tiled_kernel<LOG, true>), grid, dim3(256), lds, st, src, items, ipw, ni, relu, \
-                                clamp, max_r * max_r, dst);                                                             \
-    else hipLaunchKernelGGL((resize3_tiled_kernel<LOG, false>), grid, dim3(256), lds, st, src, items, ipw, ni, relu,    \
-                            clamp, max_r * max_r, dst);                                                                 \
-  } while (0)
-      if (no == 16) SDFR_RESIZE_T(4); else if (no == 32) SDFR_RESIZE_T(5); else if (no == 64) SDFR_RESIZE_T(6); else SDFR_RESIZE_T(7);
-#undef SDFR_RESIZE_T
+      int log_no = 4;   // (pow2: no is 16, 32, 64 or 128)
+      while ((1 << log_no) < no) ++log_no;
+      dispatch_int_else_last<4, 5, 6, 7>(log_no, [&](auto log) {
+        constexpr int LOG = decltype(log)::value;
+        if (vec) hipLaunchKernelGGL((resize3_tiled_kernel<LOG, true>), grid, dim3(256), lds, st, src, items, ipw, ni, relu,
+                                    clamp, max_r * max_r, dst);
+        else hipLaunchKernelGGL((resize3_tiled_kernel<LOG, false>), grid, dim3(256), lds, st, src, items, ipw, ni, relu,
+                                clamp, max_r * max_r, dst);
+      });
       return;
     }
     const size_t cnt = (size_t)C * no * no * no;
     hipLaunchKernelGGL(resize3_kernel, dim3((unsigned)((cnt + 255) / 256), N), dim3(256), 0, st, src, C,
                        ni, no, relu, clamp, dst);
+  };
+  // where layer l's output goes: straight to `out` (a last layer of the volume's size with no clamp left to apply),
+  // to its tape slot, or (nullptr) to the other buffer
+  // (a ReLU'd last layer of a taped forward goes to its tape slot first -- the VJP reads its mask there -- and is
+  // copied out: until round 6 it went straight to `out` and the VJP masked with whatever the slot held)
+  auto layer_dst_of = [&](int l, bool no_clamp, bool& to_out) -> float* {
+    const int m_out = d->conv_in_size[l] - d->conv_k[l] + 1;
+    to_out = l == d->n_conv - 1 && m_out == d->volume && no_clamp && !(tape && d->conv_relu[l]);
+    return to_out ? out : (tape ? tape + (size_t)N * d->tape_conv_off[l] : nullptr);
+  };
+  // behind the last layer: what is not in `out` yet gets there, resized to the volume or copied, and clamped
+  auto finish = [&](const float* act, int n_act) {
+    if (act == out) return;
+    if (n_act != d->volume) {
+      resize(act, 1, n_act, d->volume, 0, clampv, out);
+    } else {
+      copy_words_async(out, act, (size_t)N * vox, st);
+      if (clampv > 0.0f)
+        hipLaunchKernelGGL(clamp_kernel, dim3((unsigned)(((size_t)N * vox + 255) / 256)), dim3(256), 0, st, out,
+                           (size_t)N * vox, clampv);
+    }
   };
   bool premixed = false;   // the previous layer's epilogue has applied this (1x1x1) layer already: act_in is its output
   for (int l = l_first; l < d->n_conv; ++l) {
@@ -2593,21 +2500,17 @@ int decoder_forward_impl(const sdfr_decoder* d, const float* z, int N, int enfor
     // (batches: an up-sampling resize in front of a 3x3x3 layer is folded into that layer's patch load --
     // conv3d_direct_up_kernel -- and the up-sampled tensor is never written)
     bool fused_up = false, fused_mixed = false;
+    const int nf = d->conv_in_size[l], mf = nf - k + 1;   // the sizes a fused resize + convolution works at
+    bool to_out_f;
+    float* ldst = layer_dst_of(l, clampv == 0.0f, to_out_f);
+    float* cdst = ldst ? ldst : buf[cur ^ 1];
     if (!swap && n != d->conv_in_size[l] && k == 3 && d->fwd_direct_off[l] != 0) {
-      const int nf = d->conv_in_size[l], mf = nf - k + 1;
-      const bool to_out_f = is_last && mf == d->volume && clampv == 0.0f && !(tape && d->conv_relu[l]);
-      float* ldst = to_out_f ? out : (tape ? tape + (size_t)N * d->tape_conv_off[l] : nullptr);
-      float* cdst = ldst ? ldst : buf[cur ^ 1];
       fused_up = launch_direct_up(d, d->fwd_direct_off[l], act_in, n, d->d_params + d->conv_b_off[l], cdst, c, co_n,
                                   nf, mf, d->conv_relu[l], N, st);
       if (fused_up) n = nf;   // (act_in stays the coarse tensor: the launch has consumed it)
     }
     // few latents: the resize inside the split-K MFMA convolution's operand fetch (conv3d_mfma_up_kernel)
     if (!fused_up && !swap && n != d->conv_in_size[l] && k == 3) {
-      const int nf = d->conv_in_size[l], mf = nf - k + 1;
-      const bool to_out_f = is_last && mf == d->volume && clampv == 0.0f && !(tape && d->conv_relu[l]);
-      float* ldst = to_out_f ? out : (tape ? tape + (size_t)N * d->tape_conv_off[l] : nullptr);
-      float* cdst = ldst ? ldst : buf[cur ^ 1];
       // ... and where a swapped 1x1x1 layer follows (the mug decoder's last: 4 -> 1 channels behind the resize to the
       // volume), its channel mix in this launch's epilogue: the resize behind it gathers one channel, not four
       // (resize3_kernel instead of resize3_mix_kernel: bit for bit the same corner values)
@@ -2632,11 +2535,9 @@ int decoder_forward_impl(const sdfr_decoder* d, const float* z, int N, int enfor
     }
     const int m = n - k + 1;                     // swapped: k == 1, the conv keeps the incoming size
     const int m_out = d->conv_in_size[l] - k + 1;  // size of the layer's output tensor
-    // where the layer's output goes: straight to `out`, to its tape slot, or to the other buffer
-    // (a ReLU'd last layer of a taped forward goes to its tape slot first -- the VJP reads its mask there -- and is
-    // copied out: until round 6 it went straight to `out` and the VJP masked with whatever the slot held)
-    const bool to_out = is_last && m_out == d->volume && (swap || clampv == 0.0f) && !(tape && d->conv_relu[l]);
-    float* layer_dst = to_out ? out : (tape ? tape + (size_t)N * d->tape_conv_off[l] : nullptr);
+    // (a swapped layer's resize applies the clamp itself)
+    bool to_out;
+    float* layer_dst = layer_dst_of(l, swap || clampv == 0.0f, to_out);
     float* conv_dst = (!swap && layer_dst) ? layer_dst : buf[cur ^ 1];
     const int conv_relu = swap ? 0 : d->conv_relu[l];
     const float* wm = d->d_params + d->conv_w_off[l];
@@ -2648,23 +2549,15 @@ int decoder_forward_impl(const sdfr_decoder* d, const float* z, int N, int enfor
       const size_t vo = (size_t)m_out * m_out * m_out;
       const dim3 gm((unsigned)((vo + 255) / 256), N);
       const float clampm = to_out ? clampv : 0.0f;
-#define SDFR_MIXF(CO) hipLaunchKernelGGL((resize3_mix_kernel<CO>), gm, dim3(256), 0, st, act_in, wm, bs, c, n, m_out, d->conv_relu[l], clampm, dst)
-      if (co_n == 1) SDFR_MIXF(1); else if (co_n == 2) SDFR_MIXF(2); else if (co_n == 3) SDFR_MIXF(3); else SDFR_MIXF(4);
-#undef SDFR_MIXF
+      dispatch_int_else_last<1, 2, 3, 4>(co_n, [&](auto co) {
+        hipLaunchKernelGGL((resize3_mix_kernel<decltype(co)::value>), gm, dim3(256), 0, st, act_in, wm, bs, c, n, m_out,
+                           d->conv_relu[l], clampm, dst);
+      });
       if (dst == buf[cur ^ 1]) cur ^= 1;
       act_in = dst;
       c = co_n;
       n = m_out;
-      if (is_last && act_in != out) {
-        if (n != d->volume) {
-          resize(act_in, 1, n, d->volume, 0, clampv, out);
-        } else {
-          copy_words_async(out, act_in, (size_t)N * vox, st);
-          if (clampv > 0.0f)
-            hipLaunchKernelGGL(clamp_kernel, dim3((unsigned)(((size_t)N * vox + 255) / 256)), dim3(256), 0,
-                               st, out, (size_t)N * vox, clampv);
-        }
-      }
+      if (is_last) finish(act_in, n);
       continue;
     }
     // batches: a swapped 1x1x1 layer behind this one is applied in this layer's epilogue (conv3d_direct_kernel)
@@ -2695,12 +2588,11 @@ int decoder_forward_impl(const sdfr_decoder* d, const float* z, int N, int enfor
       const dim3 g1((voxn + 255) / 256, N);
       const bool v4 = N >= 32 && (voxn & 3) == 0 && (((uintptr_t)act_in | (uintptr_t)conv_dst) & 15) == 0;
       const dim3 g4((voxn / 4 + 255) / 256, N);
-#define SDFR_CONV1(CO)                                                                                                \
-  if (v4) hipLaunchKernelGGL((conv1x1_vec4_kernel<CO>), g4, dim3(256), 0, st, act_in, wm, bs, c, voxn, conv_relu,    \
-                             conv_dst);                                                                              \
-  else hipLaunchKernelGGL((conv1x1_kernel<CO>), g1, dim3(256), 0, st, act_in, wm, bs, c, voxn, conv_relu, conv_dst)
-      if (co_n == 1) { SDFR_CONV1(1); } else if (co_n == 2) { SDFR_CONV1(2); } else if (co_n == 3) { SDFR_CONV1(3); } else { SDFR_CONV1(4); }
-#undef SDFR_CONV1
+      dispatch_int_else_last<1, 2, 3, 4>(co_n, [&](auto co) {
+        constexpr int CO = decltype(co)::value;
+        if (v4) hipLaunchKernelGGL((conv1x1_vec4_kernel<CO>), g4, dim3(256), 0, st, act_in, wm, bs, c, voxn, conv_relu, conv_dst);
+        else hipLaunchKernelGGL((conv1x1_kernel<CO>), g1, dim3(256), 0, st, act_in, wm, bs, c, voxn, conv_relu, conv_dst);
+      });
     } else if (!swap && launch_direct(d, d->fwd_direct_off[l], act_in, bs, conv_dst, c, co_n, n, n, m, conv_relu, N, st)) {
       // (batched: direct VALU convolution)
     } else {
@@ -2726,16 +2618,7 @@ int decoder_forward_impl(const sdfr_decoder* d, const float* z, int N, int enfor
       act_in = dst;
       n = m_out;
     }
-    if (is_last && act_in != out) {
-      if (n != d->volume) {
-        resize(act_in, 1, n, d->volume, 0, clampv, out);
-      } else {
-        copy_words_async(out, act_in, (size_t)N * vox, st);
-        if (clampv > 0.0f)
-          hipLaunchKernelGGL(clamp_kernel, dim3((unsigned)(((size_t)N * vox + 255) / 256)), dim3(256), 0,
-                             st, out, (size_t)N * vox, clampv);
-      }
-    }
+    if (is_last) finish(act_in, n);
   }
   SDFR_HIP_TRY(hipGetLastError());
   return 0;
@@ -2821,57 +2704,29 @@ int decoder_backward_impl(const sdfr_decoder* d, const float* z, const float* ta
                              const float* mix_w = nullptr, int mix_cout = 0, int pz = 0) {
     if (pz == 0) pz = n_in + 2 * std::max(pad, 0);
     const size_t nc = (size_t)N * C;
-    bool few = nc * n_out * n_out * n_out <= kFewElements;
-    if (few) {  // longest source range, same arithmetic as resize_sources
-      const float inv = (float)n_out / (float)n_in;
-      for (int i = 0; i < n_in && few; ++i) {
-        const int d0 = std::max((int)floorf(((float)i - 0.5f) * inv - 0.5f) - 1, 0);
-        const int d1 = std::min((int)ceilf(((float)i + 1.5f) * inv - 0.5f) + 1, n_out - 1);
-        few = d1 - d0 + 1 <= kZyTaps;
-      }
-    }
+    ResizeSources local;
+    const ResizeSources& rs = resize_sources_of(d, n_in, n_out, local);
+    // (the z + y launch takes candidate ranges, as resize_sources gives them, up to kZyTaps long)
+    const bool few = nc * n_out * n_out * n_out <= kFewElements && rs.max_span <= kZyTaps;
     // (n_in <= n_out: the z pass writes a row's n_in results over the row's own n_out sources)
     // (single latents too: one launch of ~9 us instead of two of 6 + 5 in the captured loop, C5 0.144 -> 0.1375 ms)
     if (d->opt_tiled_vjp.load(std::memory_order_relaxed) && (!mix_w || (C == 1 && pad >= 0)) && n_in <= 64 &&
         n_in <= n_out && n_out <= 1024 && nc < (1u << 24)) {
       // the three passes in one launch on an LDS-staged block (resize3_backward_tiled_kernel)
-      const float ratio = (float)n_in / (float)n_out;
-      auto weight = [&](int dd, int i) {   // resize_weight on the host, same float arithmetic
-        float sp = fmaf(ratio, (float)dd + 0.5f, -0.5f);
-        sp = sp < 0.0f ? 0.0f : sp;
-        const int i0 = std::min((int)sp, n_in - 1), i1 = i0 + (i0 < n_in - 1 ? 1 : 0);
-        const float l1 = sp - (float)i0;
-        return (i0 == i ? 1.0f - l1 : 0.0f) + (i1 == i ? l1 : 0.0f);
-      };
-      const float inv = (float)n_out / (float)n_in;
-      auto exact = [&](int i, int& d0, int& d1) {
-        d0 = std::max((int)floorf(((float)i - 0.5f) * inv - 0.5f) - 1, 0);
-        d1 = std::min((int)ceilf(((float)i + 1.5f) * inv - 0.5f) + 1, n_out - 1);
-        while (d0 <= d1 && weight(d0, i) == 0.0f) ++d0;
-        while (d1 >= d0 && weight(d1, i) == 0.0f) --d1;
-      };
       const int padv = pad >= 0 ? pad : 0;
-      int max_taps = 1, max_span = 1;   // longest exact source range; longest candidate range (resize_row16: <= 16)
-      for (int i = 0; i < n_in; ++i) {
-        int d0, d1;
-        exact(i, d0, d1);
-        max_taps = std::max(max_taps, d1 - d0 + 1);
-        const int s0 = std::max((int)floorf(((float)i - 0.5f) * inv - 0.5f) - 1, 0);
-        const int s1 = std::min((int)ceilf(((float)i + 1.5f) * inv - 0.5f) + 1, n_out - 1);
-        max_span = std::max(max_span, s1 - s0 + 1);
-      }
+      const int max_taps = rs.max_taps;   // longest exact source range (the candidate ranges: resize_row16 takes <= 16)
       // tile edge and workgroup size: the pair that stages the fewest fine rows over the launch, among those whose
       // block fits the registers of the prefetch (kBtLoads vectors per thread) and leaves two workgroups on a CU
       struct Pick { int tc = 0, threads = 0, max_f = 0, wgs = 0; size_t lds = 0; double cost = 0; } best;
-      const bool aligned = (n_out & 3) == 0 && ((uintptr_t)g & 15) == 0 && max_taps <= kBtTaps && max_span <= 16;
-      const void* fn = nullptr;   // the instantiation this call takes
-      {
-#define SDFR_BT_FN(CO) (max_taps <= 6 ? reinterpret_cast<const void*>(&resize3_backward_tiled_kernel<CO, 6>)    \
-                        : max_taps <= 8 ? reinterpret_cast<const void*>(&resize3_backward_tiled_kernel<CO, 8>)  \
-                                        : reinterpret_cast<const void*>(&resize3_backward_tiled_kernel<CO, 12>))
-        fn = !mix_w ? SDFR_BT_FN(0) : mix_cout == 1 ? SDFR_BT_FN(1) : mix_cout == 2 ? SDFR_BT_FN(2) : mix_cout == 3 ? SDFR_BT_FN(3) : SDFR_BT_FN(4);
-#undef SDFR_BT_FN
-      }
+      const bool aligned = (n_out & 3) == 0 && ((uintptr_t)g & 15) == 0 && max_taps <= kBtTaps && rs.max_span <= 16;
+      // the instantiation this call takes: the channels of the 1x1 layer (0: none), the taps that hold the longest range
+      decltype(&resize3_backward_tiled_kernel<0, 6>) kernel = nullptr;
+      dispatch_int_else_last<0, 1, 2, 3, 4>(!mix_w ? 0 : (mix_cout >= 1 && mix_cout <= 3) ? mix_cout : 4, [&](auto co) {
+        dispatch_int_else_last<6, 8, 12>(max_taps <= 6 ? 6 : max_taps <= 8 ? 8 : 12, [&](auto taps) {
+          kernel = &resize3_backward_tiled_kernel<decltype(co)::value, decltype(taps)::value>;
+        });
+      });
+      const void* fn = reinterpret_cast<const void*>(kernel);
       static std::map<const void*, int> vgpr_waves;   // waves per SIMD the instantiation's registers allow
       static std::mutex vgpr_mutex;
       int waves_simd = 0;
@@ -2879,11 +2734,10 @@ int decoder_backward_impl(const sdfr_decoder* d, const float* z, const float* ta
         std::lock_guard<std::mutex> lock(vgpr_mutex);
         auto it = vgpr_waves.find(fn);
         if (it == vgpr_waves.end()) {
-          // (a block above 64 KiB of dynamic LDS needs the kernel's limit raised: once per instantiation)
+          // (a block above 64 KiB of dynamic LDS needs the kernel's limit raised)
           hipFuncAttributes fa;
           int waves = 0;   // (0: the runtime refused; the three-launch form below is taken)
-          if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) == hipSuccess &&
-              hipFuncGetAttributes(&fa, fn) == hipSuccess)
+          if (raise_lds_limit(fn, 150 * 1024) && hipFuncGetAttributes(&fa, fn) == hipSuccess)
             waves = std::max(1, std::min(8, 512 / ((std::max(fa.numRegs, 1) + 7) / 8 * 8)));
           it = vgpr_waves.emplace(fn, waves).first;
         }
@@ -2892,12 +2746,7 @@ int decoder_backward_impl(const sdfr_decoder* d, const float* z, const float* ta
       for (int tc = 2; aligned && tc <= std::min(kBtMaxTile, n_in); ++tc) {
         if (SDFR_BT_TILE > 0 && tc != std::min(SDFR_BT_TILE, n_in)) continue;
         int max_f = 1;
-        for (int c0 = 0; c0 < n_in; c0 += tc) {
-          int a0, a1, t;
-          exact(c0, a0, t);
-          exact(std::min(c0 + tc, n_in) - 1, t, a1);
-          max_f = std::max(max_f, a1 - a0 + 1);
-        }
+        for (int c0 = 0; c0 < n_in; c0 += tc) max_f = std::max(max_f, rs.hi[std::min(c0 + tc, n_in) - 1] - rs.lo[c0] + 1);
         const int tiles = (n_in + tc - 1) / tc;
         const size_t lds = ((size_t)max_f * max_f * n_out + (size_t)max_f * tc * n_in) * sizeof(float);
         if (lds > 150 * 1024) continue;
@@ -2930,18 +2779,8 @@ int decoder_backward_impl(const sdfr_decoder* d, const float* z, const float* ta
         }
         const float* wm = mix_w ? mix_w : nullptr;
         const float* zb = d->d_params + d->zero_bias_off;
-#define SDFR_BT(CO, TAPS)                                                                                             \
-  hipLaunchKernelGGL((resize3_backward_tiled_kernel<CO, TAPS>), dim3((unsigned)(tt * slots)), dim3(best.threads),     \
-                     best.lds, st, g, n_in, n_out, pad >= 0 ? act : nullptr, padv, pz, best.tc, best.max_f, (int)nc,  \
-                     slots, wm, zb, buf[cur]);
-#define SDFR_BT_TAPS(CO) { if (max_taps <= 6) SDFR_BT(CO, 6) else if (max_taps <= 8) SDFR_BT(CO, 8) else SDFR_BT(CO, 12) }
-        if (!mix_w) SDFR_BT_TAPS(0)
-        else if (mix_cout == 1) SDFR_BT_TAPS(1)
-        else if (mix_cout == 2) SDFR_BT_TAPS(2)
-        else if (mix_cout == 3) SDFR_BT_TAPS(3)
-        else SDFR_BT_TAPS(4)
-#undef SDFR_BT_TAPS
-#undef SDFR_BT
+        hipLaunchKernelGGL(kernel, dim3((unsigned)(tt * slots)), dim3(best.threads), best.lds, st, g, n_in, n_out,
+                           pad >= 0 ? act : nullptr, padv, pz, best.tc, best.max_f, (int)nc, slots, wm, zb, buf[cur]);
         g = buf[cur];
         cur ^= 1;
         return;
@@ -2961,9 +2800,10 @@ int decoder_backward_impl(const sdfr_decoder* d, const float* z, const float* ta
         const size_t np = (size_t)n_in + 2 * pad;
         const dim3 gm((unsigned)((np * np * pz + 255) / 256), N);
         const float* zb = d->d_params + d->zero_bias_off;
-#define SDFR_MIX(CO) hipLaunchKernelGGL((resize_x_backward_mix_pad_kernel<CO>), gm, dim3(256), 0, st, g, C, n_in, n_out, mix_w, zb, act, pad, pz, buf[cur])
-        if (mix_cout == 1) SDFR_MIX(1); else if (mix_cout == 2) SDFR_MIX(2); else if (mix_cout == 3) SDFR_MIX(3); else SDFR_MIX(4);
-#undef SDFR_MIX
+        dispatch_int_else_last<1, 2, 3, 4>(mix_cout, [&](auto co) {
+          hipLaunchKernelGGL((resize_x_backward_mix_pad_kernel<decltype(co)::value>), gm, dim3(256), 0, st, g, C, n_in,
+                             n_out, mix_w, zb, act, pad, pz, buf[cur]);
+        });
       } else if (a == 2 && pad >= 0) {
         const size_t np = (size_t)n_in + 2 * pad, cnt = nc * np * np * pz;
         hipLaunchKernelGGL(resize_x_backward_pad_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, g, nc,
@@ -3087,9 +2927,10 @@ int decoder_backward_impl(const sdfr_decoder* d, const float* z, const float* ta
       const dim3 g1((voxn + 255) / 256, N);
       const float* wb = d->d_params + d->bwd_w_off[l];
       const float* zb = d->d_params + d->zero_bias_off;
-#define SDFR_CONV1(CO) hipLaunchKernelGGL((conv1x1_kernel<CO>), g1, dim3(256), 0, st, g, wb, zb, co_n, voxn, 0, buf[cur])
-      if (ci_n == 1) SDFR_CONV1(1); else if (ci_n == 2) SDFR_CONV1(2); else if (ci_n == 3) SDFR_CONV1(3); else SDFR_CONV1(4);
-#undef SDFR_CONV1
+      dispatch_int_else_last<1, 2, 3, 4>(ci_n, [&](auto ci) {
+        hipLaunchKernelGGL((conv1x1_kernel<decltype(ci)::value>), g1, dim3(256), 0, st, g, wb, zb, co_n, voxn, 0,
+                           buf[cur]);
+      });
     } else if (!swap && launch_direct(d, d->bwd_direct_off[l], g, d->d_params + d->zero_bias_off, buf[cur], co_n, ci_n, np,
                                pz, nconv, 0, N, st)) {
       // (batched: direct VALU convolution)
@@ -3136,13 +2977,7 @@ int decoder_backward_impl(const sdfr_decoder* d, const float* z, const float* ta
   }
   // g is now the gradient w.r.t. the (ReLU'd) output of the Linear stack
   FcDesc fd;
-  fd.n_fc = d->n_fc;
-  fd.width[0] = d->latent;
-  for (int l = 0; l < d->n_fc; ++l) {
-    fd.width[l + 1] = d->fc_out[l];
-    fd.w_off[l] = (long long)d->fc_w_off[l];
-    fd.b_off[l] = (long long)d->fc_b_off[l];
-  }
+  decoder_fc_desc(d, &fd, nullptr, nullptr);
   // g == buf[cur ^ 1] here (every step above ends with g = buf[cur]; cur ^= 1): the transposed wide layer
   // must write the FREE buffer -- other workgroups still read g while this one stores.
   float* t_mid = buf[cur];

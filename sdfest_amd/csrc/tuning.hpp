@@ -119,6 +119,11 @@
 #ifndef SDFR_SPLITK_MAX_LATENTS
 #define SDFR_SPLITK_MAX_LATENTS 16
 #endif
+// ... and for launches of at most this many (voxel tile, channel tile) pairs: so few that a wave's K loop is the
+// critical path
+#ifndef SDFR_SPLITK_MAX_TILES
+#define SDFR_SPLITK_MAX_TILES 2048
+#endif
 // waves per SIMD the backward kernel's register allocation is held to (0: the compiler's choice)
 #ifndef SDFR_BWD_WAVES_PER_EU
 #define SDFR_BWD_WAVES_PER_EU 8
