@@ -1095,6 +1095,58 @@ SDFR_API int sdfr_vae_trainer_backward(const sdfr_vae_trainer* trainer, const fl
 SDFR_API int sdfr_adam_flat(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int* step, size_t n,
                             double lr, int device, void* stream);
 
+/* ==== 11. INITIALISATION NETWORK TRAINING ===================================================== */
+/* ---- one iteration of the reference's trainer of the single-shot network (sdfest/initialization/scripts/train.py
+ * :130-150, _compute_loss :211-287): VanillaPointNet + SDFPoseHead under train(), the loss, every parameter's gradient.
+ * The update is sdfr_adam_flat above. -----------------------------------------------------------------------------------
+ * A trainer handle describes the network only (group 4 runs the same network in inference mode): in_size, the backbone's
+ * widths and its batchnorm / dense / residual flags, the head's widths and its batchnorm, the latent size, and n_cells
+ * orientation classes (discretized) or 0 (quaternion).  The head's output row has L + 4 + n_cells or L + 8 floats:
+ * latent [L], position [3], scale [1], logits [n_cells] or the quaternion BEFORE its normalisation [4].  The handle holds
+ * no parameters and no device memory; creation makes no HIP call.  Not implemented (SDFR_E_INVALID): a residual link
+ * that adds per-point inputs to a dense link's broadcast columns (in_size = 2 x the first width, dense and residual).
+ * PARAMETERS: one flat fp32 device buffer of sdfr_pose_trainer_param_count floats that the caller owns, in the
+ * reference's parameters() order and torch's layouts: _backbone._linear_layers.i.{weight, bias} for every i, then
+ * _backbone._bn_layers.i.{weight, bias}, _head._linear_layers.i.{weight, bias}, _head._bn_layers.i.{weight, bias},
+ * _head._final_layer.{weight, bias}.  The gradient has the same length and layout.
+ * STATISTICS: a second flat buffer of sdfr_pose_trainer_stat_count floats, {running_mean [c], running_var [c]} per
+ * BatchNorm in the same order (backbone, then head); may be NULL when update_stats == 0.
+ *   forward   points [N][M][in_size] -> out [N][row], and in `tape` what the backward reads (every per-point layer's
+ *             linear output and activation, the batch statistics, the set maxima and their rows).  BatchNorm
+ *             normalises with the batch's mean and BIASED variance (eps 1e-5) over all N M rows (backbone) or N rows
+ *             (head); update_stats != 0: running <- 0.9 running + 0.1 {mean, UNBIASED variance}.
+ *   loss      terms [5] = {latent, position, scale, orientation, total}: mse (mean over all elements) of the three,
+ *             cross_entropy (mean over N) of the logits against orientation_index [N], or mean(1 - (q / |q| . t)^2)
+ *             against orientation_quat [N][4]; total = the weighted sum.  g_out [N][row] = d total / d out.
+ *   backward  the gradient of `total` w.r.t. every parameter into grads (every element is written).  The gradient of a
+ *             set maximum goes to the FIRST row that attains it.  Takes the points and tape of the forward.
+ * Every output element has one owner and a fixed summation order, no atomics: the same inputs give the same bits on
+ * every run.  Sums over the N M rows are two-stage: an fp64 record per (sample, column) or per block of rows, then
+ * the records in order; the batch variance is a centred second pass.  No allocation, no host synchronisation; kernels
+ * only, on the caller's stream.  1 <= N <= 65535, N M <= 2^30; N >= 2 with a head BatchNorm.  The workspace must be
+ * 8-byte aligned and is shared by the three calls (the loss accepts one sized for any M). */
+typedef struct sdfr_pose_trainer sdfr_pose_trainer;
+SDFR_API int sdfr_pose_trainer_create(int in_size, int n_backbone, const int* backbone_out, int batchnorm, int dense,
+                                      int residual, int n_head, const int* head_out, int head_batchnorm, int latent,
+                                      int n_cells, int device, sdfr_pose_trainer** out_handle);
+SDFR_API void sdfr_pose_trainer_destroy(sdfr_pose_trainer* trainer);
+SDFR_API size_t sdfr_pose_trainer_param_count(const sdfr_pose_trainer* trainer);   /* 0: NULL */
+SDFR_API size_t sdfr_pose_trainer_stat_count(const sdfr_pose_trainer* trainer);
+SDFR_API int sdfr_pose_trainer_output_size(const sdfr_pose_trainer* trainer);      /* floats of an output row */
+SDFR_API size_t sdfr_pose_trainer_tape_bytes(const sdfr_pose_trainer* trainer, int N, int M);        /* 0: invalid */
+SDFR_API size_t sdfr_pose_trainer_workspace_bytes(const sdfr_pose_trainer* trainer, int N, int M);   /* 0: invalid */
+SDFR_API int sdfr_pose_trainer_forward(const sdfr_pose_trainer* trainer, const float* params, float* stats,
+                                       const float* points, int N, int M, int update_stats, float* out, float* tape,
+                                       size_t tape_bytes, void* workspace, size_t workspace_bytes, void* stream);
+SDFR_API int sdfr_pose_trainer_loss(const sdfr_pose_trainer* trainer, const float* out, const float* latent,
+                                    const float* position, const float* scale, const int* orientation_index,
+                                    const float* orientation_quat, int N, float w_latent, float w_position,
+                                    float w_scale, float w_orientation, float* terms, float* g_out, void* workspace,
+                                    size_t workspace_bytes, void* stream);
+SDFR_API int sdfr_pose_trainer_backward(const sdfr_pose_trainer* trainer, const float* params, const float* points, int N,
+                                        int M, const float* tape, const float* g_out, float* grads, void* workspace,
+                                        size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
