@@ -1088,6 +1088,49 @@ SDFR_API int sdfr_vae_trainer_backward(const sdfr_vae_trainer* trainer, const fl
                                        const float* tape, const float* recon, const float* g_recon,
                                        const float* g_means, const float* g_log_var, float* grads, void* workspace,
                                        size_t workspace_bytes, void* stream);
+/* ---- the point cloud term of the same iteration: pc_weight * loss_pc (train.py:230-269, :278) -------------------------
+ * Per sample b the reference renders the TARGET volume x_b at a random orientation (position (0, 0, -5), scale 1,
+ * threshold 0.01: sdfr_render_forward with sdf_view_stride = D^3 does that for all N at once), lifts the non-zero depth
+ * pixels to points (depth_to_pointcloud, pointset_utils.py:57-77, OpenGL frame) and adds
+ *     loss_pc += sum over the points of v^2,
+ * v = train.py's own pc_loss (:30-125; losses.pc_loss without its final * scale) of the RECONSTRUCTION the other terms
+ * see: the trilinear value at o = R(q / |q|)^T (P - position) / scale, 0 where the point's base cell
+ * floor((o + 1) (D - 1) / 2) lies outside [0, D - 2]^3.
+ * sdfr_vae_trainer_pc_term goes between sdfr_vae_trainer_loss and sdfr_vae_trainer_backward, in ONE pass over the
+ * depth pixels (lift -> object frame -> cell -> the eight corners -> v; no point buffer, nothing per point in memory):
+ *   depth [N][H][W]   any depth images (a pixel != 0 is a point); cx, cy, fx, fy as sdfr_render_forward takes them
+ *                     (pixel-centre-0.5 intrinsics; the lift uses cx - 0.5, cy - 0.5 with integer pixel indices)
+ *   pos [N][3], quat [N][4] (x, y, z, w; normalised here), scale [N]   device, the pose the points are sampled at
+ *   recon, x [N][D^3], post   the forward's raw output and its (clamped) input: post != 0 and tsdf > 0 make a corner read
+ *                     clamp(recon, +-tsdf) where |x| >= tsdf and |recon| >= tsdf, exactly as sdfr_vae_trainer_loss does,
+ *                     and a corner the clamp cuts (recon < -tsdf or recon > tsdf) receives gradient 0
+ *   loss_pc [1]       device: the UNWEIGHTED sum, overwritten
+ *   terms             the terms [6] of sdfr_vae_trainer_loss: terms[5] (total) += pc_weight * loss_pc
+ *   g_recon [N][D^3]  += 2 pc_weight v (trilinear weight) per corner: ADDED to what sdfr_vae_trainer_loss wrote.  A voxel
+ *                     no point touches keeps its bits (an all-zero depth image leaves g_recon untouched, loss_pc = 0).
+ * The scatter is deterministic the way SDFR_SDF_GRAD_DETERMINISTIC is: every contribution is rounded once to the
+ * quantum 2^-SDFR_FIXED_QUANTUM_BITS (2^-40 = 9.1e-13) and added as a 64-bit INTEGER into a volume in the workspace
+ * (integer addition is associative: the same bits on every run, whatever the order), which is converted once and added
+ * to g_recon in fp64.  Representable range: |sum| < 2^(63 - 40) = 8.4e6 per voxel; a contribution that is not finite
+ * saturates (NaN counts as 0).  loss_pc is a two-stage sum in fixed order: a float record per workgroup, then the
+ * records in fp64 by one workgroup.  Pixels outside a conservative screen rectangle of the volume's bounding sphere
+ * (radius sqrt(3) |scale| around pos) are not read: their points lie outside the volume.
+ * Group 10's contract holds: no float atomics, no allocation, no host synchronisation, kernels only, on the caller's
+ * stream; 1 <= N <= 65535, 1 <= W, H <= 65535.  The workspace is the term's own (sdfr_vae_trainer_workspace_bytes
+ * keeps its values) and must be 8-byte aligned. */
+SDFR_API size_t sdfr_vae_trainer_pc_term_workspace_bytes(const sdfr_vae_trainer* trainer, int N);   /* 0: NULL or N < 1 */
+SDFR_API int sdfr_vae_trainer_pc_term(const sdfr_vae_trainer* trainer, const float* depth, int N, int W, int H, float cx,
+                                      float cy, float fx, float fy, const float* pos, const float* quat,
+                                      const float* scale, const float* recon, const float* x, int post, float pc_weight,
+                                      float* loss_pc, float* terms, float* g_recon, void* workspace,
+                                      size_t workspace_bytes, void* stream);
+/* The term's orientations, uniform on SO(3) as train.py:242-251 draws them, quat [N][4] (x, y, z, w) on the device:
+ *     q_i = (sqrt(1 - u1) sin 2 pi u2, sqrt(1 - u1) cos 2 pi u2, sqrt(u1) sin 2 pi u3, sqrt(u1) cos 2 pi u3)
+ * from the Philox-4x32-10 stream of group 7 with key = seed and counter {i, 0, 0, 0x56415043} ("VAPC", apart from the
+ * noise's 0x56414531): u_k = (word k - 1 of the output >> 8) * 2^-24, in [0, 1) with 24 bits each; the expression is
+ * evaluated in fp64 and rounded to fp32 once.  A function of (seed, i) alone: a resumed run draws what the
+ * uninterrupted one would.  N = 0: nothing to do. */
+SDFR_API int sdfr_vae_trainer_pc_orientations(unsigned long long seed, int N, float* quat, int device, void* stream);
 /* One torch.optim.Adam step (default betas 0.9 / 0.999, eps 1e-8, no weight decay, no amsgrad) over a flat buffer of n
  * floats: exp_avg += (g - exp_avg) (1 - b1); exp_avg_sq = b2 exp_avg_sq + (1 - b2) g g; p += -(lr / (1 - b1^t)) exp_avg
  * / (sqrt(exp_avg_sq) / sqrt(1 - b2^t) + eps), the bias corrections in fp64 as torch forms them.  step[0] (device int)

@@ -25,6 +25,8 @@
 //   linear weight  a thread per (out, in): the sum over the samples in ascending order (an outer-product sum over N)
 //   loss           stage 1: a thread takes kLossItems voxels, a workgroup reduces its four sums (butterfly, then the
 //                  waves in order); stage 2: one workgroup sums the records and the KLD in fp64, fixed tree
+//   pc term        a thread per depth pixel; loss_pc in the same two stages; the scatter into g_recon as 64-bit
+//                  fixed-point integer adds (associative: any order gives the same bits), converted once
 // Measured figures and what binds each kernel: DESIGN.md section 3.14.
 #include <hip/hip_runtime.h>
 
@@ -48,6 +50,10 @@ constexpr int kCombineSlices = 16;        // combine: threads per element, each 
 constexpr int kLossItems = 8;             // loss: voxels per thread
 constexpr int kSrcX = -1, kSrcZ = -2;     // an op's input: the volume, the latent, or the output of op `src`
 constexpr unsigned kMaxBlocks = 1u << 20;
+constexpr int kPcGroups = 128;            // point cloud term: workgroups (= records) per sample
+constexpr int kPcTileW = 32, kPcTileH = 8;   // ... pixels per workgroup and round
+static_assert(kPcTileW * kPcTileH == kThreads, "a thread per pixel of a tile");
+constexpr unsigned kPcStream = 0x56415043u;  // counter word 3 of the term's orientations ("VAPC", include/sdfr.h)
 }  // namespace
 
 struct TrainOp {
@@ -604,6 +610,168 @@ __global__ __launch_bounds__(kThreads) void train_z_dgrad_kernel(const float* __
   g_log_var[i] = gz[i] * (0.5f * normal_eps(seed, (unsigned)nb, (unsigned)j) * sd) + gk_log_var[i];
 }
 
+// ---- the point cloud term (train.py:230-269) --------------------------------------------------------------------------
+struct PcArgs {
+  int W, H, D;
+  float cx0, cy0, fx, fy;   // cx0, cy0: pixel-centre-0 intrinsics (the lift's; pointset_utils.py:57)
+  float tsdf;               // 0: no clamp
+  float w2;                 // 2 pc_weight
+};
+
+// the columns [c0, c1) in which X / d of a point with X in [lo, hi] and depth d in [dmin, dmax] (dmin > 0) can fall:
+// col = c + f X / d, one pixel of margin on either side
+__device__ __forceinline__ void pc_screen_range(float lo, float hi, float dmin, float dmax, float f, float c, int n, int& c0,
+                                                int& c1) {
+  const float ulo = lo <= 0.0f ? lo / dmin : lo / dmax, uhi = hi >= 0.0f ? hi / dmin : hi / dmax;
+  const float a = fmaf(f, ulo, c), b = fmaf(f, uhi, c);
+  const float top = (float)n + 1.0f;
+  c0 = max(0, (int)floorf(fminf(fmaxf(fminf(a, b), -1.0f), top)) - 1);
+  c1 = min(n, (int)ceilf(fminf(fmaxf(fmaxf(a, b), -1.0f), top)) + 2);
+}
+
+// One pass over the depth pixels of sample blockIdx.y: workgroup blockIdx.x of its kPcGroups takes the 32 x 8-pixel tiles
+// blockIdx.x, blockIdx.x + kPcGroups, ... of the screen rectangle of the volume's bounding sphere.  A hit pixel is
+// lifted, taken to the object frame and to its cell; its eight corners are read through the loss's masked clamp; v^2
+// goes to the thread's sum and 2 w v (trilinear weight) to the 64-bit fixed-point volume (integer adds: any order gives
+// the same bits).  Record (sample, workgroup) = the workgroup's sum of v^2 (butterfly, then its waves in order).
+__global__ __launch_bounds__(kThreads) void train_pc_term_kernel(const float* __restrict__ depth, PcArgs a,
+                                                                 const float* __restrict__ pos,
+                                                                 const float* __restrict__ quat,
+                                                                 const float* __restrict__ scale,
+                                                                 const float* __restrict__ recon,
+                                                                 const float* __restrict__ x,
+                                                                 unsigned long long* __restrict__ fixed,
+                                                                 float* __restrict__ records) {
+  __shared__ float part[kThreads / 64];
+  const int nb = blockIdx.y, D = a.D;
+  const size_t vox = (size_t)D * D * D;
+  const float px = pos[3 * nb], py = pos[3 * nb + 1], pz = pos[3 * nb + 2], sc = scale[nb];
+  // R(q / |q|), row-major: object -> camera; a point goes the other way, o = R^T (P - p) (train.py:48-69)
+  float rot[9];
+  {
+    const float x0 = quat[4 * nb], y0 = quat[4 * nb + 1], z0 = quat[4 * nb + 2], w0 = quat[4 * nb + 3];
+    const float inv = 1.0f / sqrtf(x0 * x0 + y0 * y0 + z0 * z0 + w0 * w0);
+    const float qx = x0 * inv, qy = y0 * inv, qz = z0 * inv, qw = w0 * inv;
+    rot[0] = 1 - 2 * (qy * qy + qz * qz); rot[1] = 2 * (qx * qy - qw * qz);     rot[2] = 2 * (qx * qz + qw * qy);
+    rot[3] = 2 * (qx * qy + qw * qz);     rot[4] = 1 - 2 * (qx * qx + qz * qz); rot[5] = 2 * (qy * qz - qw * qx);
+    rot[6] = 2 * (qx * qz - qw * qy);     rot[7] = 2 * (qy * qz + qw * qx);     rot[8] = 1 - 2 * (qx * qx + qy * qy);
+  }
+  // the rectangle: every point of the volume lies within r of pos, so with the whole sphere in front of the camera
+  // (dmin > 0) a pixel outside it lifts to a point outside the volume, whatever its depth
+  int c0 = 0, c1 = a.W, r0 = 0, r1 = a.H;
+  const float r = 1.7320508f * 1.001f * fabsf(sc), dmin = -pz - r, dmax = -pz + r;
+  if (dmin > 0.0f && dmax < 1e30f && fabsf(px) < 1e30f && fabsf(py) < 1e30f) {
+    pc_screen_range(px - r, px + r, dmin, dmax, a.fx, a.cx0, a.W, c0, c1);
+    pc_screen_range(py - r, py + r, dmin, dmax, -a.fy, a.cy0, a.H, r0, r1);
+  }
+  const int ntx = c1 > c0 ? (c1 - c0 + kPcTileW - 1) / kPcTileW : 0, nty = r1 > r0 ? (r1 - r0 + kPcTileH - 1) / kPcTileH : 0;
+  const int lx = threadIdx.x % kPcTileW, ly = threadIdx.x / kPcTileW;
+  const float h = 0.5f * (float)(D - 1), top = (float)(D - 2);
+  const float* __restrict__ rv = recon + (size_t)nb * vox;
+  const float* __restrict__ xv = x + (size_t)nb * vox;
+  unsigned long long* __restrict__ fv = fixed + (size_t)nb * vox;
+  const float* __restrict__ img = depth + (size_t)nb * a.H * a.W;
+  float sum = 0.0f;
+  for (int t = blockIdx.x; t < ntx * nty; t += kPcGroups) {
+    const int ty = t / ntx, tx = t - ty * ntx;
+    const int col = c0 + tx * kPcTileW + lx, row = r0 + ty * kPcTileH + ly;
+    if (col >= c1 || row >= r1) continue;
+    const float d = img[(size_t)row * a.W + col];
+    if (d == 0.0f) continue;
+    // depth_to_pointcloud, "opengl"
+    const float vx = ((float)col - a.cx0) * d / a.fx - px, vy = -((float)row - a.cy0) * d / a.fy - py, vz = -d - pz;
+    const float ox = fmaf(rot[0], vx, fmaf(rot[3], vy, rot[6] * vz)) / sc;
+    const float oy = fmaf(rot[1], vx, fmaf(rot[4], vy, rot[7] * vz)) / sc;
+    const float oz = fmaf(rot[2], vx, fmaf(rot[5], vy, rot[8] * vz)) / sc;
+    const float gx = (ox + 1.0f) * h, gy = (oy + 1.0f) * h, gz = (oz + 1.0f) * h;
+    const float bx = floorf(gx), by = floorf(gy), bz = floorf(gz);
+    // train.py:78-80: outside where a base cell index is < 0 or > D - 2 (a NaN coordinate: outside)
+    if (!(bx >= 0.0f && by >= 0.0f && bz >= 0.0f && bx <= top && by <= top && bz <= top)) continue;
+    const float fx1 = gx - bx, fy1 = gy - by, fz1 = gz - bz, fx0 = 1.0f - fx1, fy0 = 1.0f - fy1, fz0 = 1.0f - fz1;
+    const int lin = ((int)bx * D + (int)by) * D + (int)bz;
+    float cv[8], pass[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {   // corner k = 4 ix + 2 iy + iz (train.py:84-91)
+      const int at = lin + ((k & 4) ? D * D : 0) + ((k & 2) ? D : 0) + (k & 1);
+      float rc = rv[at];
+      pass[k] = 1.0f;
+      if (a.tsdf > 0.0f && fabsf(xv[at]) >= a.tsdf && fabsf(rc) >= a.tsdf) {   // as train_loss_kernel
+        pass[k] = (rc < -a.tsdf || rc > a.tsdf) ? 0.0f : 1.0f;
+        rc = fminf(fmaxf(rc, -a.tsdf), a.tsdf);
+      }
+      cv[k] = rc;
+    }
+    // x, then y, then z (train.py:99-123)
+    const float v = ((cv[0] * fx0 + cv[4] * fx1) * fy0 + (cv[2] * fx0 + cv[6] * fx1) * fy1) * fz0 +
+                    ((cv[1] * fx0 + cv[5] * fx1) * fy0 + (cv[3] * fx0 + cv[7] * fx1) * fy1) * fz1;
+    sum += v * v;
+    const float gv = a.w2 * v;
+    if (gv != 0.0f) {
+      const float q = (float)(1ll << SDFR_FIXED_QUANTUM_BITS);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        const float wk = ((k & 4) ? fx1 : fx0) * ((k & 2) ? fy1 : fy0) * ((k & 1) ? fz1 : fz0);
+        const long long c = __float2ll_rn(gv * wk * pass[k] * q);   // saturates; NaN -> 0
+        if (c != 0)
+          atomicAdd(fv + lin + ((k & 4) ? D * D : 0) + ((k & 2) ? D : 0) + (k & 1), (unsigned long long)c);
+      }
+    }
+  }
+#pragma unroll
+  for (int dl = 32; dl >= 1; dl >>= 1) sum += __shfl_xor(sum, dl, 64);
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = sum;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float t = part[0];
+    for (int wv = 1; wv < kThreads / 64; ++wv) t += part[wv];
+    records[(size_t)nb * kPcGroups + blockIdx.x] = t;
+  }
+}
+
+// one workgroup: thread t sums the records t, t + 256, ... (fp64), a fixed tree over the threads; loss_pc and the total
+__global__ __launch_bounds__(kThreads) void train_pc_finish_kernel(const float* __restrict__ records, long long n_records,
+                                                                   float pc_weight, float* __restrict__ loss_pc,
+                                                                   float* __restrict__ terms) {
+  __shared__ double red[kThreads];
+  double s = 0.0;
+  for (long long r = threadIdx.x; r < n_records; r += kThreads) s += (double)records[r];
+  red[threadIdx.x] = s;
+  __syncthreads();
+  for (int half = kThreads / 2; half >= 1; half >>= 1) {
+    if (threadIdx.x < half) red[threadIdx.x] += red[threadIdx.x + half];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    loss_pc[0] = (float)red[0];
+    terms[5] = (float)((double)terms[5] + (double)pc_weight * red[0]);
+  }
+}
+
+// g_recon += fixed 2^-SDFR_FIXED_QUANTUM_BITS, in fp64, rounded once; a voxel no point touched keeps its bits
+__global__ __launch_bounds__(kThreads) void train_pc_convert_kernel(const unsigned long long* __restrict__ fixed,
+                                                                    float* __restrict__ g_recon, long long total) {
+  const double quantum = 1.0 / (double)(1ll << SDFR_FIXED_QUANTUM_BITS);
+  for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < total; i += (long long)gridDim.x * kThreads) {
+    const long long f = (long long)fixed[i];
+    if (f != 0) g_recon[i] = (float)((double)g_recon[i] + (double)f * quantum);
+  }
+}
+
+// train.py:242-251 from the Philox stream (include/sdfr.h: counter {i, 0, 0, kPcStream}, 24 bits a uniform)
+__global__ __launch_bounds__(kThreads) void train_pc_orientations_kernel(unsigned long long seed, int N,
+                                                                         float* __restrict__ quat) {
+  const int i = blockIdx.x * kThreads + threadIdx.x;
+  if (i >= N) return;
+  const U4 r = philox4x32_10(U4{(unsigned)i, 0u, 0u, kPcStream}, (unsigned)seed, (unsigned)(seed >> 32));
+  const double k = 1.0 / 16777216.0, two_pi = 6.283185307179586;
+  const double u1 = (double)(r.x >> 8) * k, u2 = (double)(r.y >> 8) * k, u3 = (double)(r.z >> 8) * k;
+  const double a = sqrt(1.0 - u1), b = sqrt(u1);
+  quat[4 * i] = (float)(a * sin(two_pi * u2));
+  quat[4 * i + 1] = (float)(a * cos(two_pi * u2));
+  quat[4 * i + 2] = (float)(b * sin(two_pi * u3));
+  quat[4 * i + 3] = (float)(b * cos(two_pi * u3));
+}
+
 // ---- Adam -----------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kThreads) void adam_flat_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                              float* __restrict__ m, float* __restrict__ v,
@@ -1030,6 +1198,62 @@ extern "C" int sdfr_vae_trainer_backward(const sdfr_vae_trainer* t, const float*
       gout = gbuf[cur];
     }
   }
+  SDFR_HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+extern "C" size_t sdfr_vae_trainer_pc_term_workspace_bytes(const sdfr_vae_trainer* t, int N) {
+  if (!t || N < 1) return 0;
+  const size_t vox = (size_t)t->volume * t->volume * t->volume;
+  return (size_t)N * vox * sizeof(unsigned long long) + (size_t)N * kPcGroups * sizeof(float) + 256;
+}
+
+extern "C" int sdfr_vae_trainer_pc_term(const sdfr_vae_trainer* t, const float* depth, int N, int W, int H, float cx,
+                                        float cy, float fx, float fy, const float* pos, const float* quat,
+                                        const float* scale, const float* recon, const float* x, int post,
+                                        float pc_weight, float* loss_pc, float* terms, float* g_recon, void* workspace,
+                                        size_t workspace_bytes, void* stream) {
+  if (!t) return fail(SDFR_E_NULL, "sdfr_vae_trainer_pc_term: NULL trainer");
+  if (N < 1 || N > 65535) return fail(SDFR_E_INVALID, "sdfr_vae_trainer_pc_term: N=%d out of range", N);
+  if (W < 1 || W > 65535 || H < 1 || H > 65535)
+    return fail(SDFR_E_INVALID, "sdfr_vae_trainer_pc_term: image %d x %d out of range", W, H);
+  if (!(fabsf(fx) > 0.0f) || !(fabsf(fy) > 0.0f) || !std::isfinite(fx) || !std::isfinite(fy) || !std::isfinite(cx) ||
+      !std::isfinite(cy))
+    return fail(SDFR_E_INVALID, "sdfr_vae_trainer_pc_term: intrinsics fx=%g fy=%g cx=%g cy=%g", (double)fx, (double)fy,
+                (double)cx, (double)cy);
+  if (t->volume < 2) return fail(SDFR_E_INVALID, "sdfr_vae_trainer_pc_term: a volume of %d has no cell", t->volume);
+  if (!std::isfinite(pc_weight))
+    return fail(SDFR_E_INVALID, "sdfr_vae_trainer_pc_term: pc_weight %g is not finite", (double)pc_weight);
+  if (!depth || !pos || !quat || !scale || !recon || !x || !loss_pc || !terms || !g_recon)
+    return fail(SDFR_E_NULL, "sdfr_vae_trainer_pc_term: NULL pointer argument");
+  if (!workspace) return fail(SDFR_E_NULL, "sdfr_vae_trainer_pc_term: NULL workspace");
+  const size_t need = sdfr_vae_trainer_pc_term_workspace_bytes(t, N);
+  if (workspace_bytes < need)
+    return fail(SDFR_E_WORKSPACE, "sdfr_vae_trainer_pc_term: workspace %zu < %zu bytes", workspace_bytes, need);
+  SDFR_HIP_TRY(hipSetDevice(t->device));
+  hipStream_t st = (hipStream_t)stream;
+  const size_t vox = (size_t)t->volume * t->volume * t->volume;
+  unsigned long long* fixed = (unsigned long long*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+  float* records = (float*)(fixed + (size_t)N * vox);
+  const PcArgs a{W, H, t->volume, cx - 0.5f, cy - 0.5f, fx, fy, post ? t->tsdf : 0.0f, 2.0f * pc_weight};
+  zero_words_async((float*)fixed, (size_t)N * vox * 2, st);
+  hipLaunchKernelGGL(train_pc_term_kernel, dim3(kPcGroups, (unsigned)N), dim3(kThreads), 0, st, depth, a, pos, quat, scale,
+                     recon, x, fixed, records);
+  hipLaunchKernelGGL(train_pc_finish_kernel, dim3(1), dim3(kThreads), 0, st, (const float*)records,
+                     (long long)N * kPcGroups, pc_weight, loss_pc, terms);
+  launch_1d(train_pc_convert_kernel, (long long)(N * vox), st, (const unsigned long long*)fixed, g_recon,
+            (long long)(N * vox));
+  SDFR_HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+extern "C" int sdfr_vae_trainer_pc_orientations(unsigned long long seed, int N, float* quat, int device, void* stream) {
+  if (N < 0 || N > 65535) return fail(SDFR_E_INVALID, "sdfr_vae_trainer_pc_orientations: N=%d out of range", N);
+  if (N == 0) return 0;
+  if (!quat) return fail(SDFR_E_NULL, "sdfr_vae_trainer_pc_orientations: NULL quat");
+  SDFR_HIP_TRY(hipSetDevice(device));
+  hipLaunchKernelGGL(train_pc_orientations_kernel, dim3((unsigned)((N + kThreads - 1) / kThreads)), dim3(kThreads), 0,
+                     (hipStream_t)stream, seed, N, quat);
   SDFR_HIP_TRY(hipGetLastError());
   return 0;
 }

@@ -5,8 +5,16 @@
 forward with a tape, the loss, the gradient of every parameter, Adam -- in ``libsdfr_hip.so`` (csrc/vae_train.hip,
 include/sdfr.h group 10).  Inference handles (``SDFVAE``) are built from the trained state: ``vae()``.
 
-What the reference's iteration has and this one does not: the ``pc_weight`` term (a render of every target at a random
-pose per iteration; the reference's default weight is 0) -- a value other than 0 raises ``NotImplementedError``.
+The ``pc_weight`` term (train.py:230-269, :278; every model config the reference ships sets it to 1): per sample and
+iteration the TARGET volume is sphere-traced at an orientation uniform on SO(3) (``PC_POSITION``, ``PC_SCALE``,
+``PC_THRESHOLD``, ``PC_CAMERA``: the reference's literals), the hit pixels are lifted to points, and the sum of the
+squared trilinear values of the RECONSTRUCTION at those points (through the masked tsdf clamp when it is live) is added
+to the total with weight ``pc_weight``.  The render is ``sdfr_render_forward`` with one volume per view; the lift, the
+values, the sum and the gradient w.r.t. the reconstruction are one kernel (``sdfr_vae_trainer_pc_term``) between the
+loss and the backward.  The orientations are drawn on the device as a function of (seed, iteration, sample).  At the
+Python level the term needs ``sdf_size == 64``, the only size the reference trains at (train.py:163): there is no
+technical reason for the limit (the C entry point has none) -- tests/test_vae_train_cpu.py pins the
+``NotImplementedError`` on its 16^3 test architecture, and lifting the limit is a follow-up that edits that test.
 """
 import ctypes
 import glob
@@ -17,13 +25,19 @@ import numpy as np
 import torch
 
 from . import _lib
-from .differentiable_renderer import _stream
+from .differentiable_renderer import Camera, _stream
 from .vae import ENC_CONV, ENC_LINEAR, SDFVAE, _check_grid, _seed, encoder_state_keys, parse_encoder_layers
 
 TERMS = ("l2_small", "l2_large", "l1_small", "l1_large", "kld", "total")
 _DEFAULTS = {"iterations": 100000, "batch_size": 8, "learning_rate": 1e-3, "l2_large_weight": 1.0,
              "l2_small_weight": 1.0, "l1_large_weight": 0.0, "l1_small_weight": 0.0, "kld_weight": 1.0, "pc_weight": 0.0,
              "warm_up_iterations": 1000, "tsdf": False, "sdf_size": 64}
+
+# the pc_weight term's pose, threshold and camera: the literals of train.py:155, :255-263
+PC_POSITION = (0.0, 0.0, -5.0)
+PC_SCALE = 1.0
+PC_THRESHOLD = 0.01
+PC_CAMERA = Camera(640, 480, 320, 320, 320, 240, pixel_center=0.5)
 
 
 def parameter_shapes(config: Mapping) -> list:
@@ -57,9 +71,12 @@ def check_config(config: Mapping) -> dict:
     for key in ("latent_size", "encoder", "decoder"):
         if key not in cfg:
             raise KeyError(f"the config has no {key!r}")
-    if float(cfg["pc_weight"] or 0.0) != 0.0:
-        raise NotImplementedError(f"pc_weight={cfg['pc_weight']!r}: the point cloud term of the reference's trainer is not "
-                                  "implemented (only pc_weight = 0, the reference's default)")
+    if float(cfg["pc_weight"] or 0.0) != 0.0 and int(cfg["sdf_size"]) != 64:
+        raise NotImplementedError(f"pc_weight={cfg['pc_weight']!r} with sdf_size={cfg['sdf_size']!r}: the point cloud term "
+                                  "is enabled for sdf_size = 64 only, the one size the reference trains at "
+                                  "(train.py:163).  There is no technical reason for the limit "
+                                  "(sdfr_vae_trainer_pc_term has none): an existing test pins this error on a 16^3 "
+                                  "architecture, and lifting the limit is a follow-up that edits that test")
     if cfg["tsdf"] is not False and not float(cfg["tsdf"]) > 0.0:
         raise ValueError(f"tsdf={cfg['tsdf']!r} must be False or > 0")
     return cfg
@@ -99,9 +116,12 @@ def load_volumes(folder: str) -> torch.Tensor:
 class SDFVAETrainer:
     """One VAE and its Adam state on the GPU.  ``config``: the reference's training + network keys (iterations,
     batch_size, learning_rate, the five loss weights, pc_weight, latent_size, tsdf, encoder, decoder) plus
-    ``warm_up_iterations`` (1000, the reference's literal) and ``sdf_size`` (64)."""
+    ``warm_up_iterations`` (1000, the reference's literal) and ``sdf_size`` (64).  ``pc_camera``: the camera of the
+    ``pc_weight`` term's renders in place of ``PC_CAMERA``.  With ``pc_weight != 0``, ``pc_term`` holds the unweighted
+    point cloud sum of the last iteration (a one-element device tensor) and ``total`` includes the term."""
 
-    def __init__(self, config: Mapping, state_dict: Optional[Mapping] = None, seed: int = 0, device="cuda"):
+    def __init__(self, config: Mapping, state_dict: Optional[Mapping] = None, seed: int = 0, device="cuda",
+                 pc_camera: Optional[Camera] = None):
         self.config = check_config(config)
         cfg = self.config
         self._shapes = parameter_shapes(cfg)          # raises for unsupported layers, before anything touches the GPU
@@ -135,6 +155,9 @@ class SDFVAETrainer:
         self._exp_avg_sq = torch.zeros(count, **f32)
         self._step = torch.zeros(1, dtype=torch.int32, device=self.device)
         self._terms = torch.zeros(6, **f32)
+        self.pc_weight = float(cfg["pc_weight"] or 0.0)
+        self.pc_camera = PC_CAMERA if pc_camera is None else pc_camera
+        self.pc_term = torch.zeros(1, **f32)
         self._batch = {}       # N -> the buffers of an iteration
         self.load_state_dict(initial_state(cfg, self.seed) if state_dict is None else state_dict)
 
@@ -204,6 +227,20 @@ class SDFVAETrainer:
             b["tape"] = torch.empty(self._L.sdfr_vae_trainer_tape_bytes(self._h, N), dtype=torch.uint8, device=self.device)
             b["ws"] = torch.empty(self._L.sdfr_vae_trainer_workspace_bytes(self._h, N), dtype=torch.uint8,
                                   device=self.device)
+            if self.pc_weight != 0.0:   # the term's pose, images and the two workspaces: made once per batch size
+                cam = self.pc_camera
+                b["pc_quat"] = torch.empty((N, 4), **f32)
+                b["pc_pos"] = torch.tensor(PC_POSITION, **f32).repeat(N, 1)
+                b["pc_scale"] = torch.full((N,), PC_SCALE, **f32)
+                b["pc_inv_scale"] = torch.full((N,), 1.0 / PC_SCALE, **f32)
+                b["pc_depth"] = torch.empty((N, cam.height, cam.width), **f32)
+                # zero-filled once, as BatchRenderPlan's (the sync region's counter then counts from 0)
+                nbytes = self._L.sdfr_render_forward_workspace_bytes(D, N, cam.width, cam.height)
+                if nbytes == 0:
+                    _lib.check(_lib.ABI["SDFR_E_INVALID"], "sdfr_render_forward_workspace_bytes")
+                b["pc_render_ws"] = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
+                b["pc_ws"] = torch.empty(self._L.sdfr_vae_trainer_pc_term_workspace_bytes(self._h, N), dtype=torch.uint8,
+                                         device=self.device)
             self._batch = {N: b}     # one batch size at a time
         return b
 
@@ -212,7 +249,39 @@ class SDFVAETrainer:
             return (self.seed * 0x9E3779B97F4A7C15 + self.iteration * 0xD1B54A32D192ED03 + 1) & 0xFFFFFFFFFFFFFFFF
         return _seed(seed)
 
-    def _forward_backward(self, x: torch.Tensor, seed: int, iteration: int) -> dict:
+    def _pc_term(self, b: dict, N: int, seed: int, post: int, orientations, depth) -> None:
+        """the pc_weight term between the loss and the backward: orientations (drawn, or the caller's), the render of
+        the targets b["x"] (or the caller's images), then the kernel that adds to the total and to g_recon"""
+        L, st, cam, D = self._L, _stream(self.device), self.pc_camera, self.sdf_size
+        p = lambda name: b[name].data_ptr()
+        if orientations is None:
+            rc = L.sdfr_vae_trainer_pc_orientations(seed, N, p("pc_quat"), self.device.index, st)
+            _lib.check(rc, "sdfr_vae_trainer_pc_orientations")
+        else:
+            q = torch.as_tensor(orientations, dtype=torch.float32)
+            if tuple(q.shape) != (N, 4):
+                raise ValueError(f"pc_orientations must have shape ({N}, 4), got {tuple(q.shape)}")
+            with torch.no_grad():
+                b["pc_quat"].copy_(q)
+        fx, fy, cx, cy, _ = cam.get_pinhole_camera_parameters(0.5)
+        if depth is None:
+            rc = L.sdfr_render_forward(p("x"), D, D * D * D, p("pc_pos"), p("pc_quat"), p("pc_inv_scale"), N, cam.width,
+                                       cam.height, cx, cy, fx, fy, PC_THRESHOLD, p("pc_depth"), p("pc_render_ws"),
+                                       b["pc_render_ws"].numel(), self.device.index, st)
+            _lib.check(rc, "sdfr_render_forward")
+        else:
+            d = torch.as_tensor(depth, dtype=torch.float32)
+            if tuple(d.shape) != tuple(b["pc_depth"].shape):
+                raise ValueError(f"pc_depth must have shape {tuple(b['pc_depth'].shape)}, got {tuple(d.shape)}")
+            with torch.no_grad():
+                b["pc_depth"].copy_(d)
+        rc = L.sdfr_vae_trainer_pc_term(self._h, p("pc_depth"), N, cam.width, cam.height, cx, cy, fx, fy, p("pc_pos"),
+                                        p("pc_quat"), p("pc_scale"), p("recon"), p("x"), post, self.pc_weight,
+                                        self.pc_term.data_ptr(), self._terms.data_ptr(), p("g_recon"), p("pc_ws"),
+                                        b["pc_ws"].numel(), st)
+        _lib.check(rc, "sdfr_vae_trainer_pc_term")
+
+    def _forward_backward(self, x: torch.Tensor, seed: int, iteration: int, pc_orientations=None, pc_depth=None) -> dict:
         _check_grid(x, self.sdf_size, self.device, "x")
         N = x.shape[0]
         b = self._buffers(N)
@@ -230,22 +299,33 @@ class SDFVAETrainer:
                                      self._terms.data_ptr(), p("g_recon"), p("g_means"), p("g_log_var"), p("ws"),
                                      b["ws"].numel(), st)
         _lib.check(rc, "sdfr_vae_trainer_loss")
+        if self.pc_weight != 0.0:
+            self._pc_term(b, N, seed, post, pc_orientations, pc_depth)
+        elif pc_orientations is not None or pc_depth is not None:
+            raise ValueError("pc_orientations / pc_depth need pc_weight != 0")
         rc = L.sdfr_vae_trainer_backward(h, self._params.data_ptr(), p("x"), N, seed, p("log_var"), p("z"), p("tape"),
                                          p("recon"), p("g_recon"), p("g_means"), p("g_log_var"), self._grads.data_ptr(),
                                          p("ws"), b["ws"].numel(), st)
         _lib.check(rc, "sdfr_vae_trainer_backward")
         return b
 
-    def loss_and_grad(self, x: torch.Tensor, seed: Optional[int] = None, iteration: Optional[int] = None) -> dict:
+    def loss_and_grad(self, x: torch.Tensor, seed: Optional[int] = None, iteration: Optional[int] = None,
+                      pc_orientations=None, pc_depth=None) -> dict:
         """Forward, loss and backward at `iteration` (default: the trainer's own) without an update.  Returns the six
         loss numbers (``TERMS``) as floats, ``grads``: name -> view of the gradient buffer, and clones of ``means``,
-        ``log_var``, ``z`` and ``recon``."""
+        ``log_var``, ``z`` and ``recon``.  With ``pc_weight != 0`` also ``pc`` (the unweighted point cloud sum; ``total``
+        includes it), ``pc_orientations`` (N, 4) and ``pc_depth`` (N, H, W), the images the points were lifted from;
+        `pc_orientations` given: used in place of the draw; `pc_depth` given: used in place of the render (a float64
+        twin can then work on the same hit pixels)."""
         it = self.iteration if iteration is None else int(iteration)
-        b = self._forward_backward(x, self._iteration_seed(seed), it)
+        b = self._forward_backward(x, self._iteration_seed(seed), it, pc_orientations, pc_depth)
         out = dict(zip(TERMS, self._terms.tolist()))
         out["grads"] = self._views(self._grads)
         for name in ("means", "log_var", "z", "recon"):
             out[name] = b[name].clone()
+        if self.pc_weight != 0.0:
+            out["pc"] = float(self.pc_term.item())
+            out["pc_orientations"], out["pc_depth"] = b["pc_quat"].clone(), b["pc_depth"].clone()
         return out
 
     def step(self, x: torch.Tensor, seed: Optional[int] = None) -> torch.Tensor:
@@ -262,7 +342,8 @@ class SDFVAETrainer:
     def fit(self, volumes_or_folder, iterations: Optional[int] = None, log_every: int = 100, callback=None) -> int:
         """The reference's loop (train.py:195-372): epochs over the volumes in a seeded shuffle, ``drop_last``, until
         the trainer's iteration counter reaches `iterations` (default: the config's).  The loss terms are copied to
-        the host every `log_every` iterations only, and given to ``callback(iteration, terms: dict)`` (default: print).
+        the host every `log_every` iterations only, and given to ``callback(iteration, terms: dict)`` (default: print);
+        with ``pc_weight != 0`` the dict has ``pc`` as well.
         Returns the number of epochs begun."""
         data = load_volumes(volumes_or_folder) if isinstance(volumes_or_folder, (str, os.PathLike)) else \
             torch.as_tensor(np.asarray(volumes_or_folder) if not isinstance(volumes_or_folder, torch.Tensor)
@@ -287,6 +368,8 @@ class SDFVAETrainer:
                 terms = self.step(x)
                 if log_every and self.iteration % log_every == 0:
                     named = dict(zip(TERMS, terms.tolist()))
+                    if self.pc_weight != 0.0:
+                        named["pc"] = float(self.pc_term.item())
                     if callback is not None:
                         callback(self.iteration, named)
                     else:

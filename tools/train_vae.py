@@ -3,8 +3,9 @@
 
 Reads a folder of ``00000.npy, 00001.npy, ...`` volumes as ``tools/process_meshes.py`` writes them, and a YAML config
 with the reference's keys (``vae/configs/default_training.yaml`` + a network config: iterations, batch_size,
-learning_rate, the five loss weights, pc_weight (must be 0), latent_size, tsdf, encoder, decoder; optional
-warm_up_iterations, sdf_size).  Writes ``{out}.pt`` (``torch.save`` of the state dict, the reference's keys) and
+learning_rate, the five loss weights, pc_weight, latent_size, tsdf, encoder, decoder; optional warm_up_iterations,
+sdf_size; the reference's model configs, e.g. initialization/configs/vae_models/mug.yaml with pc_weight: 1.0, train as
+they are, and the log lines then carry the point cloud term as ``pc``).  Writes ``{out}.pt`` (``torch.save`` of the state dict, the reference's keys) and
 ``{out}.yaml`` (the model keys and ``model: ./{name}.pt``, as train.py:377-381), which ``SDFVAE.from_config`` and the
 reference load; ``{out}.ckpt`` holds the trainer's checkpoint (parameters, Adam's moments, the iteration) for
 ``--checkpoint``.
