@@ -48,7 +48,7 @@
  *        sdfr_render_forward[_workspace_bytes], sdfr_render_backward[_workspace_bytes]
  *        sdfr_pc_loss_forward, sdfr_pc_loss_backward[_workspace_bytes]
  *        sdfr_decoder_create / _destroy / _forward / _workspace_bytes / _tape_bytes,
- *        sdfr_decoder_backward_latent[_workspace_bytes], sdfr_decoder_set_option
+ *        sdfr_decoder_backward_latent[_workspace_bytes], sdfr_decoder_set_option, sdfr_decoder_fc_one_wave
  *   2. [unstable] BATCHED / STEP forms of the same arithmetic (fewer launches, fewer bytes; same results)
  *        sdfr_render_step_forward[_counted|_resident] / _step_backward / _step_workspace_bytes, sdfr_render_sync_offset,
  *        sdfr_render_forward_resident, sdfr_render_resident_state_bytes,
@@ -475,6 +475,12 @@ SDFR_API int sdfr_decoder_forward(const sdfr_decoder* decoder, const float* z, i
 #define SDFR_DECODER_OPT_FC_ONE_WAVE 2
 #define SDFR_DECODER_OPT_FUSED_SINGLE 3
 SDFR_API int sdfr_decoder_set_option(sdfr_decoder* decoder, int option, int value);
+/* Read only: 1 if the calls on this handle take the one-wave form of the Linear stack's leading layers -- at most 8
+ * layers, every layer input at most 64 wide, their weights and biases AS THEY LIE in the device image (64-float
+ * alignment gaps between the blocks included) within 6144 floats, and SDFR_DECODER_OPT_FC_ONE_WAVE not switched off --,
+ * 0 if not, SDFR_E_NULL without a handle.  The one statement of that criterion: what sdfr_loop_tail_fused(decoder_tape)
+ * requires, so a caller asks here instead of repeating the arithmetic.  Changes nothing. */
+SDFR_API int sdfr_decoder_fc_one_wave(const sdfr_decoder* decoder);
 /* Vector-Jacobian product of the decoder w.r.t. the latent, weights held constant: what
  * loss.backward() propagates to latent_shape in SDFPipeline.__call__
  * (sdfest/estimation/simple_setup.py:413-414, :456) through SDFDecoder.forward

@@ -2643,6 +2643,13 @@ bool decoder_fc_one_wave(const sdfr_decoder* dec, const FcDesc& d) {
 }
 }
 
+extern "C" int sdfr_decoder_fc_one_wave(const sdfr_decoder* d) {
+  if (!d) return fail(SDFR_E_NULL, "sdfr_decoder_fc_one_wave: decoder is NULL");
+  sdfr::FcDesc fd;
+  sdfr::decoder_fc_desc(d, &fd, nullptr, nullptr);
+  return sdfr::decoder_fc_one_wave(d, fd) ? 1 : 0;
+}
+
 extern "C" size_t sdfr_decoder_backward_workspace_bytes(const sdfr_decoder* d, int N) {
   if (!d || N <= 0) return 0;
   return 2 * (size_t)N * d->max_bwd * sizeof(float) + 512;

@@ -393,7 +393,15 @@ class FusedRenderAndCompare:
         must = self.group is not None or bool(self.sdf_grad_mode & BWD_SMALL_TILES)
         if form == "tail" and must:
             raise ValueError("a process group (and BWD_SMALL_TILES) needs the records form")
-        self.records_form = must or form == "records" or (form == "auto" and self.V_all >= 8 and bool(fuse_depth_loss))
+        # (the one-workgroup tail kernels own one parameter per thread: vectors of more than 256 entries -- a latent
+        # above 248 -- take the separate launches, whose Adam step has no such bound; a form that cannot is refused here,
+        # not by its first iteration)
+        n_vec = 8 + int(decoder.latent_size)
+        self.records_form = must or form == "records" or (form == "auto" and self.V_all >= 8 and bool(fuse_depth_loss)
+                                                          and n_vec <= 256)
+        if self.records_form and n_vec > 256:
+            raise ValueError(f"the records form's tail handles parameter vectors of up to 256 entries, this decoder's "
+                             f"latent makes {n_vec}")
         self.view_begin, self.view_end = shard_views(self.V_all, self.rank, self.world)
         if self.view_end == self.view_begin:
             raise ValueError(f"{self.V_all} view(s) cannot be sharded over {self.world} ranks: every rank needs one")
@@ -499,7 +507,7 @@ class FusedRenderAndCompare:
                     and self.max_pts > 0 and self.sdf_grad_mode in (0, 1) and 8 + self.Lz <= 256)
         if fused_render and not can_fuse:
             raise ValueError("fused_render needs the tail form over at most 8 views of a grid up to 128^3, the loss-fused "
-                             "kernels and sdf_grad_mode 0 / 1")
+                             "kernels, sdf_grad_mode 0 / 1 and a parameter vector of at most 256 entries")
         # (default: where it measured faster -- with shape optimisation up to 4 views: 1 view 0.111 -> 0.099 ms per
         # iteration, 2: 0.112 -> 0.102, 3: 0.114 -> 0.107, 4: 0.119 -> 0.116, but 7: 0.126 -> 0.132 -- every view adds a
         # megabyte to sum, to clear and to collide in; pose only, where no volume exists, wherever it applies)

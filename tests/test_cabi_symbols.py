@@ -220,6 +220,22 @@ def test_argument_errors_without_gpu(libpath):
     assert rc != 0 and b"workspace" in L.sdfr_last_error()
 
 
+def test_one_wave_query_is_declared_bound_and_validates_its_argument(libpath):
+    """sdfr_decoder_fc_one_wave: the one statement of the Linear stack's one-wave criterion, read only -- declared in the
+    header, so the binding table and the export list carry it; without a handle it reports SDFR_E_NULL before any HIP
+    call (what it answers for a decoder is asked on the GPU: tests/test_loop_decoders_gpu.py)"""
+    from sdfest_amd import _lib
+    assert "sdfr_decoder_fc_one_wave" in declared_symbols()
+    assert _lib.SIGNATURES["sdfr_decoder_fc_one_wave"] == (ctypes.c_int, [ctypes.c_void_p])
+    L = _lib.lib()
+    assert L.sdfr_decoder_fc_one_wave(None) == _lib.ABI["SDFR_E_NULL"] == -2 and b"decoder is NULL" in L.sdfr_last_error()
+    # the Python side asks the library and keeps no copy of the arithmetic
+    import inspect
+    from sdfest_amd import vae
+    src = inspect.getsource(vae.SDFDecoder.narrow_linear_stack)
+    assert "sdfr_decoder_fc_one_wave" in src and "set_option" not in src
+
+
 def test_product_does_not_import_oracle():
     """The product package must never route through the oracle (or any CPU fallback)."""
     pkg = os.path.join(ROOT, "sdfest_amd")

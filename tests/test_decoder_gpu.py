@@ -167,19 +167,18 @@ def test_decoder_latent_gradient_matches_torch_autograd_golden(mug):
     assert np.allclose(z1.grad.cpu().numpy()[0], 2.0 * gz[9], rtol=1e-5, atol=1e-5 * scale[9])
 
 
-def torch_decoder(state, fc, conv, volume, z):
-    """Plain PyTorch (CPU, float64) statement of SDFDecoder.forward (sdf_vae.py:217-259)."""
+def torch_decoder(state, fc, conv, volume, z, dtype=torch.float64):
+    """Plain PyTorch (CPU, float64 unless `dtype` says float32) statement of SDFDecoder.forward (sdf_vae.py:217-259)."""
     import torch.nn.functional as F
+    P = lambda name: torch.tensor(state[name]).to(dtype)
     out = z
     for i in range(len(fc)):
-        out = F.relu(F.linear(out, torch.tensor(state[f"decoder._fc_layers.{i}.weight"]).double(),
-                              torch.tensor(state[f"decoder._fc_layers.{i}.bias"]).double()))
+        out = F.relu(F.linear(out, P(f"decoder._fc_layers.{i}.weight"), P(f"decoder._fc_layers.{i}.bias")))
     out = out.view(-1, conv[0]["in_channels"], *([conv[0]["in_size"]] * 3))
     for i, l in enumerate(conv):
         if out.shape[2] != l["in_size"]:
             out = F.interpolate(out, size=(l["in_size"],) * 3, mode="trilinear", align_corners=False)
-        out = F.conv3d(out, torch.tensor(state[f"decoder._conv_layers.{i}.weight"]).double(),
-                       torch.tensor(state[f"decoder._conv_layers.{i}.bias"]).double())
+        out = F.conv3d(out, P(f"decoder._conv_layers.{i}.weight"), P(f"decoder._conv_layers.{i}.bias"))
         if l["relu"]:
             out = F.relu(out)
     if out.shape[2] != volume:

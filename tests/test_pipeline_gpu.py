@@ -8,80 +8,10 @@ import torch
 
 import oracle
 from helpers import GOLDEN
+# (the float64 restatement lives beside its extension to shape optimisation and to other decoders)
+from loop_decoders import oracle_loop, qinv, qmul, qrot
 
 pytestmark = pytest.mark.gpu
-
-
-def qmul(a, b):
-    ax, ay, az, aw = a
-    bx, by, bz, bw = b
-    return np.array([aw * bx + ax * bw + ay * bz - az * by, aw * by - ax * bz + ay * bw + az * bx,
-                     aw * bz + ax * by - ay * bx + az * bw, aw * bw - ax * bx - ay * by - az * bz])
-
-
-def qinv(q):
-    return q * np.array([-1, -1, -1, 1.0])
-
-
-def qrot(q, v):
-    return qmul(qmul(q, np.append(v, 0.0)), qinv(q))[:3]
-
-
-def left_mul_matrix(a):
-    """M with qmul(a, b) = M @ b."""
-    ax, ay, az, aw = a
-    return np.array([[aw, -az, ay, ax], [az, aw, -ax, ay], [-ay, ax, aw, az], [-ax, -ay, -az, aw]])
-
-
-class NumpyAdam:
-    def __init__(self, lrs):
-        self.lrs, self.m, self.v, self.t = lrs, [0.0] * len(lrs), [0.0] * len(lrs), 0
-
-    def step(self, params, grads):
-        self.t += 1
-        out = []
-        for i, (p, g) in enumerate(zip(params, grads)):
-            self.m[i] = 0.9 * self.m[i] + 0.1 * g
-            self.v[i] = 0.999 * self.v[i] + 0.001 * g * g
-            mh = self.m[i] / (1 - 0.9 ** self.t)
-            vh = self.v[i] / (1 - 0.999 ** self.t)
-            out.append(p - self.lrs[i] * mh / (np.sqrt(vh) + 1e-8))
-        return out
-
-
-def oracle_loop(sdf, depth_images, cam, cam_pos, cam_quat, p, q, s, thr, iters, wd, wpc):
-    """numpy float64 restatement of simple_setup.py:408-462 with shape_optimization=False."""
-    W, H, fx, fy, cx, cy = cam
-    V = depth_images.shape[0]
-    clouds = [oracle.depth_to_pointcloud(d, fx, fy, cx - 0.5, cy - 0.5, dtype=np.float64) for d in depth_images]
-    adam = NumpyAdam([1e-3, 1e-2, 1e-3])
-    traj = []
-    for _ in range(iters):
-        nq = q / np.linalg.norm(q)
-        gp, gnq, gs = np.zeros(3), np.zeros(4), 0.0
-        for v in range(V):
-            qw2c = qinv(cam_quat[v])
-            Rw2c = np.stack([qrot(qw2c, e) for e in np.eye(3)], axis=1)
-            pc = Rw2c @ (p - cam_pos[v])
-            qc = qmul(qw2c, nq)
-            est = oracle.render_forward(sdf, pc, qc, [1.0 / s], W, H, cx, cy, fx, fy, thr, dtype=np.float64)[0]
-            mask = (depth_images[v] > 0) & (est > 0)
-            gimg = wd * np.sign(est - depth_images[v]) * mask / mask.sum()
-            _, g_pc, g_qc, g_is = oracle.render_backward(gimg, est, sdf, pc, qc, [1.0 / s], cx, cy, fx, fy,
-                                                         dtype=np.float64)
-            val = oracle.pc_loss_forward(clouds[v], pc, qc, s, sdf, dtype=np.float64)
-            go = wpc * np.sign(val) / len(val)
-            _, g_pc2, g_qc2, g_s2 = oracle.pc_loss_backward(go, clouds[v], pc, qc, s, sdf, dtype=np.float64)
-            gp += Rw2c.T @ (g_pc[0] + g_pc2)
-            gnq += left_mul_matrix(qw2c).T @ (g_qc[0] + g_qc2)
-            gs += -g_is[0] / s ** 2 + g_s2
-        n = np.linalg.norm(q)
-        gq = (gnq - nq * (nq @ gnq)) / n
-        p, q, s = adam.step([p, q, np.array(s)], [gp, gq, np.array(gs)])
-        s = float(s)
-        q = q / np.linalg.norm(q)
-        traj.append((p.copy(), q.copy(), s))
-    return traj
 
 
 @pytest.fixture(scope="module")
