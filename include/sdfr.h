@@ -67,7 +67,8 @@
  *        sdfr_inlier_update_record
  *   4. [unstable] GENERATOR / INITIALISATION (the forward-only callers around the loop)
  *        sdfr_affine_mask; sdfr_pointnet_layer[_counted], sdfr_linear_vec, sdfr_orientation_posterior,
- *        sdfr_init_estimate
+ *        sdfr_init_estimate; N sets per launch and the trainer's validation numbers: sdfr_pointnet_layer_batch,
+ *        sdfr_linear_rows, sdfr_pose_metrics[_workspace_bytes]
  *   5. [unstable] MESH: marching cubes over N grids (SDFPipeline.generate_mesh, after the estimate)
  *        sdfr_mesh_tables, sdfr_mesh_workspace_bytes, sdfr_mesh_count, sdfr_mesh_emit
  *   6. [unstable] METRICS: surface sampling and exact neighbour search for reconstruction metrics (the evaluation)
@@ -851,6 +852,47 @@ SDFR_API int sdfr_init_estimate(const float* head, int latent, const float* grid
                        const float* centroid, const float* cam_pos, const float* cam_quat, int mean_shape,
                        int take_if_better, const float* posterior_max, float* best, float* params, int device,
                        void* stream);
+
+/* ---- the same network on N point sets per launch (eval() over a validation set: sdfest/initialization/scripts/
+ * train.py:439-481) -- csrc/initnet_eval.hip.  Row n of every result has the bits of the single-set call on set n: the
+ * same tile, the same k chunks, the same reductions; it depends neither on N nor on the other sets nor on M_capacity. */
+
+/* sdfr_pointnet_layer for N sets: x [N][M_capacity][ldx], y / resid [N][M_capacity][ldy] (both nullable), colmax
+ * [N][cout] (written).  counts: device int [N], the real rows of every set, clamped to [0, M_capacity]; NULL: every
+ * set has M_capacity rows.  Rows past counts[n] are neither read into a result nor written; a set without rows gets 0
+ * in every column of colmax.  cvec_stride = 0: cvec [cout] is shared; = cout: cvec [N][cout], one per set (a dense
+ * link's bias + W[:, cin:] . max[n], sdfr_linear_rows).  bn_scale / bn_shift [cout] are shared.
+ * pool_resid = 0: colmax = max over the rows of Y, and y = resid + Y needs y as in sdfr_pointnet_layer.
+ * pool_resid = 1 (a residual link into the LAST layer, pointnet.py:88-96): colmax = max over the rows of resid + Y,
+ * of any sign; y may be NULL.  With y == NULL nothing but colmax is stored.  1 <= N <= 65535, N M_capacity <= 2^30. */
+SDFR_API int sdfr_pointnet_layer_batch(const float* x, const int* counts, int N, int M_capacity, int cin, int ldx,
+                                       const float* w, int ldw, const float* cvec, int cvec_stride,
+                                       const float* bn_scale, const float* bn_shift, const float* resid, float* y,
+                                       int ldy, int cout, int pool_resid, float* colmax, int device, void* stream);
+
+/* sdfr_linear_vec on N rows: y[n] = act((W[:, koff:koff+k] . x[n] + bias) * bn_scale + bn_shift), x [N][ldx],
+ * y [N][ldy]; every (row, column) is summed in sdfr_linear_vec's order.  1 <= N <= 65535. */
+SDFR_API int sdfr_linear_rows(const float* w, int ldw, int koff, const float* x, int ldx, int k, const float* bias,
+                              const float* bn_scale, const float* bn_shift, int relu, float* y, int ldy, int cout, int N,
+                              int device, void* stream);
+
+/* The validation numbers of train.py:439-481 (and the "metric geodesic distance" of :344-374) for one batch, added to
+ * record [5] (fp64, caller-owned, zeroed by the caller in front of a validation set):
+ *   record[0] += sum |p - p*|_2          record[1] += sum |s - s*|
+ *   record[2] += sum 2 acos(clip(|q . q*|, 0, 1))
+ *   record[3] += sum (logsumexp(logits) - logits[orientation_index])   (n_cells > 0 and orientation_index != NULL)
+ *   record[4] += N
+ * out [N][ld_out]: the head's rows, latent [latent], position [3], scale [1], then n_cells logits or (n_cells = 0) the
+ * quaternion before its normalisation.  q = grid_quats [n_cells][4] at the FIRST maximum of the logits
+ * (sdfr_orientation_posterior's rule), or the row's quaternion normalised.  Targets: position [N][3], scale [N],
+ * quat [N][4], orientation_index [N] (nullable; clamped to the table).  Per sample in fp64 by one wave, into
+ * workspace (sdfr_pose_metrics_workspace_bytes(N), 8-byte aligned); then ONE thread adds the N samples to the record in
+ * sample order: no atomics, the same batches in the same order give the same bits. */
+SDFR_API size_t sdfr_pose_metrics_workspace_bytes(int N);   /* 0: N < 1 */
+SDFR_API int sdfr_pose_metrics(const float* out, int N, int ld_out, int latent, int n_cells, const float* grid_quats,
+                               const float* position, const float* scale, const float* quat,
+                               const int* orientation_index, double* record, void* workspace, size_t workspace_bytes,
+                               int device, void* stream);
 
 /* ==== 5. MESH ================================================================================= */
 /* ---- marching cubes: simple_setup.py:621-669 (generate_mesh: skimage.measure.marching_cubes) ----------------------

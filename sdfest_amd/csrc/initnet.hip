@@ -14,20 +14,12 @@
 //     second half is the same vector for every point, so W[:, C:] . max goes into the layer's bias;
 //   * the last backbone layer (M x 1024) is never written: only its column maximum leaves the kernel.
 #include "common.hpp"
+#include "initnet_tile.hpp"
 
 #include <algorithm>
 
 namespace sdfr {
 namespace {
-
-// torch.relu keeps NaN (fmaxf(NaN, 0) would return 0 and hide bad weights or points); the NaN returned is the
-// canonical positive one, which the bit-pattern maximum of the set pooling carries to the output
-__device__ __forceinline__ float relu_nan(float v) { return (v != v) ? __int_as_float(0x7fc00000) : fmaxf(v, 0.0f); }
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-// (K = 128, the mug backbone's inner layers, as ONE chunk -- 66 KB of dynamic LDS, a run-time row stride -- was
-// measured: 13.8 -> 16.7 us per layer; the second chunk's four columns cost less than that)
-constexpr int kPtsPerBlock = 64, kColsPerBlock = 64, kChunk = 124;
 
 // Y = relu((X W^T + c) * s + t), optionally F_out = F_res + Y, and colmax[col] = max over the points.
 //   x [M][ldx] (K = cin columns used), w [cout][ldw] (first cin columns used), c / s / t [cout]

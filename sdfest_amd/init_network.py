@@ -4,7 +4,9 @@
 ``SDFPipeline._nn_init`` (estimation/simple_setup.py:718-844), which runs it once before the
 render-and-compare loop.  The arithmetic runs in ``libsdfr_hip.so`` (initnet.hip): per-point layers
 as fp32 MFMA GEMMs with bias / BatchNorm / ReLU / residual / set-maximum epilogues, the head as
-wave-per-row products, softmax + prior adjustment + argmax in one kernel.
+wave-per-row products, softmax + prior adjustment + argmax in one kernel.  ``features_batch`` / ``forward_batch`` run N
+point sets per launch (initnet_eval.hip: the trainer's validation, sdfest_amd.init_train); row n has the bits of the
+single-set call on set n.
 
 Weights come as the state dict of the reference's ``SDFPoseNet`` (keys ``_backbone._linear_layers.i.*``,
 ``_backbone._bn_layers.i.*``, ``_head._linear_layers.i.*``, ``_head._bn_layers.i.*``,
@@ -40,6 +42,12 @@ def adjust_categorical_posterior(posterior: torch.Tensor, prior: torch.Tensor,
 
 def _f32(t, dev):
     return torch.as_tensor(np.asarray(t) if not torch.is_tensor(t) else t).to(device=dev, dtype=torch.float32).contiguous()
+
+
+def grid_quat_table(grid: SO3Grid, dev) -> torch.Tensor:
+    """``SO3Grid.index_to_quat`` of every cell as a (C, 4) float32 device tensor"""
+    return torch.tensor(np.stack([np.asarray(grid.index_to_quat(i), dtype=np.float64) for i in range(grid.num_cells())]),
+                        dtype=torch.float32, device=dev).contiguous()
 
 
 class _Layer:
@@ -156,11 +164,96 @@ class SDFPoseNet:
             orientation = orientation / torch.sqrt(torch.sum(orientation ** 2, 1, keepdim=True))
         return out[:, 0:sd], out[:, sd:sd + 3], out[:, sd + 3], orientation
 
+    def _rows(self, layer: _Layer, koff: int, x: torch.Tensor, k: int, bn: bool, relu: bool) -> torch.Tensor:
+        """``_vec`` on the N rows of x (N, >= k): (N, cout)"""
+        N = x.shape[0]
+        y = torch.empty((N, layer.cout), dtype=torch.float32, device=self.dev)
+        rc = self.L.sdfr_linear_rows(layer.w.data_ptr(), layer.cin_total, koff, x.data_ptr(), x.shape[1], k,
+                                     layer.b.data_ptr(), layer.scale.data_ptr() if bn else None,
+                                     layer.shift.data_ptr() if bn else None, int(relu), y.data_ptr(), layer.cout,
+                                     layer.cout, N, self.dev.index, self._st())
+        _lib.check(rc, "sdfr_linear_rows")
+        return y
+
+    def features_batch(self, points: torch.Tensor, counts=None) -> torch.Tensor:
+        """VanillaPointNet.forward on N sets (N, M, in_size) -> (N, C_last): one launch per per-point layer, one
+        ``sdfr_linear_rows`` per dense link, no synchronisation.  `counts` (int tensor or list, N entries): the real
+        points of every set -- rows past counts[n] are ignored, a set without points gets a zero feature.  Row n equals
+        ``features(points[n, :counts[n]])`` bit for bit."""
+        x = points.to(device=self.dev, dtype=torch.float32).contiguous()
+        if x.dim() != 3 or x.shape[2] != self.in_size or x.shape[0] < 1 or x.shape[1] < 1:
+            raise RuntimeError(f"points must have shape (N >= 1, M >= 1, {self.in_size})")
+        N, M = x.shape[0], x.shape[1]
+        cnt = None
+        if counts is not None:
+            cnt = torch.as_tensor(counts).to(device=self.dev, dtype=torch.int32).contiguous()
+            if cnt.shape != (N,):
+                raise RuntimeError(f"counts must have {N} entries")
+        F, F_width = x, self.in_size          # as in `features`; G is (N, width): one broadcast part per set
+        G = None
+        prev_width = self.in_size
+        n = len(self.pn)
+        for i, layer in enumerate(self.pn):
+            last = i == n - 1
+            if layer.cin_total != F_width + (G.shape[1] if G is not None else 0):
+                raise RuntimeError("state dict does not match the backbone configuration")
+            cvec = self._rows(layer, F_width, G, G.shape[1], False, False) if G is not None else layer.b
+            out_width = layer.cout * (2 if (self.dense and not last) else 1)
+            use_res = self.residual and prev_width == out_width
+            colmax = torch.empty((N, layer.cout), dtype=torch.float32, device=self.dev)
+            # the last layer stores nothing but its maxima: with a residual the kernel pools resid + Y itself
+            Y = torch.empty((N, M, layer.cout), dtype=torch.float32, device=self.dev) if not last else None
+            res_F = None
+            if use_res and F_width == layer.cout:
+                res_F = F
+            elif use_res:
+                res_F = torch.cat([F, G[:, None, :].expand(-1, M, -1)], dim=2).contiguous()
+            rc = self.L.sdfr_pointnet_layer_batch(
+                F.data_ptr(), cnt.data_ptr() if cnt is not None else None, N, M, F_width, F.shape[2], layer.w.data_ptr(),
+                layer.cin_total, cvec.data_ptr(), layer.cout if G is not None else 0, layer.scale.data_ptr(),
+                layer.shift.data_ptr(), res_F.data_ptr() if res_F is not None else None,
+                Y.data_ptr() if Y is not None else None, layer.cout, layer.cout, int(last and use_res),
+                colmax.data_ptr(), self.dev.index, self._st())
+            _lib.check(rc, "sdfr_pointnet_layer_batch")
+            if last:
+                return colmax
+            if self.dense:
+                G = colmax + G if (use_res and G is not None) else colmax
+            else:
+                G = None
+            F, F_width, prev_width = Y, layer.cout, out_width
+        raise AssertionError
+
+    def rows_batch(self, points: torch.Tensor, counts=None) -> torch.Tensor:
+        """the head's output rows (N, L + 4 + C) or (N, L + 8) -- the quaternion before its normalisation -- of N sets:
+        what ``sdfr_pose_metrics`` reads"""
+        out = self.features_batch(points, counts)
+        for layer in self.head:
+            out = self._rows(layer, 0, out, layer.cin_total, True, True)
+        return self._rows(self.final, 0, out, self.final.cin_total, False, False)
+
+    def forward_batch(self, points: torch.Tensor, counts=None):
+        """SDFPoseNet.forward on a batch (N, M, in_size): (latent (N,L), position (N,3), scale (N,), orientation (N,4)
+        normalised quaternion or (N,C) logits)."""
+        out = self.rows_batch(points, counts)
+        sd = self.shape_dimension
+        orientation = out[:, sd + 4:]
+        if self.orientation_repr == "quaternion":
+            orientation = orientation / torch.sqrt(torch.sum(orientation ** 2, 1, keepdim=True))
+        return out[:, 0:sd], out[:, sd:sd + 3], out[:, sd + 3], orientation
+
+    def grid_quats(self) -> Optional[torch.Tensor]:
+        """the orientation of every cell (C, 4) on the device, built once; None for the quaternion head"""
+        if self.grid is not None and getattr(self, "_grid_quats", None) is None:
+            self._grid_quats = grid_quat_table(self.grid, self.dev)
+        return self._grid_quats if self.grid is not None else None
+
     def __call__(self, points: torch.Tensor):
-        """SDFPoseNet.forward for a batch of one point set: (1,M,3) or (M,3)."""
+        """SDFPoseNet.forward: (N,M,3), or one point set as (1,M,3) or (M,3) (the estimator's use,
+        simple_setup.py:786-787: the single-set kernels)."""
         if points.dim() == 3:
             if points.shape[0] != 1:
-                raise NotImplementedError("one point set per call (the estimator's use, simple_setup.py:786-787)")
+                return self.forward_batch(points)
             points = points[0]
         return self.head_forward(self.features(points))
 

@@ -9,8 +9,12 @@ reference's ``parameters()`` order, the BatchNorm running statistics as a fifth,
 the trained state loads into the inference network unchanged (``net()``, ``init_network.SDFPoseNet``,
 ``SDFPipeline(init_state_dict=...)``).
 
+Validation (train.py:344-374, :439-481): ``validation_set`` draws a fixed set once, ``validate`` runs the current state
+under eval() over it -- ``SDFPoseNet.forward_batch`` and ``sdfr_pose_metrics`` (csrc/initnet_eval.hip),
+one host read per set -- and ``geodesic_distance`` is the per-iteration metric of the training batch.
+
 What the reference's loop has and this one does not: the other backbones, the NOCS / Redwood datasets and their mixing,
-validation metrics, wandb and the visualisations.
+wandb and the visualisations.
 """
 import ctypes
 from typing import Dict, List, Mapping, Optional
@@ -20,13 +24,14 @@ import torch
 
 from . import _lib
 from .differentiable_renderer import _stream
-from .init_network import SDFPoseNet
+from .init_network import SDFPoseNet, grid_quat_table
 from .so3grid import SO3Grid
 
 TERMS = ("latent", "position", "scale", "orientation", "total")
 WEIGHTS = ("latent_weight", "position_weight", "scale_weight", "orientation_weight")
 _DEFAULTS = {"iterations": 1000000, "batch_size": 32, "learning_rate": 1e-3}
 _TARGETS = ("latent_shape", "position", "scale", "orientation")
+RECORD = ("position", "scale", "geodesic", "nll", "count")      # the fp64 record of sdfr_pose_metrics
 
 
 def check_config(config: Mapping) -> dict:
@@ -129,6 +134,48 @@ def read_checkpoint(path: str) -> dict:
 
 def _tensor(v):
     return v if isinstance(v, torch.Tensor) else torch.as_tensor(np.asarray(v))
+
+
+def _metrics_call(L, out: torch.Tensor, latent: int, cells: int, grid_quats, position, scale, quat, index,
+                  record: torch.Tensor) -> None:
+    dev, N = out.device, out.shape[0]
+    f32 = lambda t, shape: _tensor(t).to(device=dev, dtype=torch.float32).reshape(shape).contiguous()
+    position, scale, quat = f32(position, (N, 3)), f32(scale, (N,)), f32(quat, (N, 4))
+    if index is not None:
+        index = _tensor(index).to(device=dev, dtype=torch.int32).reshape(N).contiguous()
+    if record.dtype != torch.float64 or record.numel() != len(RECORD) or record.device != dev or not record.is_contiguous():
+        raise ValueError(f"record must be a contiguous float64 tensor of {len(RECORD)} elements on {dev}")
+    ws = torch.empty(L.sdfr_pose_metrics_workspace_bytes(N) // 8, dtype=torch.float64, device=dev)
+    rc = L.sdfr_pose_metrics(out.data_ptr(), N, out.shape[1], latent, cells,
+                             grid_quats.data_ptr() if grid_quats is not None else None, position.data_ptr(),
+                             scale.data_ptr(), quat.data_ptr(), index.data_ptr() if index is not None else None,
+                             record.data_ptr(), ws.data_ptr(), ws.numel() * 8, dev.index, _stream(dev))
+    _lib.check(rc, "sdfr_pose_metrics")
+
+
+def pose_metrics(net: SDFPoseNet, points: torch.Tensor, targets: Mapping, record: Optional[torch.Tensor] = None):
+    """``net.rows_batch(points)`` and ``sdfr_pose_metrics`` against `targets`: "position" (N, 3), "scale" (N,),
+    "quaternion" (N, 4) (a quaternion head also takes it from "orientation") and, for a discretized head, "orientation"
+    (N,) class indices (optional: without them no NLL).  Adds the batch to `record` (``RECORD``: four fp64 sums and the
+    sample count, on the device; default a new zero record) and returns it; nothing is read back."""
+    discretized = net.orientation_repr == "discretized"
+    quat = targets["quaternion"] if "quaternion" in targets else (None if discretized else targets["orientation"])
+    if quat is None:
+        raise KeyError("quaternion")
+    if record is None:
+        record = torch.zeros(len(RECORD), dtype=torch.float64, device=net.dev)
+    out = net.rows_batch(points)
+    cells = net.grid.num_cells() if discretized else 0
+    _metrics_call(net.L, out, net.shape_dimension, cells, net.grid_quats(), targets["position"], targets["scale"], quat,
+                  targets.get("orientation") if discretized else None, record)
+    return record
+
+
+def validation_keys(name: str, discretized: bool) -> list:
+    """the reference's names of the validation numbers (train.py:459-472), in ``RECORD``'s order"""
+    keys = [f"{name} validation mean position error / m", f"{name} validation mean scale error / m",
+            f"{name} validation mean geodesic_distance / rad"]
+    return keys + ([f"{name} validation orientation mean NLL"] if discretized else [])
 
 
 class SDFPoseNetTrainer:
@@ -237,8 +284,10 @@ class SDFPoseNetTrainer:
 
     def net(self) -> SDFPoseNet:
         """an inference network of the current state"""
-        return SDFPoseNet(self.config["backbone"], self.config["head"], self.latent_size, self.state_dict(),
-                          device=self.device)
+        net = SDFPoseNet(self.config["backbone"], self.config["head"], self.latent_size, self.state_dict(),
+                         device=self.device)
+        net._grid_quats = self._grid_quats()      # (the cells' table is built once per trainer, not per validate())
+        return net
 
     # ---- checkpoints -------------------------------------------------------------------------------------------------
     def save_checkpoint(self, path: str) -> None:
@@ -302,6 +351,12 @@ class SDFPoseNetTrainer:
                 raise ValueError(f"targets['orientation'] must have shape {(N,) if self.cells else (N, 4)}, "
                                  f"got {tuple(o.shape)}")
             b["index" if self.cells else "quat"].copy_(o)
+            b["has_quat"] = not self.cells or "quaternion" in targets
+            if self.cells and "quaternion" in targets:        # (only the metric reads it: geodesic_distance)
+                q = _tensor(targets["quaternion"])
+                if tuple(q.shape) != (N, 4):
+                    raise ValueError(f"targets['quaternion'] must have shape {(N, 4)}, got {tuple(q.shape)}")
+                b["quat"].copy_(q)
         cfg, L, h, st = self.config, self._L, self._h, _stream(self.device)
         p = lambda name: b[name].data_ptr()
         rc = L.sdfr_pose_trainer_forward(h, self._params.data_ptr(), self._stats.data_ptr(), p("points"), N, M,
@@ -344,6 +399,55 @@ class SDFPoseNetTrainer:
             self._tracked += 1
         return self._terms.clone()
 
+    # ---- metrics -----------------------------------------------------------------------------------------------------
+    def _grid_quats(self):
+        if self.cells and getattr(self, "_quat_table", None) is None:
+            self._quat_table = grid_quat_table(SO3Grid(self.config["head"]["orientation_grid_resolution"]), self.device)
+        return self._quat_table if self.cells else None
+
+    def geodesic_distance(self) -> torch.Tensor:
+        """The reference's "metric geodesic distance" (train.py:344-374) of the last ``step`` / ``loss_and_grad``: the
+        batch mean of 2 acos(|q . q*|) between the target quaternions and the predicted ones (the argmax cell's, or the
+        head's normalised), from the train-mode output rows the forward left, as a device scalar (float64).  Computed
+        only here; a discretized head needs ``targets["quaternion"]`` next to the class indices."""
+        if not self._batch:
+            raise RuntimeError("geodesic_distance() follows a step() or loss_and_grad()")
+        b = next(iter(self._batch.values()))
+        if not b.get("has_quat"):
+            raise KeyError("quaternion")
+        record = torch.zeros(len(RECORD), dtype=torch.float64, device=self.device)
+        _metrics_call(self._L, b["out"], self.latent_size, self.cells, self._grid_quats(), b["position"], b["scale"],
+                      b["quat"], None, record)
+        return record[2] / record[4]
+
+    def validation_set(self, generator, samples: int, max_points: int = 2500, seed: int = 0) -> list:
+        """`samples` valid samples of `generator` (a ``SDFVAEViewGenerator``), drawn once and collated into batches of
+        ``batch_size`` (the last may be smaller) by ``collate``'s subset rule under its own generator seeded with `seed`:
+        [(points (N, M, 3), targets)], the targets with "quaternion".  The set is fixed, so the numbers of ``validate``
+        at different iterations are comparable."""
+        if int(samples) < 1:
+            raise ValueError("a validation set needs at least one sample")
+        pending = []
+        while len(pending) < int(samples):
+            pending += self._valid_samples(generator.generate())
+        pending = pending[:int(samples)]
+        gen, bs = torch.Generator().manual_seed(int(seed)), int(self.config["batch_size"])
+        return [self._collate_samples(pending[i:i + bs], max_points, gen) for i in range(0, len(pending), bs)]
+
+    def validate(self, batches, name: str = "") -> dict:
+        """The reference's ``_compute_validation_metrics`` (train.py:439-481) over `batches` ([(points, targets)], as
+        ``validation_set`` returns): the current parameters and running statistics under eval() (``net()``), every
+        batch through ``pose_metrics`` into one device record, ONE host read at the end.  Returns the reference's keys
+        (``validation_keys``): each sum over the sample count.  The training state is not touched."""
+        net = self.net()
+        record = torch.zeros(len(RECORD), dtype=torch.float64, device=self.device)
+        for points, targets in batches:
+            pose_metrics(net, points, targets, record)
+        sums = record.tolist()
+        if sums[4] < 1:
+            raise ValueError("validate() needs at least one batch")
+        return {key: sums[i] / sums[4] for i, key in enumerate(validation_keys(name, bool(self.cells)))}
+
     # ---- batches -----------------------------------------------------------------------------------------------------
     def _collate_samples(self, samples: List[Dict], max_points: int, generator: Optional[torch.Generator]):
         gen = self._collate_gen if generator is None else generator
@@ -355,12 +459,15 @@ class SDFPoseNetTrainer:
             pick = torch.randperm(int(s["pointset"].shape[0]), generator=gen)[:M].to(s["pointset"].device)
             sets.append(s["pointset"][pick])
         targets = {k: torch.stack([s[k] for s in samples]) for k in _TARGETS}
+        if all("quaternion" in s for s in samples):      # (what the metrics compare with: geodesic_distance, validate)
+            targets["quaternion"] = torch.stack([s["quaternion"] for s in samples])
         return torch.stack(sets), targets
 
     @staticmethod
     def _valid_samples(batch: Mapping) -> List[Dict]:
         valid = batch["valid"].tolist()
-        return [dict({k: batch[k][b] for k in _TARGETS}, pointset=batch["pointset"][b], index=b)
+        keys = _TARGETS + (("quaternion",) if "quaternion" in batch else ())
+        return [dict({k: batch[k][b] for k in keys}, pointset=batch["pointset"][b], index=b)
                 for b in range(len(valid)) if valid[b]]
 
     def collate(self, batch: Mapping, max_points: int = 2500, generator: Optional[torch.Generator] = None):
@@ -376,14 +483,18 @@ class SDFPoseNetTrainer:
         return points, targets
 
     def fit(self, generator, iterations: Optional[int] = None, log_every: int = 100, callback=None,
-            max_points: int = 2500) -> int:
+            max_points: int = 2500, validation: Optional[Mapping] = None, validation_every: Optional[int] = None) -> int:
         """The reference's loop: batches of exactly ``batch_size`` valid samples of `generator` (a
         ``SDFVAEViewGenerator``; invalid samples are redrawn, what a ``generate()`` leaves over opens the next batch)
         until the iteration counter reaches `iterations` (default: the config's).  The loss terms are copied to the host
-        every `log_every` iterations only and given to ``callback(iteration, terms: dict)`` (default: print).  Returns
+        every `log_every` iterations only and given to ``callback(iteration, terms: dict)`` (default: print).
+        `validation` ({name: batches of ``validation_set``}) with `validation_every`: every that many iterations
+        ``validate`` runs over each set and its numbers join the dictionary (on such an iteration the callback is called
+        whether it is a logged one or not), and a logged iteration also carries "metric geodesic distance".  Returns
         the number of ``generate()`` calls."""
         total = int(self.config["iterations"]) if iterations is None else int(iterations)
         bs = int(self.config["batch_size"])
+        validating = bool(validation) and bool(validation_every)
         pending, calls = [], 0
         while self.iteration < total:
             while len(pending) < bs:
@@ -392,8 +503,15 @@ class SDFPoseNetTrainer:
             points, targets = self._collate_samples(pending[:bs], max_points, None)
             pending = pending[bs:]
             terms = self.step(points, targets)
-            if log_every and self.iteration % log_every == 0:
-                named = dict(zip(TERMS, terms.tolist()))
+            logged = bool(log_every) and self.iteration % log_every == 0
+            validated = validating and self.iteration % int(validation_every) == 0
+            if logged or validated:
+                named = dict(zip(TERMS, terms.tolist())) if logged else {}
+                if logged and validating:
+                    named["metric geodesic distance"] = float(self.geodesic_distance())
+                if validated:
+                    for name, batches in validation.items():
+                        named.update(self.validate(batches, name))
                 if callback is not None:
                     callback(self.iteration, named)
                 else:
