@@ -62,6 +62,7 @@
  *        sdfr_depth_to_points[_ordered|_shifted], sdfr_depth_points_workspace_bytes, sdfr_depth_centroid_workspace_bytes
  *        sdfr_pose_to_views[_objects], sdfr_views_to_pose_grad[_deferred], sdfr_decoder_backward_latent_deferred[_batch|_scaled], sdfr_decoder_forward_stage,
  *        sdfr_loop_tail, sdfr_loop_tail_fused, sdfr_loop_tail_objects, sdfr_adam_step, sdfr_point_constraint, sdfr_add_inplace
+ *        K objects with V views each: sdfr_volumes_replicate, sdfr_volumes_sum_views, sdfr_inlier_ratio_objects
  *        sdfr_depth_l1_loss[_workspace_bytes], sdfr_pc_l1_loss, sdfr_inlier_ratio, sdfr_nn_loss_forward / _backward
  *        sharded over ranks: sdfr_loop_view_records, sdfr_loop_tail_records, sdfr_inlier_counts_record,
  *        sdfr_inlier_update_record
@@ -626,6 +627,32 @@ SDFR_API int sdfr_loop_tail_objects(float* params, float* grads, float* exp_avg,
                            float* quat_c, float* inv_scale, float* scale_v, float* pc_loss,
                            const sdfr_decoder* decoder, const float* decoder_t_mid, float* latents, int device,
                            void* stream);
+
+/* Around that tail once an object has V > 1 views (pipeline.MultiObjectRenderAndCompare(views=V)): the render and sampler
+ * launches take one SDF volume per VIEW (sdf_view_stride) and leave one d/dSDF volume per view, the decoder and its VJP
+ * work per OBJECT.  Rows of n floats (n = R^3), object-major:
+ *   sdfr_volumes_replicate   src [K][n] -> dst [K V][n]:  dst[k V + v] = src[k]                      (bit copies)
+ *   sdfr_volumes_sum_views   src [K V][n] -> dst [K][n]:  dst[k] = ((src[k V] + src[k V + 1]) + ...) in fp32, v
+ *                            ascending: one fixed order per element, the same bits on every run
+ * One launch each over (chunks of a row, K); 16-byte accesses for every row that starts on a 16-byte boundary (all of
+ * them when n is a multiple of 4 and the buffers are aligned), float by float for the others.  K = 0 or n = 0: nothing is
+ * launched.  V < 1, K < 0 or K > 65535: SDFR_E_INVALID. */
+SDFR_API int sdfr_volumes_replicate(const float* src, float* dst, int K, int V, size_t n, int device, void* stream);
+SDFR_API int sdfr_volumes_sum_views(const float* src, float* dst, int K, int V, size_t n, int device, void* stream);
+
+/* sdfr_inlier_ratio (below) for the K objects of sdfr_loop_tail_objects, after it, in two launches whatever K is -- a
+ * count grid over (chunks of 1024 pixels, K) and K update workgroups; integer atomics only:
+ *   depth_input [K][H][W];  depth_estimate: image k starts at depth_estimate + k * estimate_stride floats (>= W H: with
+ *   V views per object the caller passes the LAST view of the [K][V][H][W] estimates, stride V W H; :463-470)
+ *   step [K], counts [K][2] (zero on the first call, left zero), history [K][max_history] (may be NULL),
+ *   state [K][3], params / best_params [K][n_params]
+ * Per object exactly sdfr_inlier_ratio: the same expression per pixel, integer counts, ratio = (float)inliers /
+ * (float)valid (0 / 0 stays NaN), history[k][step[k] - 1] written only for 1 <= step[k] <= max_history, a strictly larger
+ * ratio, or the first, copies row k of params.  K = 0: nothing is launched. */
+SDFR_API int sdfr_inlier_ratio_objects(const float* depth_input, const float* depth_estimate, size_t estimate_stride,
+                              int K, int W, int H, float relative_threshold, const int* step, int* counts,
+                              float* history, int max_history, float* state, const float* params, int n_params,
+                              float* best_params, int device, void* stream);
 
 /* ---- the loop sharded over ranks (one process per GPU) ------------------------------------------------
  * The reference's multi-view iteration is one Python loop over the views with ONE shared pose and ONE shared SDF

@@ -1151,20 +1151,35 @@ class FusedRenderAndCompare:
 
 
 class MultiObjectRenderAndCompare:
-    """K estimates optimised SIDE BY SIDE: the K detected objects of one frame -- each with its own depth image (the
-    frame masked by the object's instance mask), pose, scale, latent and Adam state -- go through ONE launch sequence
+    """K estimates optimised SIDE BY SIDE: the K detected objects of one frame -- each with its own depth images (the
+    frames masked by the object's instance masks), pose, scale, latent and Adam state -- go through ONE launch sequence
     per iteration.  The reference calls its pipeline once per object, one after the other (simple_setup.py:213-225), and
     a single estimate's iteration is a chain of ~13 dependent launches that leaves most of an MI355X idle (C5: 0.11 ms
-    per iteration whatever the object); here the decoder runs on K latents at once, the renderer and the sampler on K
+    per iteration whatever the object); here the decoder runs on K latents at once, the renderer and the sampler on K V
     views with one SDF each (``sdf_view_stride = R^3``), the decoder's VJP on the K gradient volumes, and the tail is K
-    workgroups (``sdfr_loop_tail_objects``).  Same arithmetic per object as :class:`FusedRenderAndCompare` (one view per
-    object, no point constraint, no inlier bookkeeping, "last_iteration" results); the objects share the camera.
+    workgroups (``sdfr_loop_tail_objects``).  Same arithmetic per object as :class:`FusedRenderAndCompare` in its
+    two-launch form; the objects share the camera list.  No point constraint.
 
-    Everything is allocated here; ``rebind`` takes the next frame's K images (point clouds at capacity, counts on the
+    views=V: every object is seen from the same V cameras.  All per-view buffers are object-major, view k V + v is object
+    k from camera v.  An iteration is then: decode K volumes -> ``sdfr_volumes_replicate`` to K V -> render and sampler on
+    K V views -> ``sdfr_volumes_sum_views`` back to K gradient volumes -> the batched deferred VJP -> the tail with V.  With
+    ``views == 1`` neither volume kernel is launched (the renderer reads the decoder's output, the VJP the renderer's).
+    Memory: K V volumes of SDF and twice that of d/dSDF (the plan keeps two gradient volumes per view), 4 R^3 bytes each.
+    track_inliers: the inlier bookkeeping of simple_setup.py:177-211 for every object, on its LAST view (:463-470), behind
+    the tail and inside the captured graphs (``sdfr_inlier_ratio_objects``: two launches whatever K is); default: on for
+    ``config["result_selection_strategy"] == "best_inlier_ratio"``.  ``inlier_history`` (K, max_iterations) and
+    ``best_estimates()`` hold a run's bookkeeping; the returned rows are the last iterate either way, as the reference's
+    are (:class:`_BestEstimate`).
+
+    Everything is allocated here; ``rebind`` takes the next frame's images (point clouds at capacity, counts on the
     device); ``__call__`` replays captured graphs."""
 
+    MAX_VIEWS = 64        # views per object the tail reduces (sdfr_loop_tail_objects)
+    MAX_LAUNCH = 65535    # objects x views of one launch
+
     def __init__(self, decoder, camera: Camera, config: Dict, objects: int, shape_optimization: bool = True,
-                 device="cuda", graph_iterations: int = 5, sdf_grad_mode: int = SDF_GRAD_EXACT):
+                 device="cuda", graph_iterations: int = 5, sdf_grad_mode: int = SDF_GRAD_EXACT, views: int = 1,
+                 track_inliers: Optional[bool] = None):
         from .differentiable_renderer import BatchRenderPlan
         self.L, self.check = _lib.lib(), _lib.check
         self.dec, self.cam, self.cfg = decoder, camera, config
@@ -1174,6 +1189,13 @@ class MultiObjectRenderAndCompare:
         K = self.K = int(objects)
         if K < 1:
             raise ValueError("objects must be >= 1")
+        V = self.V = int(views)
+        if V < 1 or V > self.MAX_VIEWS:
+            raise ValueError(f"views must be in [1, {self.MAX_VIEWS}] (the tail reduces an object's views in one "
+                             f"workgroup), got {views}")
+        B = self.B = K * V
+        if B > self.MAX_LAUNCH:
+            raise ValueError(f"{K} objects x {V} views exceed a launch ({self.MAX_LAUNCH} views)")
         self.shape_opt = bool(shape_optimization)
         self.graph_iterations = max(1, int(graph_iterations))
         H, W = int(camera.height), int(camera.width)
@@ -1192,58 +1214,93 @@ class MultiObjectRenderAndCompare:
         self.step = torch.zeros(K, **i32)
         self.z = torch.zeros((K, self.Lz), **f32)             # the latents, packed for the decoder
         self.g_z = torch.zeros((K, self.Lz), **f32)
-        self.cam_pos = torch.zeros((1, 3), **f32)
-        self.cam_quat = torch.tensor([[0.0, 0.0, 0.0, 1.0]], **f32)
-        self.target = torch.zeros((K, H, W), **f32)
+        self.cam_pos = torch.zeros((V, 3), **f32)
+        self.cam_quat = torch.tensor([[0.0, 0.0, 0.0, 1.0]], **f32).repeat(V, 1)
+        self.target = torch.zeros((B, H, W), **f32)           # [K][V] images
+        # (the bookkeeping reads K contiguous images: with V > 1 the objects' last views get a copy at rebind)
+        self.target_last = self.target if V == 1 else torch.zeros((K, H, W), **f32)
         self.max_pts = W * H
-        self.points = torch.zeros((K * W * H, 3), **f32)
-        self.offsets = torch.zeros(K + 1, **i32)
-        self.counts = torch.zeros(K, **i32)
-        self.ws_points = torch.empty(max(self.L.sdfr_depth_points_workspace_bytes(K, W, H), 256), **u8)
+        self.points = torch.zeros((B * W * H, 3), **f32)
+        self.offsets = torch.zeros(B + 1, **i32)
+        self.counts = torch.zeros(B, **i32)
+        self.ws_points = torch.empty(max(self.L.sdfr_depth_points_workspace_bytes(B, W, H), 256), **u8)
         self.sdf_grad_mode = int(sdf_grad_mode)     # SDF_GRAD_EXACT / SDF_GRAD_CUDA_COMPAT
-        self.plan = BatchRenderPlan(R, K, camera, device=self.dev, per_view_sdf=True, close_views=False,
+        self.plan = BatchRenderPlan(R, B, camera, device=self.dev, per_view_sdf=True, close_views=False,
                                     sdf_grad_mode=self.sdf_grad_mode)
-        self.pos_c = torch.empty((K, 3), **f32)
-        self.quat_c = torch.empty((K, 4), **f32)
-        self.inv_scale = torch.empty((K,), **f32)
-        self.scale_v = torch.empty((K,), **f32)
-        self.loss_pc = torch.zeros((K,), **f32)
-        self.sdf = torch.empty((K, 1, R, R, R), **f32)
+        self.pos_c = torch.empty((B, 3), **f32)
+        self.quat_c = torch.empty((B, 4), **f32)
+        self.inv_scale = torch.empty((B,), **f32)
+        self.scale_v = torch.empty((B,), **f32)
+        self.loss_pc = torch.zeros((B,), **f32)
+        self.sdf_objects = torch.empty((K, 1, R, R, R), **f32)      # what the decoder writes
+        self.sdf = self.sdf_objects if V == 1 else torch.empty((B, 1, R, R, R), **f32)     # what the views read
+        self.g_sdf_objects = torch.empty((K, R, R, R), **f32) if (V > 1 and self.shape_opt) else None
         self.tape = torch.empty(max(self.L.sdfr_decoder_tape_bytes(decoder._h, K), 256), **u8)
         self.ws_dec = torch.empty(max(self.L.sdfr_decoder_workspace_bytes(decoder._h, K),
                                       self.L.sdfr_decoder_backward_workspace_bytes(decoder._h, K), 256), **u8)
-        self.ws_pc = torch.empty(max(self.L.sdfr_pc_loss_backward_workspace_bytes(K, self.max_pts), 256), **u8)
-        self.defer_loss = K < 32
+        self.ws_pc = torch.empty(max(self.L.sdfr_pc_loss_backward_workspace_bytes(B, self.max_pts), 256), **u8)
+        self.defer_loss = B < 32
+        self.strategy = _selection_strategy(config)
+        self.track_inliers = (self.strategy == "best_inlier_ratio") if track_inliers is None else bool(track_inliers)
+        self.rel_thr = float(config.get("relative_inlier_threshold", 0.03))
+        # the bookkeeping's state in ONE buffer, [counts K x 2 (int; first: each pair 8-byte aligned, one atomic adds both)
+        # | history K x max_iterations | best state K x 3 | best parameters K x n]: one fill resets a run
+        self.max_history = int(config["max_iterations"])
+        mh = max(self.max_history, 1)
+        self._inliers_state = torch.zeros(K * (2 + mh + 3 + n), **f32)
+        self.inlier_counts = self._inliers_state[0:K * 2].view(torch.int32).view(K, 2)
+        o = K * 2
+        self.inlier_history = self._inliers_state[o:o + K * mh].view(K, mh); o += K * mh
+        self.best_state = self._inliers_state[o:o + K * 3].view(K, 3); o += K * 3     # ratio, 1-based iteration, has_best
+        self.best_params = self._inliers_state[o:o + K * n].view(K, n)
         self.graph = self.graph_many = None
         self.bound = False
 
     def _stream(self):
         return torch.cuda.current_stream(self.dev).cuda_stream
 
-    def rebind(self, depth_images: torch.Tensor, camera_position: Optional[torch.Tensor] = None,
-               camera_orientation: Optional[torch.Tensor] = None, masks: Optional[torch.Tensor] = None,
+    def rebind(self, depth_images: torch.Tensor, camera_positions: Optional[torch.Tensor] = None,
+               camera_orientations: Optional[torch.Tensor] = None, masks: Optional[torch.Tensor] = None,
                far_field: Optional[float] = None) -> "MultiObjectRenderAndCompare":
-        """depth_images (K,H,W): one image per object (``masks`` / ``far_field``: preprocessed in place on the way,
-        simple_setup.py:671-693).  camera_position (3,) / camera_orientation (4,): the one camera all objects are seen
-        from (default: the origin)."""
-        if tuple(depth_images.shape) != (self.K, self.H, self.W):
-            raise ValueError(f"depth_images must have shape {(self.K, self.H, self.W)}, got {tuple(depth_images.shape)}")
+        """The next observation.  depth_images is either
+          (V,H,W)    the V frames, with masks (K,V,H,W) (or (K,H,W) for one view): ``target[k, v]`` = frame v under mask
+                     (k, v); the frames are NOT modified; or
+          (K,H,W) / (K,V,H,W)   one image per object and view already (``masks`` / ``far_field``: preprocessed IN PLACE on
+                     the way, simple_setup.py:671-693).
+        (With K == V a (K,H,W) tensor is read as V frames only when the masks are 4-D.)  camera_positions (V,3) /
+        camera_orientations (V,4): the cameras every object is seen from (default: the origin)."""
+        K, V, B, H, W = self.K, self.V, self.B, self.H, self.W
+        shape = tuple(depth_images.shape)
+        frames = shape == (V, H, W) and (V > 1 or shape != (K, H, W) or (masks is not None and masks.dim() == 4))
+        if not frames and shape != (K, V, H, W) and not (V == 1 and shape == (K, H, W)):
+            raise ValueError(f"depth_images must have shape {(V, H, W)} (frames), {(K, H, W)} or {(K, V, H, W)}, "
+                             f"got {shape}")
+        if masks is not None and masks.numel() != B * H * W:
+            raise ValueError(f"masks must have shape {(K, V, H, W)}, got {tuple(masks.shape)}")
         with torch.no_grad():
-            if masks is not None or far_field is not None:
-                preprocess_depth(depth_images, masks, far_field, copy_to=(self.target, 0, self.K))
+            if frames:     # every object its own copy of every frame
+                images = depth_images.to(device=self.dev, dtype=torch.float32)[None].repeat(K, 1, 1, 1).view(B, H, W)
             else:
-                self.target.copy_(depth_images)
-            if camera_position is None:
+                images = depth_images.view(B, H, W) if depth_images.is_contiguous() else depth_images.reshape(B, H, W)
+            if masks is not None or far_field is not None:
+                preprocess_depth(images, masks.reshape(B, H, W) if masks is not None else None, far_field,
+                                 copy_to=(self.target, 0, B))
+            else:
+                self.target.copy_(images)
+            if V > 1:
+                self.target_last.copy_(self.target.view(K, V, H, W)[:, V - 1])
+            if camera_positions is None:
                 self.cam_pos.zero_()
             else:
-                self.cam_pos.copy_(camera_position.reshape(1, 3))
-            if camera_orientation is None:
-                self.cam_quat.copy_(torch.tensor([[0.0, 0.0, 0.0, 1.0]]))
+                self.cam_pos.copy_(camera_positions.reshape(V, 3))
+            if camera_orientations is None:
+                self.cam_quat.zero_()
+                self.cam_quat[:, 3] = 1.0
             else:
-                self.cam_quat.copy_(camera_orientation.reshape(1, 4))
+                self.cam_quat.copy_(camera_orientations.reshape(V, 4))
             fx, fy, cx0, cy0, _ = self.cam.get_pinhole_camera_parameters(0.0)
             self.check(self.L.sdfr_depth_to_points_resident(
-                self.target.data_ptr(), self.K, self.W, self.H, _lib.ABI["SDFR_POINT_ORDER_TILED"], 1.0 / fx,
+                self.target.data_ptr(), B, self.W, self.H, _lib.ABI["SDFR_POINT_ORDER_TILED"], 1.0 / fx,
                 1.0 / fy, cx0, cy0, self.counts.data_ptr(), self.offsets.data_ptr(), self.ws_points.data_ptr(),
                 self.ws_points.numel(), self.points.data_ptr(), self.dev.index, self._stream()),
                 "sdfr_depth_to_points_resident")
@@ -1252,15 +1309,18 @@ class MultiObjectRenderAndCompare:
 
     def _decode(self, st, with_tape):
         # (self.z holds the current latents, packed: sdfr_pose_to_views_objects at the start of a run, the tail after)
-        self.check(self.L.sdfr_decoder_forward(self.dec._h, self.z.data_ptr(), self.K, 0, self.sdf.data_ptr(),
+        self.check(self.L.sdfr_decoder_forward(self.dec._h, self.z.data_ptr(), self.K, 0, self.sdf_objects.data_ptr(),
                                                self.tape.data_ptr() if with_tape else None, self.ws_dec.data_ptr(),
                                                self.ws_dec.numel(), st), "sdfr_decoder_forward")
+        if self.V > 1:     # one volume per view: view k V + v reads object k's
+            self.check(self.L.sdfr_volumes_replicate(self.sdf_objects.data_ptr(), self.sdf.data_ptr(), self.K, self.V,
+                                                     self.R ** 3, self.dev.index, st), "sdfr_volumes_replicate")
 
     def _poses_to_views(self, st):
-        """every object's pose in the camera's frame (simple_setup.py:411, :424-430), once per run: the tail leaves the
+        """every object's pose in every camera's frame (simple_setup.py:411, :424-430), once per run: the tail leaves the
         NEXT iteration's"""
         self.check(self.L.sdfr_pose_to_views_objects(
-            self.params.data_ptr(), self.n, self.K, self.cam_pos.data_ptr(), self.cam_quat.data_ptr(), 1,
+            self.params.data_ptr(), self.n, self.K, self.cam_pos.data_ptr(), self.cam_quat.data_ptr(), self.V,
             self.pos_c.data_ptr(), self.quat_c.data_ptr(), self.inv_scale.data_ptr(), self.scale_v.data_ptr(),
             self.z.data_ptr(), self.dev.index, st), "sdfr_pose_to_views_objects")
 
@@ -1276,6 +1336,10 @@ class MultiObjectRenderAndCompare:
                                          weight=self.cfg["depth_weight"], pc_weight=self.cfg["pc_weight"])
         t_mid = ctypes.c_void_p()
         if self.shape_opt:
+            if self.V > 1:     # an object's d loss / d SDF is the sum over its views
+                self.check(L.sdfr_volumes_sum_views(g_sdf.data_ptr(), self.g_sdf_objects.data_ptr(), self.K, self.V,
+                                                    self.R ** 3, d, st), "sdfr_volumes_sum_views")
+                g_sdf = self.g_sdf_objects
             # the VJP without its last stage: workgroup k of the tail finishes object k's (one launch and a copy less)
             self.check(L.sdfr_decoder_backward_latent_deferred_batch(
                 self.dec._h, self.z.data_ptr(), self.tape.data_ptr(), g_sdf.data_ptr(), self.K, self.ws_dec.data_ptr(),
@@ -1283,22 +1347,39 @@ class MultiObjectRenderAndCompare:
         self.check(L.sdfr_loop_tail_objects(
             self.params.data_ptr(), self.grads.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.step.data_ptr(),
             self.n, self.K, 1e-3, 1e-2, 1e-3, 1e-2, int(self.shape_opt), self.cam_pos.data_ptr(), self.cam_quat.data_ptr(),
-            1, self.plan.workspace.data_ptr(), self.plan.partials_offset, self.W, self.H, self.ws_pc.data_ptr(),
+            self.V, self.plan.workspace.data_ptr(), self.plan.partials_offset, self.W, self.H, self.ws_pc.data_ptr(),
             self.offsets.data_ptr(), self.max_pts, self.pos_c.data_ptr(), self.quat_c.data_ptr(),
             self.inv_scale.data_ptr(), self.scale_v.data_ptr(), self.loss_pc.data_ptr(),
             self.dec._h if self.shape_opt else None, t_mid if self.shape_opt else None, self.z.data_ptr(), d, st),
             "sdfr_loop_tail_objects")
+        if self.track_inliers:
+            # :463-470 -- every object's LAST view: its input and the estimate rendered before this step, against the
+            # parameters after it
+            npix = self.W * self.H
+            self.check(L.sdfr_inlier_ratio_objects(
+                self.target_last.data_ptr(), self.plan.depth.data_ptr() + 4 * (self.V - 1) * npix, self.V * npix, self.K,
+                self.W, self.H, self.rel_thr, self.step.data_ptr(), self.inlier_counts.data_ptr(),
+                self.inlier_history.data_ptr(), self.max_history, self.best_state.data_ptr(), self.params.data_ptr(),
+                self.n, self.best_params.data_ptr(), d, st), "sdfr_inlier_ratio_objects")
 
     def view_losses(self):
-        """(depth loss, point-cloud loss) of every object in the last iteration, (K,) each"""
+        """(depth loss, point-cloud loss) of every object and view in the last iteration, (K V,) each, object-major"""
         return self.plan.loss, self.loss_pc
+
+    def last_view_depth(self) -> torch.Tensor:
+        """the K images the last iteration rendered of the objects' last views (what the bookkeeping compared), a view
+        of the plan's depth buffer"""
+        return self.plan.depth.view(self.K, self.V, self.H, self.W)[:, self.V - 1]
 
     def __call__(self, position, orientation, scale, latent, use_graph: bool = True, history: Optional[List] = None):
         """position (K,3), orientation (K,4), scale (K,), latent (K,L): the initial estimates (or ``params=`` rows from
-        ResidentInit).  Returns the optimised (position (K,3), orientation (K,4), scale (K,), latent (K,L))."""
+        ResidentInit).  Returns the optimised (position (K,3), orientation (K,4), scale (K,), latent (K,L)).
+        history: one entry per iteration -- ``loss_depth`` / ``loss_pc`` (K V,), ``params`` (K,n) and, with the inlier
+        bookkeeping, ``depth`` (K,H,W: the last views as just rendered) and ``inlier_ratio`` (K,)."""
         if not self.bound:
             raise RuntimeError("no observation bound: call rebind(depth_images, ...) first")
         K = self.K
+        state = (self.params, self._zeroed, self.step) + ((self._inliers_state,) if self.track_inliers else ())
         with torch.no_grad():
             self.params[:, 0:3] = position.reshape(K, 3)
             self.params[:, 3:7] = orientation.reshape(K, 4)
@@ -1306,13 +1387,15 @@ class MultiObjectRenderAndCompare:
             self.params[:, 8:] = latent.reshape(K, self.Lz)
             self._zeroed.zero_()
             self.step.zero_()
+            if self.track_inliers:
+                self._inliers_state.zero_()
         st = self._stream()
         self._poses_to_views(st)        # (also packs the latents for the decoder)
         if not self.shape_opt:
             self._decode(st, False)
         n_iter = self.cfg["max_iterations"]
         if use_graph and self.graph is None:
-            saved = [t.clone() for t in (self.params, self._zeroed, self.step)]
+            saved = [t.clone() for t in state]
             side = torch.cuda.Stream(self.dev)
             side.wait_stream(torch.cuda.current_stream(self.dev))
             with torch.cuda.stream(side):
@@ -1326,7 +1409,7 @@ class MultiObjectRenderAndCompare:
                 with torch.cuda.graph(self.graph_many):
                     for _ in range(self.graph_iterations):
                         self.iteration()
-            for t, c in zip((self.params, self._zeroed, self.step), saved):
+            for t, c in zip(state, saved):
                 t.copy_(c)
             self._poses_to_views(self._stream())     # (the warm-up's tail left the poses of ITS updated parameters)
         done = 0
@@ -1334,13 +1417,29 @@ class MultiObjectRenderAndCompare:
             for _ in range(n_iter // self.graph_iterations):
                 self.graph_many.replay()
             done = n_iter - n_iter % self.graph_iterations
-        for _ in range(n_iter - done):
+        for it in range(done, n_iter):
             if use_graph:
                 self.graph.replay()
             else:
                 self.iteration()
             if history is not None:
                 ld, lp = self.view_losses()
-                history.append({"loss_depth": ld.clone(), "loss_pc": lp.clone(), "params": self.params.clone()})
+                entry = {"loss_depth": ld.clone(), "loss_pc": lp.clone(), "params": self.params.clone()}
+                if self.track_inliers:
+                    entry["depth"] = self.last_view_depth().clone()
+                    entry["inlier_ratio"] = self.inlier_history[:, it].clone()
+                history.append(entry)
         p = self.params
         return p[:, 0:3].clone(), p[:, 3:7].clone(), p[:, 7].clone(), p[:, 8:].clone()
+
+    def best_estimates(self):
+        """K entries (ratio, 1-based iteration, (position (1,3), orientation (1,4), scale (1,), latent (1,L))): every
+        object's parameters at its best inlier ratio of the last run (strictly greater wins, the first counts:
+        simple_setup.py:203-210), as ``FusedRenderAndCompare.best_estimate``; None without ``track_inliers``; an object's
+        entry is None before its first iteration."""
+        if not self.track_inliers:
+            return None
+        out = []
+        for (ratio, it, has), bp in zip(self.best_state.tolist(), self.best_params.clone()):
+            out.append((ratio, int(it), (bp[0:3][None], bp[3:7][None], bp[7:8], bp[8:][None])) if has else None)
+        return out

@@ -105,7 +105,7 @@ class SDFPipeline:
         # (init_network.ResidentInit) where its architecture allows; False: the host-driven nn_init (two host reads)
         self._resident_wanted = bool(resident_init)
         self._residents = {}
-        self._multi_loops, self._resident_objects = {}, {}     # estimate_objects: per (K, shape_optimization) / per K
+        self._multi_loops, self._resident_objects = {}, {}     # estimate_objects: per (K, shape_optimization, V, tracking) / per (K, V)
         self._ignored_warned = False
 
     def _parse_config(self, config: Dict) -> None:
@@ -277,68 +277,98 @@ class SDFPipeline:
         # self.best_estimate()
         return position, orientation, scale, latent_shape
 
-    def estimate_objects(self, depth_image: torch.Tensor, masks: torch.Tensor,
-                         camera_position: Optional[torch.Tensor] = None,
-                         camera_orientation: Optional[torch.Tensor] = None, shape_optimization: bool = True,
+    def estimate_objects(self, depth_images: torch.Tensor, masks: torch.Tensor,
+                         camera_positions: Optional[torch.Tensor] = None,
+                         camera_orientations: Optional[torch.Tensor] = None, shape_optimization: bool = True,
                          prior_orientation_distribution: Optional[torch.Tensor] = None,
                          training_orientation_distribution: Optional[torch.Tensor] = None) -> tuple:
         """The K detected objects of ONE frame at once: what a caller of the reference does with a loop of K
         ``pipeline(depth, mask_k, color)`` calls (one per instance mask), as one call whose K estimates are optimised side
         by side (``pipeline.MultiObjectRenderAndCompare``: one launch sequence per iteration for all of them).
 
-        depth_image (H,W): the frame (NOT modified: every object gets its own masked copy); masks (K,H,W) bool: the
-        instance masks; camera_position (3,) / camera_orientation (4,): the camera in the world (default: the origin);
+        depth_images (H,W): the frame (NOT modified: every object gets its own masked copy); masks (K,H,W) bool: the
+        instance masks; camera_positions (3,) / camera_orientations (4,): the camera in the world (default: the origin).
+        Or SEVERAL views of the same K objects (two cameras, or one that moved), as ``__call__`` takes them: depth_images
+        (V,H,W), masks (K,V,H,W), camera_positions (V,3), camera_orientations (V,4) -- every view needs every object in it.
+        The initialisation network sees each object's first view (``init_view: first``, camera 0); ``init_view: best``
+        with V > 1 is not implemented.
         prior_orientation_distribution (K,C) / training_orientation_distribution (C,): as in ``__call__``, one row per
         object.  Returns position (K,3), orientation (K,4), scale (K,), latent (K,L) -- row k follows what
-        ``pipeline(depth, masks[k], color)`` estimates for object k (`result_selection_strategy` "last_iteration") TO
+        ``pipeline(depth, masks[k], color, camera_positions=..., camera_orientations=...)`` estimates for object k TO
         ROUNDING, tested to 1 % of an Adam step per iteration: the single call runs its render pair as one launch
         (``FusedRenderAndCompare(fused_render=)``: the depth loss's weight / count multiplies sums instead of terms), and with
         shape optimisation a batch of latents takes other, equivalent decoder kernels than a single one (the direct
         convolution from 8 latents on, the tiled resize from 2, no split-K above 16).  Against the single loop in its
-        two-launch form the pose-only rows are BIT FOR BIT the same (tests/test_multi_object_gpu.py).  ``NoDepthError`` for an object without a valid depth pixel is raised AFTER the call's work was
+        two-launch form the pose-only rows are BIT FOR BIT the same (tests/test_multi_object_gpu.py).
+        The rows are the LAST iterate for both values of ``result_selection_strategy``, as ``__call__``'s are; with
+        "best_inlier_ratio" every object's inlier bookkeeping (:177-211, on its last view) runs beside the loop and
+        ``best_estimates()`` returns it.
+        ``NoDepthError`` for an (object, view) without a valid depth pixel is raised AFTER the call's work was
         enqueued (the counts are read behind the launches), where the reference raises before optimising (:780-781)."""
         dev = self._dev
-        if depth_image.dim() != 2 or masks.dim() != 3 or tuple(masks.shape[1:]) != tuple(depth_image.shape):
-            raise ValueError("depth_image (H,W) and masks (K,H,W) are expected")
+        if depth_images.dim() == 2 and masks.dim() == 3 and tuple(masks.shape[1:]) == tuple(depth_images.shape):
+            V = 1
+        elif (depth_images.dim() == 3 and masks.dim() == 4 and masks.shape[1] == depth_images.shape[0]
+              and tuple(masks.shape[2:]) == tuple(depth_images.shape[1:])):
+            V = int(depth_images.shape[0])
+        else:
+            raise ValueError("depth_images (H,W) and masks (K,H,W), or depth_images (V,H,W) and masks (K,V,H,W), "
+                             "are expected")
+        if V > 1 and self.config.get("init_view", "first") != "first":
+            raise NotImplementedError("estimate_objects with several views initialises from each object's first view "
+                                      f"(init_view: first), not init_view: {self.config.get('init_view')}")
         K = int(masks.shape[0])
-        key = (K, bool(shape_optimization))
+        track = self.result_selection_strategy == "best_inlier_ratio"
+        key = (K, bool(shape_optimization), V, track)
         loop = self._multi_loops.get(key)
         if loop is None:
             self._bounded(self._multi_loops, self.MAX_CACHED_LOOPS)
             loop = self._multi_loops[key] = MultiObjectRenderAndCompare(
                 self.vae, self.cam, self.config, K, shape_optimization=shape_optimization, device=dev,
-                sdf_grad_mode=self.sdf_grad_mode)
+                sdf_grad_mode=self.sdf_grad_mode, views=V, track_inliers=track)
         with torch.no_grad():
-            frames = depth_image.to(device=dev, dtype=torch.float32)[None].expand(K, -1, -1).contiguous()
-            loop.rebind(frames, camera_position, camera_orientation, masks=masks, far_field=self._far_field)
+            H, W = loop.H, loop.W
+            loop.rebind(depth_images.reshape(V, H, W), camera_positions, camera_orientations,
+                        masks=masks.reshape(K, V, H, W), far_field=self._far_field)
+            first = loop.target.view(K, V, H, W)[:, 0]     # every object's first view: K contiguous images
             resident = None
             if self._resident_wanted and self._nn_init_override is None and isinstance(self.init_network, SDFPoseNet):
-                if K not in self._resident_objects:
+                # (per (K, V): its captured sequence holds the addresses of K images V images apart)
+                if (K, V) not in self._resident_objects:
                     self._bounded(self._resident_objects, self.MAX_CACHED_LOOPS)
                     try:
-                        self._resident_objects[K] = ResidentInit(
+                        self._resident_objects[K, V] = ResidentInit(
                             self.init_network, self.cam, K, dict(self.config, init_view="first"),
                             normalize_pose=bool(self.init_config.get("normalize_pose", False)), objects=True)
                     except NotImplementedError:
-                        self._resident_objects[K] = None
-                resident = self._resident_objects[K]
+                        self._resident_objects[K, V] = None
+                resident = self._resident_objects[K, V]
             if resident is not None:
-                latent, position, scale, orientation = resident(loop.target, loop.cam_pos, loop.cam_quat,
+                latent, position, scale, orientation = resident(first, loop.cam_pos, loop.cam_quat,
                                                                 prior_orientation_distribution,
                                                                 training_orientation_distribution)
             else:     # the host-driven form, object by object
                 rows = []
                 for k in range(K):
                     prior = prior_orientation_distribution[k:k + 1] if prior_orientation_distribution is not None else None
-                    rows.append(self._nn_init(loop.target[k:k + 1], loop.cam_pos, loop.cam_quat, prior,
+                    rows.append(self._nn_init(first[k:k + 1], loop.cam_pos[0:1], loop.cam_quat[0:1], prior,
                                               training_orientation_distribution))
                 latent, position, scale, orientation = (torch.cat([r[i].reshape(1, -1) for r in rows]) for i in range(4))
                 scale = scale.reshape(K)
             out = loop(position, orientation, scale, latent)
+            self._last_multi_loop = loop
             if resident is not None and resident.empty_views():
                 raise NoDepthError
-        self._last_multi_loop = loop
+            if V > 1 and bool((loop.counts == 0).any()):     # (the initialisation saw the first views only)
+                raise NoDepthError
         return out
+
+    def best_estimates(self):
+        """K entries (ratio, 1-based iteration, (position, orientation, scale, latent)), one per object: the parameters
+        at each object's best inlier ratio in the last ``estimate_objects`` call (``result_selection_strategy ==
+        "best_inlier_ratio"``); None when that call did not keep the bookkeeping"""
+        loop = getattr(self, "_last_multi_loop", None)
+        return loop.best_estimates() if loop is not None else None
 
     def prepare(self, views: int = 1, shape_optimization: bool = True) -> "SDFPipeline":
         """Optional: build the loop for `views` images and capture its graphs NOW (on an empty observation) instead of
