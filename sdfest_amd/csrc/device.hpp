@@ -81,22 +81,30 @@ __device__ __forceinline__ void gather_cell(const float* __restrict__ src, int R
   c.v[4] = p10.lo; c.v[5] = p10.hi; c.v[6] = p11.lo; c.v[7] = p11.hi;
 }
 
-// Face records are stored x-major with 2 x 2 blocks in (y, z): a 64-byte chunk of the record array
-// holds the faces of a 2 x 2 neighbourhood, so the cells a wave touches in one step fall into fewer
-// chunks -- the gather unit costs ~2 cycles per distinct 64-byte chunk per load
-// (tools/microbench/gather_bench.hip).  Measured: forward 247.5 -> 232.3 us per 256 random views.
+// Face records are stored in 2 x 2 x 2 blocks: a 128-byte line of the record array holds the faces of a 2 x 2 x 2
+// neighbourhood of voxels, a 64-byte chunk those of a 2 x 2 neighbourhood in (y, z) -- the gather unit costs ~2 cycles
+// per distinct 64-byte chunk per load (tools/microbench/gather_bench.hip), and every line a load touches that the L1
+// does not hold is a round trip to L2.
+//   index = [ y >> 1 | z >> 1 | x | y & 1 | z & 1 ]
+// x keeps all its bits together, its lowest one on top of the block's (y, z) bits: the record of (x + 1, y, z) -- the
+// other face of the cell -- is ALWAYS the record 4 further on, in the same line for even x and in the next line for
+// odd x.  A sample's second load is the first one's address plus 64 bytes, no arithmetic of its own.
+// History: grid order until round 1; x-major with 2 x 2 blocks in (y, z), [x | y >> 1 | z >> 1 | y & 1 | z & 1], until
+// round 7 (forward 247.5 -> 232.3 us per 256 random views) -- a line was 1 x 2 x 4 records there and the two records of
+// a sample never shared one: 10.9 lines per wave-step over both loads against 8.5 for the 2 x 2 x 2 line
+// (tools/analysis/record_lines.py; LABNOTES appendix I has the measurement).
 // (Three arrays -- faces perpendicular to x, y, z, each view marching the one for its dominant
 // viewing axis so that the 2 x 2 blocks lie in the plane its rays sweep -- were built and measured:
 // 261 us.  12 MiB of records no longer fit the 4 MiB per-XCD L2.)
-// Hb = ceil(R/2) blocks per axis; one x-slab = 4 Hb^2 records.
-constexpr bool kRecordsBlocked = true;
-__host__ __device__ __forceinline__ int record_slab(int R) {
-  return kRecordsBlocked ? 4 * ((R + 1) >> 1) * ((R + 1) >> 1) : R * R;
+// Records exist for x < R and y, z < R - 1: R >> 1 blocks along y and z, (R + 1) >> 1 along x.  The array keeps the
+// size it always had, R * record_slab(R) records -- the blocks fill it exactly for even R and leave a tail for odd R
+// (8 Hx Hyz^2 = (R + 1) (R - 1)^2 < R (R + 1)^2).
+__host__ __device__ __forceinline__ int record_slab(int R) { return 4 * ((R + 1) >> 1) * ((R + 1) >> 1); }
+__host__ __device__ __forceinline__ int record_index(int x, int y, int z, int R) {
+  const int Hyz = R >> 1, X2 = ((R + 1) >> 1) * 2;
+  return (((((y >> 1) * Hyz + (z >> 1)) * X2 + x) << 2) | ((y & 1) << 1)) | (z & 1);
 }
-__device__ __forceinline__ int record_index(int x, int y, int z, int Hb) {
-  if (!kRecordsBlocked) return (x * (2 * Hb) + y) * (2 * Hb) + z;  // timing only: even R
-  return (((x * Hb + (y >> 1)) * Hb + (z >> 1)) << 2) | ((y & 1) << 1) | (z & 1);
-}
+constexpr int kRecordNextX = 4;   // record_index(x + 1, y, z, R) - record_index(x, y, z, R)
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 
@@ -130,21 +138,28 @@ __device__ __forceinline__ float march_sample(__amdgpu_buffer_rsrc_t src, int R,
   f32x2 a01, a23, b01, b23;  // corner pairs (z, z+1) at (x,y), (x,y+1), (x+1,y), (x+1,y+1)
   if (PACKED) {
     int rix;
-    if (!kRecordsBlocked) {
-      rix = lin;
-    } else if (RT > 0 && is_pow2(RT) && RT >= 4) {
-      // lin = [x | y5..y1 y0 | z5..z1 z0]  ->  record_index = [x | y5..y1 | z5..z1 | y0 | z0]
-      // as two bit-field inserts (the compiler expands the C form into and/and/and/or3)
+    if (RT > 0 && is_pow2(RT) && RT >= 4 && RT <= 64) {
+      // The three coordinates go into ONE float -> int conversion with x where record_index wants it, y's high bits
+      // where it wants them, and z on top (4 L <= 24 bits: exact):
+      //   w            = [ z5..z1 z0 | y5..y1 y0 | 0 .. 0 | x5..x0 | 0 0 ]      z at 3 L, y at 2 L, x at 2
+      //   w >> (2L-1)  = [            z5..z1 | z0 | y5..y1 | y0 | 0 ]            z5..z1 at L + 2, y0 at 1
+      //   record_index = [ y5..y1 | z5..z1 | x5..x0 | y0 | z0 ]
+      // one shift, one bit-field insert that takes (x5..x0, y5..y1) from w and everything else -- z5..z1, y0 and zeros:
+      // the shift has dropped what w holds above -- from w >> (2L-1), one bit-field extract for z0, and one add-and-
+      // shift that puts z0 in and scales to bytes: with the multiplication by 4 as many instructions as the 2 x 2
+      // order took (the compiler expands the C form of the insert into and/and/or).
       constexpr int L = __builtin_ctz(RT > 0 ? RT : 2);
-      constexpr int zhi = ((1 << L) - 2) << 1;  // where z5..z1 land
+      constexpr int from_w = (((1 << L) - 1) << 2) | (((1 << (L - 1)) - 1) << (2 * L + 1));
+      const int w = (int)fmaf(bz, (float)(1 << (3 * L)), fmaf(bxy.y, (float)(1 << (2 * L)), bxy.x * 4.0f));
       int t;
-      asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(t) : "s"(zhi), "v"(lin << 1), "v"(lin));  // VOP3: no literals
-      asm("v_bfi_b32 %0, 2, %1, %2" : "=v"(rix) : "v"(lin >> (L - 1)), "v"(t));
+      asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(t) : "s"(from_w), "v"(w), "v"(w >> (2 * L - 1)));  // VOP3: no literals
+      rix = t + (int)__builtin_amdgcn_ubfe(w, 3 * L, 1);   // (bit 0 of t is 0: v_add_lshl_u32 with the * 16 below)
     } else {
-      rix = record_index((int)bxy.x, (int)bxy.y, (int)bz, (Rr + 1) >> 1);
+      rix = record_index((int)bxy.x, (int)bxy.y, (int)bz, Rr);
     }
+    // the face at x + 1 is the record kRecordNextX further on (record_index): an immediate offset
     const i32x4 a = __builtin_amdgcn_raw_buffer_load_b128(src, rix * 16, 0, 0);
-    const i32x4 b = __builtin_amdgcn_raw_buffer_load_b128(src, rix * 16, record_slab(Rr) * 16, 0);
+    const i32x4 b = __builtin_amdgcn_raw_buffer_load_b128(src, rix * 16 + kRecordNextX * 16, 0, 0);
     a01 = f32x2{__int_as_float(a.x), __int_as_float(a.y)};
     a23 = f32x2{__int_as_float(a.z), __int_as_float(a.w)};
     b01 = f32x2{__int_as_float(b.x), __int_as_float(b.y)};

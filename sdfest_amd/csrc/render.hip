@@ -440,8 +440,10 @@ __global__ __launch_bounds__(256) void backward_prologue_kernel(
 // too: 8 MiB, 2.5 % slower -- it overflows the 4 MiB per-XCD L2).  Storage order: device.hpp,
 // record_index.
 // ---------------------------------------------------------------------------------------------
-// (A 2x2x2-blocked record order was measured: +10 integer ops per step, no gain -- the march is
-// bound by dependent-load latency, not by lines per access.  Records stay in grid order.)
+// (Round 1 measured a 2x2x2-blocked order at +10 integer ops per step and found no gain: the march then walked the
+// whole cube and was bound by dependent-load latency.  Since the may-hit box it is bound by the CU's vector-memory
+// path, where every line a gather sends to L2 counts, and the 2 x 2 x 2 order of device.hpp costs no instruction
+// more than the 2 x 2 one did.)
 // The launch's last 3R blocks compute the plane minima for the may-hit boxes (compute_view_setup);
 // the views are set up by the next launch, which needs them.
 // Plane minima for the one-launch prologue (R % 4 == 0, 16-byte aligned grid): 3R blocks, every thread a few
@@ -495,13 +497,17 @@ __device__ __forceinline__ void plane_min_fast_block(const float* __restrict__ s
   }
 }
 
-__device__ __forceinline__ void pack_cell(const float* __restrict__ sdf, int R, float4* __restrict__ cells, int lin) {
-  const int RR = R * R;
-  if (lin >= RR * R) return;
-  const int z = lin % R, y = (lin / R) % R;
-  if (y >= R - 1 || z >= R - 1) return;
-  const float* p = sdf + lin;
-  cells[record_index(lin / RR, y, z, (R + 1) >> 1)] = make_float4(p[0], p[1], p[R], p[R + 1]);
+// Thread `rix` writes record `rix` (the inverse of record_index): a wave stores 1 KiB of consecutive records and
+// gathers its corners from 16 x-planes of the grid, which the plane-minimum blocks have just pulled through L2.
+// (Thread = voxel, the grid read in order, would scatter a wave's records over 32 lines 4 KiB apart.)
+// The launches bring R^3 threads: at least as many as there are records (device.hpp).
+__device__ __forceinline__ void pack_cell(const float* __restrict__ sdf, int R, float4* __restrict__ cells, int rix) {
+  const int Hyz = R >> 1, X2 = ((R + 1) >> 1) * 2;
+  const int q = rix >> 2, x = q % X2, b = q / X2;
+  const int y = (b / Hyz) * 2 + ((rix >> 1) & 1), z = (b % Hyz) * 2 + (rix & 1);
+  if (x >= R || y >= R - 1 || z >= R - 1) return;
+  const float* p = sdf + ((size_t)x * R + y) * R + z;
+  cells[rix] = make_float4(p[0], p[1], p[R], p[R + 1]);
 }
 
 __global__ __launch_bounds__(256) void pack_cells_kernel(const float* __restrict__ sdf, int R,
