@@ -80,6 +80,9 @@
  *        sdfr_mesh_depth_workspace_bytes, sdfr_mesh_depth
  *   9. [unstable] MESH TO SDF: the signed distance volume of a triangle mesh (what the VAE is trained on and encodes)
  *        sdfr_mesh_sdf_workspace_bytes, sdfr_mesh_sdf
+ *  12. [unstable] NOCS ANNOTATION: pose and scale of a NOCS frame's objects (NOCSDataset's preprocessing)
+ *        sdfr_nocs_workspace_bytes, sdfr_nocs_count, sdfr_nocs_correspondences,
+ *        sdfr_similarity_ransac[_workspace_bytes], sdfr_nocs_sample_indices
  * (Within the file the groups follow the order in which the reference's code runs; every declaration carries the
  * reference file:line it replaces.)
  */
@@ -1264,6 +1267,91 @@ SDFR_API int sdfr_pose_trainer_loss(const sdfr_pose_trainer* trainer, const floa
 SDFR_API int sdfr_pose_trainer_backward(const sdfr_pose_trainer* trainer, const float* params, const float* points, int N,
                                         int M, const float* tape, const float* g_out, float* grads, void* workspace,
                                         size_t workspace_bytes, void* stream);
+
+/* ==== 12. NOCS ANNOTATION ===================================================================== */
+/* ---- pose and scale of the annotated objects of a NOCS frame (sdfest/initialization/datasets/nocs_dataset.py:673-712,
+ * nocs_utils.py:14-241): the NOCS-map points of an object are aligned to its back-projected depth points by a RANSAC
+ * over 100 five-point similarity fits and a final fit over the winner's inliers.  K objects per call, ragged through
+ * DEVICE offsets [K + 1] (long long) as sdfr_nn_query's.  Kernels only, on the caller's stream; no allocation, no host
+ * synchronisation; every result is written with ordinary vector stores.
+ *
+ * CORRESPONDENCES (:673-698), for the K mask ids of ONE frame.  depth [H][W] fp32 metres, mask [H][W] bytes (the
+ * instance ids), nocs [H][W][channels] bytes (channels 3 or 4; the first three are used), mask_ids [K] DEVICE ints.
+ * The valid pixels of object k are those with `(mask == mask_ids[k]) * depth != 0`, in ROW-MAJOR order (the order is
+ * part of the result: the RANSAC's samples index it).  For each,
+ *     source = (float(c) / 255 - 0.5,  float(c) / 255 - 0.5,  (1 - float(c) / 255) - 0.5)      (fp32, each step rounded)
+ *     target = ((col - cx0) * z * rfx,  (row - cy0) * z * rfy,  z)                              (OpenCV frame)
+ * with the pixel-centre-0 principal point and reciprocal focal lengths of sdfr_depth_to_points (the same expressions,
+ * y and z not negated).  Two calls because the caller sizes the output: sdfr_nocs_count writes counts [K] (DEVICE
+ * ints), max_depth [K] (the largest valid depth; 0 for an empty object) and its block counts into `workspace`; the
+ * caller forms offsets [K + 1] and passes the SAME inputs and workspace to sdfr_nocs_correspondences, which writes
+ * source / target rows offsets[k] ... of [capacity][3] floats.  A row outside [0, min(offsets[k + 1], capacity)) is
+ * not written.  The reference's rejections (:692-698: fewer than 30 points, a depth above 32) are the caller's, from
+ * counts and max_depth.  W H < 2^31 - 1024, 0 <= K <= 65535. */
+SDFR_API size_t sdfr_nocs_workspace_bytes(int W, int H, int K);   /* 0: invalid */
+SDFR_API int sdfr_nocs_count(const float* depth, const unsigned char* mask, int W, int H, const int* mask_ids, int K,
+                             int* counts, float* max_depth, void* workspace, size_t workspace_bytes, int device,
+                             void* stream);
+SDFR_API int sdfr_nocs_correspondences(const float* depth, const unsigned char* mask, const unsigned char* nocs,
+                                       int channels, int W, int H, float rfx, float rfy, float cx0, float cy0,
+                                       const int* mask_ids, int K, const long long* offsets, long long capacity,
+                                       const void* workspace, float* source, float* target, int device, void* stream);
+
+/* THE FIT: nocs_utils.estimate_similarity_transform for K correspondence sets.  source / target [total][3] of `dtype`
+ * (SDFR_NOCS_F32 or SDFR_NOCS_F64; NOCS data is fp32, the reference's own test passes fp64); object k owns rows
+ * offsets[k] ... offsets[k + 1] - 1, at most max_n of them.  offsets must be NON-DECREASING: the objects' rows may
+ * not overlap (overlapping objects share per-row scratch, and their results are undefined).  Offsets outside
+ * [0, total] are clamped, so nothing is read out of bounds whatever they hold; an object that has more than max_n rows
+ * after clamping is not fitted from a part of its rows, it answers SDFR_NOCS_TRUNCATED.  ALL arithmetic is fp64, as numpy's is from the moment the reference appends the homogeneous ones --
+ * the two thresholds included (numpy takes an fp32 input's norms in fp32; the difference is ~1e-7 relative).
+ *   sample_indices [K][SDFR_NOCS_HYPOTHESES][5] DEVICE ints: the five correspondences of every hypothesis, an INPUT
+ *   (the reference draws them with np.random.choice; sdfr_nocs_sample_indices below draws them on the device).
+ *   pass_t = 0.01 max(t / s, s / t) from the mean norms of target and source, stop_t = pass_t / 100.
+ *   Hypothesis i = the Umeyama fit of its five pairs; residual_i = sqrt(sum_n |target_n - T_i source_n|^2).
+ *   Selection = the reference's sequential loop (:111-131) replayed: j = the first iteration whose residual is below
+ *   stop_t (99 without one), the winner = the first strict minimum of residual_0..j starting from 1e10; only
+ *   iterations 0..j "ran": a zero source variance or a NaN covariance among THEM fails the object, later ones do not.
+ *   Inliers = the winner's |d_n| < pass_t (every point when no residual beat 1e10).  inlier_ratio keeps the
+ *   reference's quirk: np.count_nonzero(inlier_idx) counts inlier INDICES that are non-zero, so point 0 never counts
+ *   (:167-169); it is 0 when no residual beat 1e10.  Final fit = Umeyama over the inliers.
+ * Outputs, per object (DEVICE): position [3], rotation [3][3], scale, transform [4][4] (doubles, row-major; NaN unless
+ * status is SDFR_NOCS_OK), inlier_ratio (double), best_iteration (the winner, -1 without one), iterations_run (j + 1),
+ * status; inlier_mask [total] bytes (nullable).
+ *   SDFR_NOCS_OK          the four results are valid
+ *   SDFR_NOCS_NONE        the reference returns four None: fewer than 5 points, or inlier_ratio < 0.1
+ *   SDFR_NOCS_POSE_ERROR  the reference raises PoseEstimationError: zero source variance in a fit that ran (:226-229)
+ *   SDFR_NOCS_NAN_INPUT   the reference raises RuntimeError: a NaN covariance in a fit that ran (:211-215)
+ *   SDFR_NOCS_TRUNCATED   the object has more than max_n rows: the caller's max_n is too small (iterations_run 0)
+ * Every sum has a fixed order that depends on the object's own point count only: an object's results are the same bits
+ * alone, in any batch and at any place in it.  1 <= K <= 65535, 0 <= max_n <= total.  The workspace is 128-byte
+ * aligned. */
+#define SDFR_NOCS_HYPOTHESES 100
+#define SDFR_NOCS_F32 0
+#define SDFR_NOCS_F64 1
+#define SDFR_NOCS_OK 0
+#define SDFR_NOCS_NONE 1
+#define SDFR_NOCS_POSE_ERROR 2
+#define SDFR_NOCS_NAN_INPUT 3
+#define SDFR_NOCS_TRUNCATED 4
+SDFR_API size_t sdfr_similarity_ransac_workspace_bytes(int K, long long total, int max_n);   /* 0: invalid */
+SDFR_API int sdfr_similarity_ransac(const void* source, const void* target, int dtype, const long long* offsets,
+                                    long long total, int max_n, int K, const int* sample_indices, double* position,
+                                    double* rotation, double* scale, double* transform, double* inlier_ratio,
+                                    int* best_iteration, int* iterations_run, int* status, unsigned char* inlier_mask,
+                                    void* workspace, size_t workspace_bytes, int device, void* stream);
+
+/* sample_indices [K][SDFR_NOCS_HYPOTHESES][5]: five DISTINCT indices in [0, N_k), N_k = offsets[k + 1] - offsets[k],
+ * per hypothesis.  A stream of this library's own -- numpy's global Mersenne Twister stream, which the reference
+ * draws from, is NOT reproduced: Philox-4x32-10, key = the object's seed (object_seeds[k], DEVICE, or `seed` for every
+ * object when object_seeds is NULL), counter = {iteration, draw, attempt, 0x4E4F4353}; index = floor(word0 * N / 2^32);
+ * a draw equal to an earlier one of its row is drawn again with attempt + 1 (after 64 attempts: the smallest index
+ * not yet in the row).  An object's place in the batch is not part of the stream: the same seed and N give the same
+ * rows.  N_k < 5: the rows are zeros (the fit answers SDFR_NOCS_NONE without reading them).  N_k is taken from the
+ * offsets as they are, not clamped to a buffer or to the fit's max_n: the fit clamps every index it reads into the
+ * object's rows, and an object it truncates answers SDFR_NOCS_TRUNCATED, so such rows never reach a result. */
+SDFR_API int sdfr_nocs_sample_indices(const long long* offsets, int K, unsigned long long seed,
+                                      const unsigned long long* object_seeds, int* sample_indices, int device,
+                                      void* stream);
 
 #ifdef __cplusplus
 }
