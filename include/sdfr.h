@@ -63,6 +63,7 @@
  *        sdfr_pose_to_views[_objects], sdfr_views_to_pose_grad[_deferred], sdfr_decoder_backward_latent_deferred[_batch|_scaled], sdfr_decoder_forward_stage,
  *        sdfr_loop_tail, sdfr_loop_tail_fused, sdfr_loop_tail_objects, sdfr_adam_step, sdfr_point_constraint, sdfr_add_inplace
  *        K objects with V views each: sdfr_volumes_replicate, sdfr_volumes_sum_views, sdfr_inlier_ratio_objects
+ *        N hypotheses of one object, refined as N such rows: sdfr_select_row
  *        sdfr_depth_l1_loss[_workspace_bytes], sdfr_pc_l1_loss, sdfr_inlier_ratio, sdfr_nn_loss_forward / _backward
  *        sharded over ranks: sdfr_loop_view_records, sdfr_loop_tail_records, sdfr_inlier_counts_record,
  *        sdfr_inlier_update_record
@@ -70,6 +71,7 @@
  *        sdfr_affine_mask; sdfr_pointnet_layer[_counted], sdfr_linear_vec, sdfr_orientation_posterior,
  *        sdfr_init_estimate; N sets per launch and the trainer's validation numbers: sdfr_pointnet_layer_batch,
  *        sdfr_linear_rows, sdfr_pose_metrics[_workspace_bytes]
+ *        the N most probable orientation cells as N starts of the loop: sdfr_orientation_topk, sdfr_init_hypotheses
  *   5. [unstable] MESH: marching cubes over N grids (SDFPipeline.generate_mesh, after the estimate)
  *        sdfr_mesh_tables, sdfr_mesh_workspace_bytes, sdfr_mesh_count, sdfr_mesh_emit
  *   6. [unstable] METRICS: surface sampling and exact neighbour search for reconstruction metrics (the evaluation)
@@ -657,6 +659,20 @@ SDFR_API int sdfr_inlier_ratio_objects(const float* depth_input, const float* de
                               float* history, int max_history, float* state, const float* params, int n_params,
                               float* best_params, int device, void* stream);
 
+/* ---- N orientation hypotheses of ONE object (SDFPipeline.estimate_hypotheses; the reference has no counterpart: it
+ * refines the one argmax cell, and "init_view: best" picks a view, not a cell) ---------------------------------------
+ * The N most probable cells (sdfr_orientation_topk, sdfr_init_hypotheses: group 4) are N rows of the K-object loop on
+ * N copies of the object's images; this is the way back from N rows to one answer, on the device. */
+#define SDFR_MAX_HYPOTHESES 32
+
+/* j* = argmax over j < N of score[j * score_stride]; out_row[0..n) = rows[j*][0..n) (rows [N][n], bit copies),
+ * out_index[0] = j*, out_score[0] = the winning score's bits.  Equal scores: the smaller j (the more probable cell).
+ * A NaN counts as -inf: never taken while a finite score is left; all NaN gives row 0.  The loop's scores: column
+ * max_iterations - 1 of sdfr_inlier_ratio_objects' history (stride max_history), or its state's best ratios (stride 3).
+ * One wave, one launch, no atomics, nothing allocated.  1 <= N <= SDFR_MAX_HYPOTHESES, score_stride >= 1, n >= 0. */
+SDFR_API int sdfr_select_row(const float* score, int score_stride, int N, const float* rows, int n, float* out_row,
+                             int* out_index, float* out_score, int device, void* stream);
+
 /* ---- the loop sharded over ranks (one process per GPU) ------------------------------------------------
  * The reference's multi-view iteration is one Python loop over the views with ONE shared pose and ONE shared SDF
  * (simple_setup.py:420-446, update :456-462).  Sharded, every rank renders and samples a contiguous shard of the
@@ -882,6 +898,24 @@ SDFR_API int sdfr_init_estimate(const float* head, int latent, const float* grid
                        const float* centroid, const float* cam_pos, const float* cam_quat, int mean_shape,
                        int take_if_better, const float* posterior_max, float* best, float* params, int device,
                        void* stream);
+
+/* The N largest entries of posterior [C] (what sdfr_orientation_posterior left, prior-adjusted or not), descending:
+ * out_index [N], out_prob [N] = posterior[out_index] (its bits).  Equal values: the smaller index first (-0 = +0).  A
+ * NaN counts as -inf: it is never taken while a finite number is left -- the rule of sdfr_orientation_posterior's argmax
+ * (`p > best` from best = -1), so entry 0 is that call's out_index / out_max.  One workgroup, N passes over the
+ * posterior, which is only read; integer comparisons only: the same bits on every run.
+ * 1 <= N <= SDFR_MAX_HYPOTHESES, N <= C <= 2^24. */
+SDFR_API int sdfr_orientation_topk(const float* posterior, int C, int N, int* out_index, float* out_prob, int device,
+                                   void* stream);
+
+/* N starts of the loop from one estimate: params [N][n_params], row j = params_one [n_params] (the row
+ * sdfr_init_estimate wrote: [position 3 | orientation 4 | scale 1 | latent], world frame) bit for bit, except
+ * orientation = cam_quat (x) grid_quats[index[j]] -- sdfr_init_estimate's own product, rounding for rounding, so the row
+ * of the argmax cell is params_one itself.  grid_quats [C][4]; index [N] on the device (sdfr_orientation_topk's
+ * out_index), clamped to [0, C) there.  params must not overlap params_one.  8 <= n_params <= 8 + 1024. */
+SDFR_API int sdfr_init_hypotheses(const float* params_one, int n_params, const float* grid_quats, int C,
+                                  const int* index, int N, const float* cam_quat, float* params, int device,
+                                  void* stream);
 
 /* ---- the same network on N point sets per launch (eval() over a validation set: sdfest/initialization/scripts/
  * train.py:439-481) -- csrc/initnet_eval.hip.  Row n of every result has the bits of the single-set call on set n: the

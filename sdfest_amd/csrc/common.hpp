@@ -36,6 +36,26 @@ __device__ __forceinline__ V3 cross(V3 a, V3 b) {
   return mk(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x);
 }
 
+// The ranking of sdfr_orientation_topk and sdfr_select_row as ONE unsigned comparison: the larger key is the larger
+// value, and among equal values the smaller index.  High word: the float's bits made order-preserving (sign bit set for
+// positives, all bits flipped for negatives); -0 counts as +0 and a NaN as -inf, so a NaN is never taken while a finite
+// number is left.  Low word: ~index.  Keys of different indices differ, and no key is 0 or ~0.
+__device__ __forceinline__ unsigned long long rank_key(float v, int index) {
+  unsigned u = __float_as_uint(v);
+  if (v != v) u = 0xff800000u;
+  if (v == 0.0f) u = 0u;
+  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+  return ((unsigned long long)u << 32) | (unsigned)~(unsigned)index;
+}
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long k) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    const unsigned long long o = __shfl_xor(k, off, 64);
+    k = o > k ? o : k;
+  }
+  return k;
+}
+
 // Per-view record written once by the set-up kernel and then read through the
 // scalar cache by every workgroup of that view.
 struct alignas(128) ViewSetup {

@@ -124,6 +124,18 @@ __global__ __launch_bounds__(256) void pointnet_layer_kernel(
   }
 }
 
+// o = a (x) b, quaternion_multiply (quaternion_utils.py:12-33), scalar last -- the camera -> world product of an
+// orientation, shared by init_estimate_kernel and init_hypotheses_kernel so that both give the same bits.  Every
+// component is  fma(+-a1, b., fma(a3, b., +-(a0 * b.))) +- (a2 * b.)  with each rounding spelled out: the form the
+// compiler gave init_estimate_kernel's plain expression, pinned here so that it no longer depends on the surrounding
+// code (tests/hypotheses_twin.py states the same four lines in numpy).
+__device__ __forceinline__ void quat_mul_world(const float* a, const float* b, float* o) {
+  o[0] = __fsub_rn(fmaf(a[1], b[2], fmaf(a[3], b[0], __fmul_rn(a[0], b[3]))), __fmul_rn(a[2], b[1]));
+  o[1] = __fadd_rn(fmaf(a[1], b[3], fmaf(a[3], b[1], -__fmul_rn(a[0], b[2]))), __fmul_rn(a[2], b[0]));
+  o[2] = __fadd_rn(fmaf(-a[1], b[0], fmaf(a[3], b[2], __fmul_rn(a[0], b[1]))), __fmul_rn(a[2], b[3]));
+  o[3] = __fsub_rn(fmaf(-a[1], b[1], fmaf(a[3], b[3], -__fmul_rn(a[0], b[0]))), __fmul_rn(a[2], b[2]));
+}
+
 // simple_setup.py:790-838 for ONE view, on the device: the head's output row -> the estimate in the world frame,
 // written straight into the loop's parameter vector [position 3 | orientation 4 | scale 1 | latent L].
 //   head [L + 4 + C] (discretised: latent, position, scale, C orientation logits) or [L + 8] (quaternion)
@@ -165,7 +177,7 @@ __global__ void init_estimate_kernel(const float* __restrict__ head, int L, cons
   float t[4], r[4], qw[4];
   mul(c, pq, t);      // quaternion_apply (:36-54): q (p, 0) q^-1
   mul(t, ci, r);
-  mul(c, q, qw);
+  quat_mul_world(c, q, qw);
   params[0] = r[0] + cam_pos[0]; params[1] = r[1] + cam_pos[1]; params[2] = r[2] + cam_pos[2];
   for (int k = 0; k < 4; ++k) params[3 + k] = qw[k];
   params[7] = head[L + 3];
@@ -256,6 +268,60 @@ __global__ __launch_bounds__(256) void orientation_posterior_kernel(const float*
   if (tid == 0) { out_index[0] = red_i[0]; out_max[0] = red[0]; }
 }
 
+// The N largest entries of posterior[C], descending, equal values by ascending index, NaN as -inf (rank_key,
+// common.hpp).  ONE workgroup, N rounds: round r takes the largest key below round r - 1's.  Keys of different cells
+// differ, so "below the last one taken" leaves out exactly the cells already taken: nothing is marked, the posterior
+// is only read, and a round is one strided pass (L2-resident: 144 KB at resolution 3), one wave reduction and one
+// exchange of kTopkThreads / 64 keys through LDS.  Every thread ends a round with the same key, so the loop and its
+// barriers are workgroup-uniform.
+constexpr int kTopkThreads = 1024;
+__global__ __launch_bounds__(kTopkThreads) void orientation_topk_kernel(const float* __restrict__ posterior, int C, int N,
+                                                                        int* __restrict__ out_index,
+                                                                        float* __restrict__ out_prob) {
+  __shared__ unsigned long long wave_best[kTopkThreads / 64];
+  const int tid = threadIdx.x;
+  unsigned long long below = ~0ull;
+  for (int r = 0; r < N; ++r) {
+    unsigned long long best = 0;
+    for (int i = tid; i < C; i += kTopkThreads) {
+      const unsigned long long k = rank_key(posterior[i], i);
+      if (k < below && k > best) best = k;
+    }
+    best = wave_max_u64(best);
+    if ((tid & 63) == 0) wave_best[tid >> 6] = best;
+    __syncthreads();
+    best = wave_best[0];
+#pragma unroll
+    for (int w = 1; w < kTopkThreads / 64; ++w) best = wave_best[w] > best ? wave_best[w] : best;
+    __syncthreads();   // (the next round's stores wait for these reads)
+    if (best == 0) break;   // N > C: the host refuses it
+    if (tid == 0) {
+      const int i = (int)~(unsigned)best;
+      out_index[r] = i;
+      out_prob[r] = posterior[i];
+    }
+    below = best;
+  }
+}
+
+// workgroup j: params[j] = params_one, with orientation = cam_quat (x) grid_quats[index[j]] (index clamped to the table)
+__global__ __launch_bounds__(64) void init_hypotheses_kernel(const float* __restrict__ params_one, int n_params,
+                                                             const float* __restrict__ grid_quats, int C,
+                                                             const int* __restrict__ index,
+                                                             const float* __restrict__ cam_quat,
+                                                             float* __restrict__ params) {
+  float* const row = params + (size_t)blockIdx.x * n_params;
+  for (int i = threadIdx.x; i < n_params; i += 64)
+    if (i < 3 || i > 6) row[i] = params_one[i];
+  if (threadIdx.x != 0) return;
+  const int i = min(max(index[blockIdx.x], 0), C - 1);
+  const float q[4] = {grid_quats[4 * i], grid_quats[4 * i + 1], grid_quats[4 * i + 2], grid_quats[4 * i + 3]};
+  const float c[4] = {cam_quat[0], cam_quat[1], cam_quat[2], cam_quat[3]};
+  float qw[4];
+  quat_mul_world(c, q, qw);
+  for (int k = 0; k < 4; ++k) row[3 + k] = qw[k];
+}
+
 }  // namespace
 }  // namespace sdfr
 
@@ -338,6 +404,33 @@ extern "C" int sdfr_orientation_posterior(const float* logits, int C, const floa
   SDFR_HIP_TRY(hipSetDevice(device));
   hipLaunchKernelGGL(orientation_posterior_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, logits, C, prior,
                      train_prior, posterior, out_index, out_max);
+  SDFR_HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+extern "C" int sdfr_orientation_topk(const float* posterior, int C, int N, int* out_index, float* out_prob, int device,
+                                     void* stream) {
+  if (N < 1 || N > SDFR_MAX_HYPOTHESES || C < N || C > (1 << 24))
+    return fail(SDFR_E_INVALID, "sdfr_orientation_topk: N=%d of C=%d cells (1 <= N <= %d, N <= C <= 2^24)", N, C,
+                SDFR_MAX_HYPOTHESES);
+  if (!posterior || !out_index || !out_prob) return fail(SDFR_E_NULL, "sdfr_orientation_topk: NULL pointer argument");
+  SDFR_HIP_TRY(hipSetDevice(device));
+  hipLaunchKernelGGL(orientation_topk_kernel, dim3(1), dim3(kTopkThreads), 0, (hipStream_t)stream, posterior, C, N,
+                     out_index, out_prob);
+  SDFR_HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+extern "C" int sdfr_init_hypotheses(const float* params_one, int n_params, const float* grid_quats, int C,
+                                    const int* index, int N, const float* cam_quat, float* params, int device,
+                                    void* stream) {
+  if (N < 1 || N > SDFR_MAX_HYPOTHESES || C < 1 || n_params < 8 || n_params > 8 + 1024)
+    return fail(SDFR_E_INVALID, "sdfr_init_hypotheses: N=%d rows of n_params=%d from C=%d cells", N, n_params, C);
+  if (!params_one || !grid_quats || !index || !cam_quat || !params)
+    return fail(SDFR_E_NULL, "sdfr_init_hypotheses: NULL pointer argument");
+  SDFR_HIP_TRY(hipSetDevice(device));
+  hipLaunchKernelGGL(init_hypotheses_kernel, dim3((unsigned)N), dim3(64), 0, (hipStream_t)stream, params_one, n_params,
+                     grid_quats, C, index, cam_quat, params);
   SDFR_HIP_TRY(hipGetLastError());
   return 0;
 }

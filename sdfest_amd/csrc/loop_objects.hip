@@ -4,7 +4,9 @@
 //                              per view (sdf_view_stride), and view k V + v is object k from camera v
 //   sdfr_volumes_sum_views     the K V gradient volumes those launches leave, summed per object for the batched VJP
 //   sdfr_inlier_ratio_objects  sdfr_inlier_ratio (simple_setup.py:177-211) for K objects in two launches
-// All three move bytes and do next to no arithmetic: a thread owns 4 consecutive floats of a row and moves them as one
+// and, where the K rows are N hypotheses of one object, the way back to one answer:
+//   sdfr_select_row            the row with the best score (one wave)
+// The first three move bytes and do next to no arithmetic: a thread owns 4 consecutive floats of a row and moves them as one
 // 16-byte access wherever the row starts on a 16-byte boundary (always for the loop's own buffers: R^3 and W H are
 // multiples of 4 there), float by float where it does not (R odd: every row but each fourth starts off the boundary).
 #include "common.hpp"
@@ -158,6 +160,23 @@ __global__ __launch_bounds__(256) void inlier_update_objects_kernel(int* __restr
       best_params[k * (size_t)n_params + i] = params[k * (size_t)n_params + i];
 }
 
+// ONE wave: lane j < N holds row j's score as a rank_key (common.hpp: the larger score, then the smaller j; NaN as
+// -inf, so all-NaN gives row 0); after the wave maximum every lane knows the winner and the lanes copy its row
+__global__ __launch_bounds__(64) void select_row_kernel(const float* __restrict__ score, int score_stride, int N,
+                                                        const float* __restrict__ rows, int n,
+                                                        float* __restrict__ out_row, int* __restrict__ out_index,
+                                                        float* __restrict__ out_score) {
+  const int lane = threadIdx.x;
+  const unsigned long long key = wave_max_u64(lane < N ? rank_key(score[(size_t)lane * score_stride], lane) : 0ull);
+  const int j = (int)~(unsigned)key;
+  const float* const row = rows + (size_t)j * n;
+  for (int i = lane; i < n; i += 64) out_row[i] = row[i];
+  if (lane == 0) {
+    out_index[0] = j;
+    out_score[0] = score[(size_t)j * score_stride];
+  }
+}
+
 // K rows of n floats as a (chunks, K) grid, or the reason why not
 int rows_grid(const char* fn, int K, int V, size_t n, dim3* grid) {
   if (K < 0 || V < 1 || K > 65535 || (long long)K * V > 0x7fffffffLL)
@@ -217,6 +236,20 @@ extern "C" int sdfr_inlier_ratio_objects(const float* depth_input, const float* 
                        counts);
   hipLaunchKernelGGL(inlier_update_objects_kernel, dim3((unsigned)K), dim3(256), 0, st, counts, step, history,
                      max_history, state, params, n_params, best_params);
+  SDFR_HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+extern "C" int sdfr_select_row(const float* score, int score_stride, int N, const float* rows, int n, float* out_row,
+                               int* out_index, float* out_score, int device, void* stream) {
+  if (N < 1 || N > SDFR_MAX_HYPOTHESES || score_stride < 1 || n < 0)
+    return fail(SDFR_E_INVALID, "sdfr_select_row: N=%d rows of n=%d, score_stride=%d (1 <= N <= %d)", N, n, score_stride,
+                SDFR_MAX_HYPOTHESES);
+  if (!score || !out_index || !out_score || (n > 0 && (!rows || !out_row)))
+    return fail(SDFR_E_NULL, "sdfr_select_row: NULL pointer argument");
+  SDFR_HIP_TRY(hipSetDevice(device));
+  hipLaunchKernelGGL(select_row_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, score, score_stride, N, rows, n,
+                     out_row, out_index, out_score);
   SDFR_HIP_TRY(hipGetLastError());
   return 0;
 }

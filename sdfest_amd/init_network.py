@@ -274,6 +274,19 @@ class SDFPoseNet:
         _lib.check(rc, "sdfr_orientation_posterior")
         return post, idx, mx
 
+    def orientation_topk(self, posterior: torch.Tensor, n: int):
+        """the `n` most probable cells of a posterior (C,), descending; equal values by ascending index, a NaN below
+        every number (``sdfr_orientation_topk``): (index (n,) int32, prob (n,)).  Entry 0 is ``orientation_posterior``'s
+        index and maximum."""
+        post = posterior.reshape(-1).to(device=self.dev, dtype=torch.float32).contiguous()
+        n = int(n)
+        idx = torch.empty(max(n, 0), dtype=torch.int32, device=self.dev)
+        prob = torch.empty(max(n, 0), dtype=torch.float32, device=self.dev)
+        rc = self.L.sdfr_orientation_topk(post.data_ptr(), post.numel(), n, idx.data_ptr(), prob.data_ptr(),
+                                          self.dev.index, self._st())
+        _lib.check(rc, "sdfr_orientation_topk")
+        return idx, prob
+
 
 def nn_init(network: SDFPoseNet, camera: Camera, depth_images: torch.Tensor, camera_positions: torch.Tensor,
             camera_orientations: torch.Tensor, config: Dict, normalize_pose: bool = True,
@@ -341,11 +354,21 @@ class ResidentInit:
     counts afterwards (one small copy; the caller raises ``NoDepthError``)."""
 
     def __init__(self, network: SDFPoseNet, camera: Camera, views: int, config: Dict, normalize_pose: bool = True,
-                 objects: bool = False):
+                 objects: bool = False, hypotheses: int = 1):
         """objects: the `views` images are `views` different OBJECTS seen from one camera (cam_pos / cam_quat hold one
         row): every image gets its own estimate, ``self.params`` is (views, 8 + L) -- the initialisation of
-        ``pipeline.MultiObjectRenderAndCompare``; the "first" / "best" choice among views does not apply."""
+        ``pipeline.MultiObjectRenderAndCompare``; the "first" / "best" choice among views does not apply.
+        hypotheses=N > 1 (one view of one object, discretised head): behind the estimate the N most probable cells of
+        ``self.posterior`` (``sdfr_orientation_topk`` -> ``self.hyp_index`` / ``self.hyp_prob``, on the device) become N
+        rows ``self.params_h`` (N, 8 + L) that differ in their orientation only (``sdfr_init_hypotheses``); row 0 is
+        ``self.params``.  Both launches are part of the captured sequence.  With 1 the sequence is the one without."""
         net = self.net = network
+        self.hypotheses = int(hypotheses)
+        if not 1 <= self.hypotheses <= _lib.ABI["SDFR_MAX_HYPOTHESES"]:
+            raise ValueError(f"hypotheses must be in [1, {_lib.ABI['SDFR_MAX_HYPOTHESES']}], got {hypotheses}")
+        if self.hypotheses > 1 and (objects or int(views) != 1 or net.orientation_repr != "discretized"):
+            raise ValueError("hypotheses > 1 needs one view of one object (views=1, objects=False) and a discretized "
+                             "orientation head: the hypotheses are cells of its posterior")
         self.cam, self.V = camera, int(views)
         self.objects = bool(objects)
         self.dev, self.L = net.dev, net.L            # (L: the loaded library, as in SDFPoseNet)
@@ -405,6 +428,12 @@ class ResidentInit:
         self.post_max = torch.zeros(1, **f32)
         self.best = torch.zeros(1, **f32)
         self.params = torch.zeros((self.V, 8 + net.shape_dimension) if self.objects else (8 + net.shape_dimension,), **f32)
+        if self.hypotheses > 1:
+            if self.hypotheses > self.C:
+                raise ValueError(f"hypotheses={self.hypotheses} exceed the grid's {self.C} cells")
+            self.hyp_index = torch.zeros(self.hypotheses, **i32)
+            self.hyp_prob = torch.zeros(self.hypotheses, **f32)
+            self.params_h = torch.zeros((self.hypotheses, 8 + net.shape_dimension), **f32)
         self._graphs = {}
         self._host_counts = torch.zeros(self.V, dtype=torch.int32).pin_memory()
         self._counts_event = None
@@ -485,6 +514,14 @@ class ResidentInit:
                 cam_pos[0 if self.objects else v].data_ptr(), cam_quat[0 if self.objects else v].data_ptr(),
                 int(self.mean_shape), int(best), self.post_max.data_ptr(), self.best.data_ptr(),
                 (self.params[v] if self.objects else self.params).data_ptr(), d, st), "sdfr_init_estimate")
+        if self.hypotheses > 1:     # (one view: self.posterior and self.params are that view's)
+            _lib.check(L.sdfr_orientation_topk(self.posterior.data_ptr(), self.C, self.hypotheses,
+                                               self.hyp_index.data_ptr(), self.hyp_prob.data_ptr(), d, st),
+                       "sdfr_orientation_topk")
+            _lib.check(L.sdfr_init_hypotheses(self.params.data_ptr(), self.params.numel(), self.grid_quats.data_ptr(),
+                                              self.C, self.hyp_index.data_ptr(), self.hypotheses,
+                                              cam_quat[0].data_ptr(), self.params_h.data_ptr(), d, st),
+                       "sdfr_init_hypotheses")
 
     def __call__(self, depth: torch.Tensor, cam_pos: torch.Tensor, cam_quat: torch.Tensor,
                  prior_orientation_distribution: Optional[torch.Tensor] = None,

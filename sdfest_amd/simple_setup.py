@@ -28,6 +28,7 @@ from typing import Dict, List, Mapping, Optional, Tuple
 
 import torch
 
+from . import _lib
 from .differentiable_renderer import Camera, parse_sdf_grad_mode, render_depth_gpu
 from .mesh import Mesh, extract_mesh
 from .init_network import NoDepthError, ResidentInit, SDFPoseNet, adjust_categorical_posterior, nn_init
@@ -57,7 +58,8 @@ class SDFPipeline:
     ``threshold``, ``max_iterations``, ``depth_weight``, ``pc_weight``, ``nn_weight``, ``mean_shape``, ``init_view``,
     ``init`` {backbone_type, backbone, head_type, head, normalize_pose, model}, ``vae`` {latent_size, decoder, tsdf,
     model} (or ``init["vae"]``), optionally ``far_field``, ``result_selection_strategy``,
-    ``relative_inlier_threshold``.
+    ``relative_inlier_threshold``, ``orientation_hypotheses`` (N > 1: ``__call__`` refines the N most probable
+    orientation cells side by side and returns the best supported one, ``estimate_hypotheses``; not in the reference).
     vae_state_dict / init_state_dict: the state dicts of the reference's ``SDFVAE`` (keys ``decoder.*``; encoder
     keys are ignored) and ``SDFPoseNet``; default: ``torch.load`` of ``config[...]["model"]`` if that file exists.
     init_network: an object called like ``nn_init``'s network, or a callable
@@ -106,6 +108,7 @@ class SDFPipeline:
         self._resident_wanted = bool(resident_init)
         self._residents = {}
         self._multi_loops, self._resident_objects = {}, {}     # estimate_objects: per (K, shape_optimization, V, tracking) / per (K, V)
+        self._resident_hypotheses, self._last_hypotheses = {}, None     # estimate_hypotheses: per N / the last call's record
         self._ignored_warned = False
 
     def _parse_config(self, config: Dict) -> None:
@@ -224,6 +227,16 @@ class SDFPipeline:
             warnings.warn("sdfest_amd.SDFPipeline: visualize / log_path / animation_path are accepted and ignored "
                           "(plots, step logs and animations are outside the hot path)")
             self._ignored_warned = True
+        n_hypotheses = int(self.config.get("orientation_hypotheses", 1))
+        if n_hypotheses != 1:     # (the default path below is untouched by the key's absence or 1)
+            if point_constraint is not None:
+                raise ValueError("point_constraint cannot be combined with orientation_hypotheses > 1: the K-row loop "
+                                 "(MultiObjectRenderAndCompare) has no point constraint")
+            return self.estimate_hypotheses(depth_images, masks, color_images, hypotheses=n_hypotheses,
+                                            camera_positions=camera_positions, camera_orientations=camera_orientations,
+                                            shape_optimization=shape_optimization,
+                                            prior_orientation_distribution=prior_orientation_distribution,
+                                            training_orientation_distribution=training_orientation_distribution)
         # batch dimension (:306-318)
         if depth_images.dim() == 2:
             depth_images = depth_images.unsqueeze(0)
@@ -362,6 +375,153 @@ class SDFPipeline:
             if V > 1 and bool((loop.counts == 0).any()):     # (the initialisation saw the first views only)
                 raise NoDepthError
         return out
+
+    # ---- N orientation hypotheses of one object ----------------------------------------------------------------
+    def _hypothesis_loop(self, depth_images: torch.Tensor, masks: torch.Tensor, hypotheses: int,
+                         camera_positions, camera_orientations, shape_optimization: bool):
+        """the K-row loop with K = N rows for ONE object, bound to its V images (the masks repeated N times)"""
+        N = int(hypotheses)
+        if not 1 <= N <= _lib.ABI["SDFR_MAX_HYPOTHESES"]:
+            raise ValueError(f"hypotheses must be in [1, {_lib.ABI['SDFR_MAX_HYPOTHESES']}], got {hypotheses}")
+        if depth_images.dim() not in (2, 3) or tuple(masks.shape) != tuple(depth_images.shape):
+            raise ValueError("depth_images (H,W) or (V,H,W) and the masks of ONE object in the same shape are expected")
+        V = 1 if depth_images.dim() == 2 else int(depth_images.shape[0])
+        # (the inlier bookkeeping always runs: it is the score; "hypotheses" keeps these loops apart from
+        # estimate_objects' loops of the same K)
+        key = ("hypotheses", N, bool(shape_optimization), V)
+        loop = self._multi_loops.get(key)
+        if loop is None:
+            self._bounded(self._multi_loops, self.MAX_CACHED_LOOPS)
+            loop = self._multi_loops[key] = MultiObjectRenderAndCompare(
+                self.vae, self.cam, self.config, N, shape_optimization=shape_optimization, device=self._dev,
+                sdf_grad_mode=self.sdf_grad_mode, views=V, track_inliers=True)
+            f32 = dict(dtype=torch.float32, device=self._dev)
+            loop.selection = dict(row=torch.zeros(loop.n, **f32), index=torch.zeros(1, dtype=torch.int32, device=self._dev),
+                                  score=torch.zeros(1, **f32), initial=torch.zeros((N, loop.n), **f32))
+        H, W = loop.H, loop.W
+        with torch.no_grad():
+            # (frames + masks: every row gets its own masked copy, the caller's depth is only read)
+            loop.rebind(depth_images.reshape(V, H, W), camera_positions, camera_orientations,
+                        masks=masks.reshape(1, V, H, W).expand(N, V, H, W), far_field=self._far_field)
+        return loop
+
+    def _refine_bound(self, loop: MultiObjectRenderAndCompare, position, orientation, scale, latent, index=None,
+                      probability=None) -> tuple:
+        """run the N rows of a bound loop and select: every launch on the current stream, nothing read back"""
+        N, n = loop.K, loop.n
+        sel = loop.selection
+        with torch.no_grad():
+            initial = sel["initial"]
+            initial[:, 0:3] = position.reshape(N, 3)
+            initial[:, 3:7] = orientation.reshape(N, 4)
+            initial[:, 7] = scale.reshape(N)
+            initial[:, 8:] = latent.reshape(N, loop.Lz)
+            loop(initial[:, 0:3], initial[:, 3:7], initial[:, 7], initial[:, 8:])
+            score, stride = self._hypothesis_scores(loop)
+            _lib.check(loop.L.sdfr_select_row(score.data_ptr(), stride, N, loop.params.data_ptr(), n,
+                                              sel["row"].data_ptr(), sel["index"].data_ptr(), sel["score"].data_ptr(),
+                                              self._dev.index, torch.cuda.current_stream(self._dev).cuda_stream),
+                       "sdfr_select_row")
+            row = sel["row"]
+            out = row[0:3][None].clone(), row[3:7][None].clone(), row[7:8].clone(), row[8:][None].clone()
+        self._last_multi_loop = loop
+        self._last_hypotheses = dict(loop=loop, index=index, probability=probability)
+        return out
+
+    def _hypothesis_scores(self, loop: MultiObjectRenderAndCompare):
+        """(first score, stride in floats): every row's inlier ratio at the last iteration, or its best one with
+        ``result_selection_strategy: best_inlier_ratio``; without an iteration all are 0 and row 0 wins"""
+        if self.result_selection_strategy == "best_inlier_ratio":
+            return loop.best_state[:, 0], 3
+        last = max(loop.max_history - 1, 0)
+        return loop.inlier_history[:, last], max(loop.max_history, 1)
+
+    def refine_hypotheses(self, depth_images: torch.Tensor, masks: torch.Tensor, position: torch.Tensor,
+                          orientation: torch.Tensor, scale: torch.Tensor, latent: torch.Tensor,
+                          camera_positions: Optional[torch.Tensor] = None,
+                          camera_orientations: Optional[torch.Tensor] = None, shape_optimization: bool = True) -> tuple:
+        """N estimates of ONE object -- position (N,3), orientation (N,4), scale (N,), latent (N,L) -- refined side by
+        side on the same observation (``MultiObjectRenderAndCompare`` with K = N rows, every row the object's own masked
+        images), and the one the observation supports best: the largest inlier ratio (simple_setup.py:177-211, on the
+        last view) at the last iteration, or each row's best ratio with ``result_selection_strategy:
+        best_inlier_ratio``; equal ratios go to the smaller row, a NaN ratio (0 / 0: an image without a valid
+        pixel) ranks below every number (``sdfr_select_row``, on the device).
+        depth_images (H,W) or (V,H,W), NOT modified; masks: the object's, same shape.  Returns (position (1,3),
+        orientation (1,4), scale (1,), latent (1,L)): the winner's LAST iterate, as ``__call__`` returns.  ``NoDepthError``
+        is raised after the work was enqueued, as in ``estimate_objects``; ``last_hypotheses()`` has every row."""
+        N = int(position.reshape(-1, 3).shape[0])
+        loop = self._hypothesis_loop(depth_images, masks, N, camera_positions, camera_orientations, shape_optimization)
+        out = self._refine_bound(loop, position, orientation, scale, latent)
+        if bool((loop.counts == 0).any()):
+            raise NoDepthError
+        return out
+
+    def estimate_hypotheses(self, depth_images: torch.Tensor, masks: torch.Tensor, color_images=None,
+                            hypotheses: int = 1, camera_positions: Optional[torch.Tensor] = None,
+                            camera_orientations: Optional[torch.Tensor] = None, shape_optimization: bool = True,
+                            prior_orientation_distribution: Optional[torch.Tensor] = None,
+                            training_orientation_distribution: Optional[torch.Tensor] = None) -> tuple:
+        """``__call__`` with N starts instead of one: the initialisation network's estimate from the object's first view,
+        once per each of the N most probable cells of its (prior-adjusted) orientation posterior
+        (``ResidentInit(hypotheses=N)``), through ``refine_hypotheses``.  Where the argmax cell is wrong -- a symmetric
+        body, a flat posterior, a hidden handle -- the loop converges into a wrong minimum from it; the other cells are
+        the remedy the reference lacks.  Arguments as ``__call__`` (depth NOT modified; color_images unused); the prior
+        is (C,) or (V,C), of which the first view's row counts.  Needs a discretized orientation head, the resident
+        initialisation (no ``init_network`` override, ``resident_init=True``) and ``init_view: first`` for several views.
+        ``hypotheses=1`` is ``estimate_objects(depth, mask[None])`` bit for bit."""
+        N = int(hypotheses)
+        if not 1 <= N <= _lib.ABI["SDFR_MAX_HYPOTHESES"]:
+            raise ValueError(f"hypotheses (config key orientation_hypotheses) must be in "
+                             f"[1, {_lib.ABI['SDFR_MAX_HYPOTHESES']}], got {hypotheses}")
+        if (self._nn_init_override is not None or not isinstance(self.init_network, SDFPoseNet)
+                or not self._resident_wanted):
+            raise ValueError("orientation hypotheses are cells of the initialisation network's posterior: they need "
+                             "the SDFPoseNet itself (no init_network override) and resident_init=True")
+        if self.init_network.orientation_repr != "discretized":
+            raise ValueError("orientation hypotheses need a discretized orientation head "
+                             f"(init.head.orientation_repr: {self.init_network.orientation_repr})")
+        V = 1 if depth_images.dim() == 2 else int(depth_images.shape[0])
+        if V > 1 and self.config.get("init_view", "first") != "first":
+            raise ValueError("orientation hypotheses with several views start from the first view (init_view: first), "
+                             f"not init_view: {self.config.get('init_view')}")
+        loop = self._hypothesis_loop(depth_images, masks, N, camera_positions, camera_orientations, shape_optimization)
+        if N not in self._resident_hypotheses:
+            self._bounded(self._resident_hypotheses, self.MAX_CACHED_LOOPS)
+            self._resident_hypotheses[N] = ResidentInit(
+                self.init_network, self.cam, 1, dict(self.config, init_view="first"),
+                normalize_pose=bool(self.init_config.get("normalize_pose", False)), hypotheses=N)
+        resident = self._resident_hypotheses[N]
+        with torch.no_grad():
+            prior = prior_orientation_distribution
+            if prior is not None:
+                prior = prior.reshape(-1, resident.C)[0:1]
+            # (on the loop's own address-stable buffers: row 0's first view, camera 0)
+            resident(loop.target[0:1], loop.cam_pos[0:1], loop.cam_quat[0:1], prior, training_orientation_distribution)
+            if N > 1:
+                p, index, probability = resident.params_h, resident.hyp_index, resident.hyp_prob
+            else:
+                p, index, probability = resident.params[None], resident.index, resident.post_max
+            out = self._refine_bound(loop, p[:, 0:3], p[:, 3:7], p[:, 7], p[:, 8:], index, probability)
+            if resident.empty_views():
+                raise NoDepthError
+            if V > 1 and bool((loop.counts == 0).any()):
+                raise NoDepthError
+        return out
+
+    def last_hypotheses(self):
+        """the last ``estimate_hypotheses`` / ``refine_hypotheses`` call (also one routed from ``__call__``), read from
+        the device here and nowhere else: ``index`` (N,) the cells and ``probability`` (N,) their posterior, descending
+        (None after ``refine_hypotheses``, which is handed orientations, not cells), ``inlier_ratio`` (N,) the scores,
+        ``winner`` the selected row, ``initial`` / ``final`` (N, 8 + L) the rows [position 3 | orientation 4 | scale |
+        latent] before and after the loop.  None before the first such call."""
+        last = self._last_hypotheses
+        if last is None:
+            return None
+        loop = last["loop"]
+        clone = lambda t: None if t is None else t.clone()
+        return dict(index=clone(last["index"]), probability=clone(last["probability"]),
+                    inlier_ratio=self._hypothesis_scores(loop)[0].clone(), winner=int(loop.selection["index"].item()),
+                    initial=loop.selection["initial"].clone(), final=loop.params.clone())
 
     def best_estimates(self):
         """K entries (ratio, 1-based iteration, (position, orientation, scale, latent)), one per object: the parameters
