@@ -1350,7 +1350,9 @@ SDFR_API int sdfr_nocs_correspondences(const float* depth, const unsigned char* 
  *   (:167-169); it is 0 when no residual beat 1e10.  Final fit = Umeyama over the inliers.
  * Outputs, per object (DEVICE): position [3], rotation [3][3], scale, transform [4][4] (doubles, row-major; NaN unless
  * status is SDFR_NOCS_OK), inlier_ratio (double), best_iteration (the winner, -1 without one), iterations_run (j + 1),
- * status; inlier_mask [total] bytes (nullable).
+ * status; inlier_mask [total] bytes (nullable).  A valid rotation is a ROTATION (orthogonal, determinant +1) whatever
+ * the covariance's rank: for exactly planar or collinear sources, where a rotation and its mirror image fit equally
+ * well and the reference returns either by rounding, it is the rotation.
  *   SDFR_NOCS_OK          the four results are valid
  *   SDFR_NOCS_NONE        the reference returns four None: fewer than 5 points, or inlier_ratio < 0.1
  *   SDFR_NOCS_POSE_ERROR  the reference raises PoseEstimationError: zero source variance in a fit that ran (:226-229)

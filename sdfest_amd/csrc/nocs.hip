@@ -214,10 +214,14 @@ constexpr int kFitOk = 0, kFitZeroVariance = 1, kFitNan = 2;
 
 // The tail of _estimate_similarity_umeyama (nocs_utils.py:209-241) from the centroids, the covariance (row-major,
 // cov[i][j] = mean(ct_i * cs_j)) and var_p = sum of the source's population variances.  T = the 3 x 4 transform
-// [scale * R | t], row-major; rot / scale: nullable.  R = U S V^T is formed as
-//     u1 v1^T + u2 v2^T + sign * u3 v3^T,   u3 = +-(u1 x u2) on the side of A v3,   v3 = the third column of V,
-// which is the reference's product whenever the singular values are distinct and non-zero, and stays orthogonal when
-// the smallest one is tiny (five nearly coplanar points).
+// [scale * R | t], row-major; rot / scale: nullable.  With the Jacobi columns sorted, R is formed as
+//     u1 v1^T + u2 v2^T + u3 v3^T,   u3 = det(V) * (u1 x u2),   v3 = the third column of V,
+// and the scale takes sigma3 with the sign of u3 . (A v3).  Contract: whenever the fit is kFitOk, R is a ROTATION
+// (orthogonal, det R = det(V)^2 = +1 by construction), whatever the covariance's rank.  For a covariance of full rank
+// this is the reference's U S V^T, S = diag(1, 1, sign det(cov)): u1 x u2 is +-(A v3) / sigma3, and the sign of
+// u3 . (A v3) is that of det(cov).  For a covariance of rank two or one (an exactly planar or collinear source set,
+// e.g. one flat face of 8-bit NOCS colours) a rotation and its mirror image fit equally well and det(cov) is zero but
+// for rounding; the reference then returns either by LAPACK's rounding, this returns the rotation.
 __device__ int umeyama_finish(D3 cs, D3 ct, const double* cov, double var_p, double* T, double* rot, double* scale) {
   bool nan = false;
 #pragma unroll
@@ -243,19 +247,18 @@ __device__ int umeyama_finish(D3 cs, D3 ct, const double* cov, double var_p, dou
   }
   SDFR_SWAP(0, 1) SDFR_SWAP(0, 2) SDFR_SWAP(1, 2)
 #undef SDFR_SWAP
-  const double det = cov[0] * (cov[4] * cov[8] - cov[5] * cov[7]) - cov[1] * (cov[3] * cov[8] - cov[5] * cov[6]) +
-                     cov[2] * (cov[3] * cov[7] - cov[4] * cov[6]);
-  const double sign = det < 0.0 ? -1.0 : 1.0;
   const D3 u0 = dunit(w0, d3(1, 0, 0));
   D3 u1 = dunit(w1, d3(0, 1, 0));
   // (re-orthogonalised against u0: exact for converged columns, and a rank-one covariance still gets a frame)
   const double p01 = ddot(u0, u1);
   u1 = dunit(d3(u1.x - p01 * u0.x, u1.y - p01 * u0.y, u1.z - p01 * u0.z), dunit(dcross(u0, d3(0, 0, 1)), d3(0, 1, 0)));
+  // V is a product of plane rotations and the column swaps above: det(V) = +-1, read off its triple product
   D3 u2 = dcross(u0, u1);
-  if (ddot(u2, w2) < 0.0) u2 = d3(-u2.x, -u2.y, -u2.z);
+  if (ddot(v0, dcross(v1, v2)) < 0.0) u2 = d3(-u2.x, -u2.y, -u2.z);
+  const double sign = ddot(u2, w2) < 0.0 ? -1.0 : 1.0;
   if (var_p == 0.0) return kFitZeroVariance;   // PoseEstimationError (:226-229)
   const double sc = 1.0 / var_p * (s0 + s1 + sign * s2);
-  const D3 u[3] = {u0, u1, d3(sign * u2.x, sign * u2.y, sign * u2.z)};
+  const D3 u[3] = {u0, u1, u2};
   const D3 v[3] = {v0, v1, v2};
   double R[9];
 #pragma unroll
