@@ -85,6 +85,8 @@
  *  12. [unstable] NOCS ANNOTATION: pose and scale of a NOCS frame's objects (NOCSDataset's preprocessing)
  *        sdfr_nocs_workspace_bytes, sdfr_nocs_count, sdfr_nocs_correspondences,
  *        sdfr_similarity_ransac[_workspace_bytes], sdfr_nocs_sample_indices
+ *  13. [unstable] FRAME ANNOTATION: the visibility mask of an annotated RGB-D frame (AnnotatedRedwoodDataset)
+ *        sdfr_visible_mask
  * (Within the file the groups follow the order in which the reference's code runs; every declaration carries the
  * reference file:line it replaces.)
  */
@@ -1388,6 +1390,28 @@ SDFR_API int sdfr_similarity_ransac(const void* source, const void* target, int 
 SDFR_API int sdfr_nocs_sample_indices(const long long* offsets, int K, unsigned long long seed,
                                       const unsigned long long* object_seeds, int* sample_indices, int device,
                                       void* stream);
+
+/* ==== 13. FRAME ANNOTATION ==================================================================== */
+/* ---- the instance mask of an annotated RGB-D frame (sdfest/initialization/datasets/redwood_dataset.py:262-275,
+ * AnnotatedRedwoodDataset._compute_mask): where the ground-truth mesh, drawn at its annotated pose (sdfr_mesh_depth),
+ * covers a pixel and the sensor did not see something in front of it.  B images per call; rendered, observed
+ * [B][H][W] fp32 metres (0 = nothing drawn / no reading).  Per pixel
+ *     mask   = rendered != 0 && !(observed != 0 && observed < rendered - margin)
+ * with the subtraction rounded to fp32 and IEEE comparisons: a pixel at exactly fl(rendered - margin) stays visible
+ * (the comparison is strict), and so does an observed NaN or infinity, as in torch.  margin >= 0 and finite (the
+ * reference's is 0.01).
+ *   mask    [B][H][W] bytes, 0 or 1 (a torch.bool buffer)
+ *   masked  [B][H][W] fp32, nullable: mask ? observed : 0
+ *   counts  [B][4] int32, nullable: covered (rendered != 0), visible (mask), occluded (covered && !mask), valid
+ *           (mask && observed != 0: the points of the frame's masked point cloud).  OVERWRITTEN by every call.
+ * Image b starts at pixel b H W of every buffer; the float pointers need 4-byte alignment only (a view into a larger
+ * buffer, H W no multiple of 4): an image whose rendered, observed and masked pixels are equally far from a 16-byte
+ * boundary, with the mask 4-byte aligned at the same pixel, moves 16 bytes per lane and access, any other one pixel.
+ * Same results either way, and the same bits on every run (the counts are integer atomics).  H, W >= 1,
+ * H W <= 2^31 - 1, 0 <= B <= 65535 (B = 0: nothing to do).  Kernels only, on the caller's stream; no workspace, no
+ * allocation, no host synchronisation: the call can be captured into a graph. */
+SDFR_API int sdfr_visible_mask(const float* rendered, const float* observed, int B, int H, int W, float margin,
+                               unsigned char* mask, float* masked, int* counts, int device, void* stream);
 
 #ifdef __cplusplus
 }

@@ -4,20 +4,26 @@
 estimate's mesh, samples of both surfaces, the reconstruction metrics -- with this package's own stages
 (``render_mesh_depth``, ``SDFPipeline``, ``generate_mesh``, ``sample_points``, ``evaluate_metrics``) and no host round
 trip between them but the one the metrics end in.  Visualisation and logs are out of scope, as in ``simple_setup``.
+
+``evaluate_annotated`` is the same loop over REAL frames with ground-truth poses and meshes (a dataset such as
+``AnnotatedRedwoodDataset``): what the reference's ``estimation/configs/redwood_evaluation.yaml`` is the config of.
 """
 import math
 from typing import Dict, List, Optional, Tuple
 
+import numpy as np
 import torch
 
 from .generated_views import sample_uniform_quaternions
 from .mesh import Mesh, extract_mesh, render_mesh_depth, sample_points
-from .metrics import evaluate_metrics
+from .init_network import NoDepthError
+from .metrics import _Quat, correct_thresh, evaluate_metrics
 from .pipeline import quaternion_apply, quaternion_invert, quaternion_multiply
+from .pointset_utils import change_orientation_camera_convention, change_position_camera_convention
 from .sdf_utils import mesh_to_sdf, normalized_mesh
 
 __all__ = ["view_poses", "generate_views", "evaluate_mesh", "evaluate_meshes", "vae_reconstruction", "metric_stats",
-           "DEFAULT_METRICS"]
+           "evaluate_annotated", "DEFAULT_METRICS", "DEFAULT_POSE_THRESHOLDS"]
 
 # the ``metrics:`` mapping of the reference's estimation/configs/rendering_evaluation.yaml
 DEFAULT_METRICS = {
@@ -173,3 +179,147 @@ def evaluate_meshes(pipeline, gt_meshes: List[Mesh], num_views: int, camera_dist
     ``_compute_metric_stats`` returns"""
     return metric_stats([evaluate_mesh(pipeline, m, num_views, camera_distance, samples, seed, metrics_config,
                                        shape_optimization, generator) for m in gt_meshes])
+
+
+# ---- annotated real frames -------------------------------------------------------------------------------------------
+# name -> (degrees, metres): the four usual pairs
+DEFAULT_POSE_THRESHOLDS = {"5deg_2cm": (5.0, 0.02), "5deg_5cm": (5.0, 0.05), "10deg_2cm": (10.0, 0.02),
+                           "10deg_5cm": (10.0, 0.05)}
+
+
+def pose_errors(position_gt, orientation_gt, position, orientation,
+                rotational_symmetry_axis: Optional[int] = None) -> Tuple[float, float]:
+    """(position error in metres, rotation error in degrees) of an estimate against the ground truth, in float64 on the
+    host, by ``correct_thresh``'s formulas: the Euclidean distance; the angle of gt * estimate^-1, or, with a
+    `rotational_symmetry_axis` (0, 1, 2), the angle between the two images of that object axis."""
+    host = lambda v: np.asarray(v.detach().cpu() if isinstance(v, torch.Tensor) else v, dtype=np.float64).reshape(-1)
+    position_error = float(np.linalg.norm(host(position_gt) - host(position)))
+    r_gt, r = _Quat(host(orientation_gt)), _Quat(host(orientation))
+    if rotational_symmetry_axis is None:
+        radians = (r_gt * r.inv()).magnitude()
+    else:
+        axis = np.zeros(3)
+        axis[int(rotational_symmetry_axis)] = 1.0
+        radians = float(np.arccos(np.clip(r_gt.apply(axis) @ r.apply(axis), -1.0, 1.0)))
+    return position_error, float(np.degrees(radians))
+
+
+def _annotated_groups(dataset, indices: List[int], pipelines, frames_per_call: int, skipped: list) -> List[List[int]]:
+    """runs of at most `frames_per_call` consecutive samples of one category; a sample whose category has no pipeline
+    goes to `skipped` and ends a run"""
+    groups, run, run_category = [], [], None
+    for i in indices:
+        category = dataset.annotation(i)["category_str"] if hasattr(dataset, "annotation") else dataset[i]["category_str"]
+        if isinstance(pipelines, dict) and category not in pipelines:
+            skipped.append({"index": i, "category_str": category, "reason": f"no pipeline for category {category}"})
+            category = None
+        if run and (category != run_category or len(run) >= frames_per_call):
+            groups.append(run)
+            run = []
+        if category is not None:
+            run.append(i)
+        run_category = category
+    if run:
+        groups.append(run)
+    return groups
+
+
+def evaluate_annotated(pipelines, dataset, samples: int, seed: int, metrics_config: Optional[dict] = None,
+                       pose_thresholds: Optional[dict] = None, symmetry_axes: Optional[dict] = None,
+                       frames_per_call: int = 1, shape_optimization: bool = True,
+                       indices: Optional[List[int]] = None) -> dict:
+    """The evaluation over annotated real frames: every sample of `dataset` (``AnnotatedRedwoodDataset``, or anything
+    with its sample dictionary, ``load_mesh`` and ``_config``) -> the pipeline on a clone of its depth under its mask
+    -> ``pipeline.generate_mesh(latent, scale, True)`` posed with the estimate, and ``dataset.load_mesh(obj_path)``
+    posed with the annotation -> `samples` points of each with one `seed` -> the metrics of `metrics_config`
+    (default: ``DEFAULT_METRICS``) on the two point sets, the position error (metres) and the rotation error (degrees)
+    in float64 on the host (``pose_errors``), and one ``correct_thresh`` flag per entry of `pose_thresholds` ({name:
+    (degrees, metres)}; default ``DEFAULT_POSE_THRESHOLDS``).
+
+    pipelines: one pipeline for every sample, or {category_str: pipeline}.  Only ``pipeline(depth, mask, color,
+    shape_optimization=...)``, ``pipeline.generate_mesh`` and, for `frames_per_call` > 1, ``pipeline.estimate_frames``
+    are used.  The dataset may use either camera convention: its poses are brought to the pipeline's OpenGL frame.
+    symmetry_axes: {category_str: 0 | 1 | 2}, the ``rotational_symmetry_axis`` of such a category's rotation error and
+    flags.  frames_per_call = K: runs of up to K consecutive samples of one category go through ``estimate_frames``
+    together (a run in which a frame has no depth is done again frame by frame).  indices: these samples, in this
+    order (default: all).
+
+    Returns {"samples": [{"index", "category_str", "metrics": {name: float}, "position_error", "rotation_error",
+    "correct": {name: 0 | 1}}], "stats": {category_str and "all": ``metric_stats`` of the metrics and the two errors},
+    "correct": {name: the share of samples with the flag}, "skipped": [{"index", "category_str", "reason"}]} -- a sample
+    whose category has no pipeline, or whose masked depth is empty (``NoDepthError``), is skipped."""
+    metrics_config = DEFAULT_METRICS if metrics_config is None else metrics_config
+    pose_thresholds = DEFAULT_POSE_THRESHOLDS if pose_thresholds is None else pose_thresholds
+    symmetry_axes = {} if symmetry_axes is None else symmetry_axes
+    K = int(frames_per_call)
+    if K < 1:
+        raise ValueError(f"frames_per_call={frames_per_call} must be >= 1")
+    config = getattr(dataset, "_config", {})
+    if config.get("normalize_pointcloud", False):
+        raise ValueError("evaluate_annotated needs a dataset with normalize_pointcloud: False (a normalised sample's "
+                         "position is shifted by its point cloud's centroid)")
+    convention = config.get("camera_convention", "opengl")
+    indices = list(range(len(dataset))) if indices is None else [int(i) for i in indices]
+    skipped, entries = [], {}
+    for group in _annotated_groups(dataset, indices, pipelines, K, skipped):
+        frames = dataset.samples(group) if hasattr(dataset, "samples") else [dataset[i] for i in group]
+        category = frames[0]["category_str"]
+        pipeline = pipelines[category] if isinstance(pipelines, dict) else pipelines
+        estimates = None
+        if len(frames) > 1:
+            try:
+                rows = pipeline.estimate_frames(torch.stack([f["depth"] for f in frames]),
+                                                torch.stack([f["mask"] for f in frames]),
+                                                shape_optimization=shape_optimization)
+                estimates = [tuple(r[k:k + 1] for r in rows) for k in range(len(frames))]
+            except NoDepthError:
+                estimates = None      # which frame is empty is not known: one by one below
+        for k, (i, frame) in enumerate(zip(group, frames)):
+            if estimates is not None:
+                estimate = estimates[k]
+            else:
+                try:     # the pipeline masks its depth argument in place; the sample stays as loaded
+                    estimate = pipeline(frame["depth"].clone(), frame["mask"], frame["color"],
+                                        shape_optimization=shape_optimization)
+                except NoDepthError:
+                    skipped.append({"index": i, "category_str": category, "reason": "no valid depth under the mask"})
+                    continue
+            entries[i] = _annotated_entry(pipeline, dataset, i, frame, estimate, convention, samples, seed,
+                                          metrics_config, pose_thresholds, symmetry_axes.get(category))
+    done = [entries[i] for i in indices if i in entries]
+    rows = lambda es: [dict(e["metrics"], position_error=e["position_error"], rotation_error=e["rotation_error"])
+                       for e in es]
+    stats = {c: metric_stats(rows([e for e in done if e["category_str"] == c]))
+             for c in dict.fromkeys(e["category_str"] for e in done)}
+    stats["all"] = metric_stats(rows(done))
+    correct = {name: (sum(e["correct"][name] for e in done) / len(done) if done else float("nan"))
+               for name in pose_thresholds}
+    order = {i: n for n, i in enumerate(indices)}
+    return {"samples": done, "stats": stats, "correct": correct,
+            "skipped": sorted(skipped, key=lambda s: order[s["index"]])}
+
+
+def _annotated_entry(pipeline, dataset, index: int, frame: dict, estimate: tuple, convention: str, samples: int,
+                     seed: int, metrics_config: dict, pose_thresholds: dict, symmetry_axis: Optional[int]) -> dict:
+    position, orientation, scale, latent = estimate
+    out_mesh = pipeline.generate_mesh(latent, scale, True)
+    if out_mesh is None:
+        raise KeyError("evaluate_annotated: the pipeline's config has no iso_threshold, so it generates no mesh")
+    out_mesh.position = position[0].detach()
+    out_mesh.orientation = orientation[0].detach()
+    gt_position = change_position_camera_convention(frame["position"], convention, "opengl")
+    gt_orientation = change_orientation_camera_convention(frame["quaternion"], convention, "opengl")
+    gt_mesh = dataset.load_mesh(frame["obj_path"])
+    gt_mesh.position = gt_position
+    gt_mesh.orientation = gt_orientation
+    gt_pts = sample_points([gt_mesh], samples, seed)[0]
+    out_pts = sample_points([out_mesh], samples, seed)[0]
+    metrics = evaluate_metrics(gt_pts, out_pts, metrics_config)
+    position_error, rotation_error = pose_errors(gt_position, gt_orientation, position[0], orientation[0],
+                                                 symmetry_axis)
+    correct = {name: int(correct_thresh(gt_position, position[0], gt_orientation, orientation[0],
+                                        position_threshold=metres, degree_threshold=degrees,
+                                        rotational_symmetry_axis=symmetry_axis))
+               for name, (degrees, metres) in pose_thresholds.items()}
+    return {"index": index, "category_str": frame["category_str"], "metrics": metrics,
+            "position_error": position_error, "rotation_error": rotation_error, "correct": correct}

@@ -14,7 +14,7 @@ import torch
 from . import _lib
 from .pipeline import quaternion_apply
 
-__all__ = ["Mesh", "extract_mesh", "sample_points", "render_mesh_depth", "draw_depth_geometry"]
+__all__ = ["Mesh", "extract_mesh", "sample_points", "render_mesh_depth", "draw_depth_geometry", "visible_mask"]
 
 
 class Mesh:
@@ -539,3 +539,45 @@ def draw_depth_geometry(obj: Mesh, camera) -> torch.Tensor:
     down, looking along +z), 0 where no triangle is seen, back faces shown.  Skew (``camera.s != 0``) raises
     ``ValueError``: the rasteriser has no skew term, as ``ray_setup`` in render.hip has none."""
     return render_mesh_depth(obj, camera, convention="open3d")[0]
+
+
+def visible_mask(rendered: torch.Tensor, observed: torch.Tensor, margin: float = 0.01, return_masked: bool = False,
+                 return_counts: bool = False):
+    """The instance mask of annotated frames on the GPU (``sdfr_visible_mask``, csrc/annotate.hip; the reference's
+    ``AnnotatedRedwoodDataset._compute_mask``, redwood_dataset.py:262-275): ``(rendered != 0) & ~((observed != 0) &
+    (observed < rendered - margin))`` -- the pixels the ground-truth mesh covers, minus those where the sensor saw
+    something more than `margin` in front of it.
+
+    rendered, observed: (H,W) or (B,H,W) float32 CUDA tensors of one shape; a contiguous view is read where it is, at
+    whatever 4-byte offset into a larger buffer it starts (anything else is copied first).  Returns the
+    ``torch.bool`` mask of that shape; with `return_masked` also ``where(mask, observed, 0)`` float32; with
+    `return_counts` also (B,4) (or (4,)) int32 on the device: covered, visible, occluded, valid (visible with a depth
+    reading: the points of the masked point cloud).  One launch sequence for all images, nothing read back."""
+    if rendered.shape != observed.shape or rendered.dim() not in (2, 3):
+        raise ValueError(f"rendered {tuple(rendered.shape)} and observed {tuple(observed.shape)}: two (H,W) or (B,H,W) "
+                         "tensors of one shape expected")
+    for name, t in (("rendered", rendered), ("observed", observed)):
+        if not t.is_cuda or t.dtype != torch.float32:
+            raise TypeError(f"{name} must be a CUDA float32 tensor (sdfest_amd has no CPU path)")
+    if rendered.device != observed.device:
+        raise ValueError("rendered and observed must live on one device")
+    margin = float(margin)
+    if not (0.0 <= margin < float("inf")):
+        raise ValueError(f"margin={margin} must be >= 0 and finite")
+    single = rendered.dim() == 2
+    shape = tuple(rendered.shape)
+    B, H, W = (1,) + shape if single else shape
+    if H < 1 or W < 1:
+        raise ValueError(f"images of {H} x {W} pixels")
+    dev = rendered.device
+    rendered, observed = rendered.detach().contiguous(), observed.detach().contiguous()
+    mask = torch.empty(shape, dtype=torch.bool, device=dev)
+    masked = torch.empty(shape, dtype=torch.float32, device=dev) if return_masked else None
+    counts = torch.empty((B, 4), dtype=torch.int32, device=dev) if return_counts else None
+    if B:
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().sdfr_visible_mask(_ptr(rendered), _ptr(observed), B, H, W, margin, _ptr(mask),
+                                                    _ptr(masked), _ptr(counts), dev.index,
+                                                    torch.cuda.current_stream(dev).cuda_stream), "sdfr_visible_mask")
+    out = (mask,) + ((masked,) if return_masked else ()) + (((counts[0] if single else counts),) if return_counts else ())
+    return out[0] if len(out) == 1 else out

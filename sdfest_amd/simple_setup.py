@@ -318,7 +318,6 @@ class SDFPipeline:
         ``best_estimates()`` returns it.
         ``NoDepthError`` for an (object, view) without a valid depth pixel is raised AFTER the call's work was
         enqueued (the counts are read behind the launches), where the reference raises before optimising (:780-781)."""
-        dev = self._dev
         if depth_images.dim() == 2 and masks.dim() == 3 and tuple(masks.shape[1:]) == tuple(depth_images.shape):
             V = 1
         elif (depth_images.dim() == 3 and masks.dim() == 4 and masks.shape[1] == depth_images.shape[0]
@@ -331,50 +330,97 @@ class SDFPipeline:
             raise NotImplementedError("estimate_objects with several views initialises from each object's first view "
                                       f"(init_view: first), not init_view: {self.config.get('init_view')}")
         K = int(masks.shape[0])
+        loop = self._objects_loop(K, V, shape_optimization)
+        with torch.no_grad():
+            H, W = loop.H, loop.W
+            loop.rebind(depth_images.reshape(V, H, W), camera_positions, camera_orientations,
+                        masks=masks.reshape(K, V, H, W), far_field=self._far_field)
+            return self._run_objects(loop, prior_orientation_distribution, training_orientation_distribution)
+
+    def _objects_loop(self, K: int, V: int, shape_optimization: bool) -> MultiObjectRenderAndCompare:
+        """the K-row loop of ``estimate_objects`` and ``estimate_frames``, built on first use and kept"""
         track = self.result_selection_strategy == "best_inlier_ratio"
         key = (K, bool(shape_optimization), V, track)
         loop = self._multi_loops.get(key)
         if loop is None:
             self._bounded(self._multi_loops, self.MAX_CACHED_LOOPS)
             loop = self._multi_loops[key] = MultiObjectRenderAndCompare(
-                self.vae, self.cam, self.config, K, shape_optimization=shape_optimization, device=dev,
+                self.vae, self.cam, self.config, K, shape_optimization=shape_optimization, device=self._dev,
                 sdf_grad_mode=self.sdf_grad_mode, views=V, track_inliers=track)
-        with torch.no_grad():
-            H, W = loop.H, loop.W
-            loop.rebind(depth_images.reshape(V, H, W), camera_positions, camera_orientations,
-                        masks=masks.reshape(K, V, H, W), far_field=self._far_field)
-            first = loop.target.view(K, V, H, W)[:, 0]     # every object's first view: K contiguous images
-            resident = None
-            if self._resident_wanted and self._nn_init_override is None and isinstance(self.init_network, SDFPoseNet):
-                # (per (K, V): its captured sequence holds the addresses of K images V images apart)
-                if (K, V) not in self._resident_objects:
-                    self._bounded(self._resident_objects, self.MAX_CACHED_LOOPS)
-                    try:
-                        self._resident_objects[K, V] = ResidentInit(
-                            self.init_network, self.cam, K, dict(self.config, init_view="first"),
-                            normalize_pose=bool(self.init_config.get("normalize_pose", False)), objects=True)
-                    except NotImplementedError:
-                        self._resident_objects[K, V] = None
-                resident = self._resident_objects[K, V]
-            if resident is not None:
-                latent, position, scale, orientation = resident(first, loop.cam_pos, loop.cam_quat,
-                                                                prior_orientation_distribution,
-                                                                training_orientation_distribution)
-            else:     # the host-driven form, object by object
-                rows = []
-                for k in range(K):
-                    prior = prior_orientation_distribution[k:k + 1] if prior_orientation_distribution is not None else None
-                    rows.append(self._nn_init(first[k:k + 1], loop.cam_pos[0:1], loop.cam_quat[0:1], prior,
-                                              training_orientation_distribution))
-                latent, position, scale, orientation = (torch.cat([r[i].reshape(1, -1) for r in rows]) for i in range(4))
-                scale = scale.reshape(K)
-            out = loop(position, orientation, scale, latent)
-            self._last_multi_loop = loop
-            if resident is not None and resident.empty_views():
-                raise NoDepthError
-            if V > 1 and bool((loop.counts == 0).any()):     # (the initialisation saw the first views only)
-                raise NoDepthError
+        return loop
+
+    def _run_objects(self, loop: MultiObjectRenderAndCompare, prior_orientation_distribution,
+                     training_orientation_distribution) -> tuple:
+        """initialise the K rows of a bound loop from each row's first view and run it (under ``torch.no_grad``)"""
+        K, V, H, W = loop.K, loop.V, loop.H, loop.W
+        first = loop.target.view(K, V, H, W)[:, 0]     # every object's first view: K contiguous images
+        resident = None
+        if self._resident_wanted and self._nn_init_override is None and isinstance(self.init_network, SDFPoseNet):
+            # (per (K, V): its captured sequence holds the addresses of K images V images apart)
+            if (K, V) not in self._resident_objects:
+                self._bounded(self._resident_objects, self.MAX_CACHED_LOOPS)
+                try:
+                    self._resident_objects[K, V] = ResidentInit(
+                        self.init_network, self.cam, K, dict(self.config, init_view="first"),
+                        normalize_pose=bool(self.init_config.get("normalize_pose", False)), objects=True)
+                except NotImplementedError:
+                    self._resident_objects[K, V] = None
+            resident = self._resident_objects[K, V]
+        if resident is not None:
+            latent, position, scale, orientation = resident(first, loop.cam_pos, loop.cam_quat,
+                                                            prior_orientation_distribution,
+                                                            training_orientation_distribution)
+        else:     # the host-driven form, object by object
+            rows = []
+            for k in range(K):
+                prior = prior_orientation_distribution[k:k + 1] if prior_orientation_distribution is not None else None
+                rows.append(self._nn_init(first[k:k + 1], loop.cam_pos[0:1], loop.cam_quat[0:1], prior,
+                                          training_orientation_distribution))
+            latent, position, scale, orientation = (torch.cat([r[i].reshape(1, -1) for r in rows]) for i in range(4))
+            scale = scale.reshape(K)
+        out = loop(position, orientation, scale, latent)
+        self._last_multi_loop = loop
+        if resident is not None and resident.empty_views():
+            raise NoDepthError
+        if V > 1 and bool((loop.counts == 0).any()):     # (the initialisation saw the first views only)
+            raise NoDepthError
         return out
+
+    def estimate_frames(self, depth_images: torch.Tensor, masks: torch.Tensor, shape_optimization: bool = True,
+                        prior_orientation_distribution: Optional[torch.Tensor] = None,
+                        training_orientation_distribution: Optional[torch.Tensor] = None) -> tuple:
+        """K DIFFERENT frames with one object each -- what a caller of the reference does with K
+        ``pipeline(depth_k, mask_k, color_k)`` calls over a sequence or a dataset --, refined side by side as the K rows
+        of ``estimate_objects``' loop (the same cached ``MultiObjectRenderAndCompare`` and initialisation: a loop built
+        by either call serves the other).  The camera of every frame sits at the origin.
+
+        depth_images (K,H,W): masked and far-field-clipped IN PLACE, as ``__call__`` does (pass a copy if the full
+        depth is used afterwards); masks (K,H,W) bool.  prior_orientation_distribution (K,C) /
+        training_orientation_distribution (C,): one row per frame.  Returns position (K,3), orientation (K,4), scale
+        (K,), latent (K,L): row k follows ``estimate_objects(depth_images[k], masks[k][None])`` as that follows
+        ``__call__`` (its docstring); K copies of one frame under K masks are ``estimate_objects(frame, masks)`` bit for
+        bit.  ``best_estimates()`` works as after ``estimate_objects``.  ``ValueError`` for other shapes;
+        ``NoDepthError`` for a frame without a valid pixel, raised AFTER the call's work was enqueued."""
+        if depth_images.dim() != 3 or tuple(masks.shape) != tuple(depth_images.shape):
+            raise ValueError("depth_images (K,H,W) and masks (K,H,W) are expected, got "
+                             f"{tuple(depth_images.shape)} and {tuple(masks.shape)}")
+        K, H, W = (int(x) for x in depth_images.shape)
+        if K < 1 or (H, W) != (int(self.cam.height), int(self.cam.width)):
+            raise ValueError(f"depth_images of shape {(K, H, W)}: K >= 1 images of the camera's "
+                             f"{int(self.cam.height)} x {int(self.cam.width)} pixels are expected")
+        dev = self._dev
+        loop = self._objects_loop(K, 1, shape_optimization)
+        with torch.no_grad():
+            if (depth_images.is_cuda and depth_images.dtype is torch.float32 and depth_images.is_contiguous()
+                    and depth_images.device == dev):
+                # one image per row already: preprocessed in place on the way into the loop's buffers
+                loop.rebind(depth_images, masks=masks, far_field=self._far_field)
+            else:     # any other tensor: the reference's two in-place assignments, then the copy
+                depth_images[~masks.to(device=depth_images.device, dtype=torch.bool)] = 0
+                if self._far_field is not None:
+                    depth_images[depth_images > self._far_field] = 0
+                loop.rebind(depth_images.to(dev, torch.float32).contiguous())
+            return self._run_objects(loop, prior_orientation_distribution, training_orientation_distribution)
 
     # ---- N orientation hypotheses of one object ----------------------------------------------------------------
     def _hypothesis_loop(self, depth_images: torch.Tensor, masks: torch.Tensor, hypotheses: int,

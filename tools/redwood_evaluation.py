@@ -1,0 +1,82 @@
+#!/usr/bin/env python3
+"""Evaluation on the annotated Redwood frames from the command line (sdfest_amd.evaluation.evaluate_annotated): what
+the reference's ``estimation/configs/redwood_evaluation.yaml`` configures -- every annotated frame's depth and mask
+through the category's SDFPipeline, the estimate's mesh against the annotated mesh, the reconstruction metrics, the pose
+errors and the pose-threshold flags -- written as ONE JSON document {"samples", "stats", "correct", "skipped"}.  No
+visualisation and no logs.
+
+    python tools/redwood_evaluation.py --config cfg.json [--out result.json]
+
+--config: a JSON file of the shape of the reference's config:
+    category_configs   {category_str: a JSON file, or a mapping} -- one pipeline per category; a category without an
+                       entry is skipped.  An entry may hold ``vae_weights`` / ``init_weights`` (.npz state dicts) and
+                       any of the pipeline keys below, which then hold for that category only.
+    metrics            the reference's ``metrics:`` mapping (default: sdfest_amd.evaluation.DEFAULT_METRICS)
+    samples            points per mesh (default 20000)
+    the dataset keys   root_dir, ann_dir, camera_convention, scale_convention, remap_x_axis, remap_y_axis,
+                       category_str, occlusion_margin, camera (default: the Redwood camera, 640 x 480, f = 525)
+    pipeline keys      threshold, max_iterations, iso_threshold, shape_optimization
+    of this project    seed, frames_per_call, symmetry_axes {category_str: 0 | 1 | 2}, pose_thresholds {name:
+                       [degrees, metres]}, indices
+The decoder's architecture is the mug decoder's of tests/golden (``vae_weights``: a state dict for it); the
+initialisation network's trained weights are not part of either repository, so without ``init_weights`` the stand-in of
+``synthetic.plausible_init_network_state`` answers (as in tools/rendering_evaluation.py).
+"""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+GOLDEN = os.path.join(ROOT, "tests", "golden")
+REDWOOD_CAMERA = {"width": 640, "height": 480, "fx": 525.0, "fy": 525.0, "cx": 319.5, "cy": 239.5, "pixel_center": 0.0}
+DEFAULTS = {"camera": REDWOOD_CAMERA, "threshold": 0.005, "max_iterations": 30, "samples": 20000,
+            "iso_threshold": 0.02, "shape_optimization": True, "seed": 0, "metrics": None, "frames_per_call": 1,
+            "symmetry_axes": None, "pose_thresholds": None, "indices": None, "category_configs": {}}
+DATASET_KEYS = ("root_dir", "ann_dir", "mask_pointcloud", "camera_convention", "scale_convention", "orientation_repr",
+                "orientation_grid_resolution", "remap_x_axis", "remap_y_axis", "category_str", "occlusion_margin",
+                "camera", "device")
+
+
+def load_json(source):
+    if isinstance(source, dict):
+        return source
+    with open(source) as fh:
+        return json.load(fh)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--config", required=True, help="JSON file: category_configs, metrics, samples, the dataset keys")
+    ap.add_argument("--out", help="write the result here instead of standard output")
+    a = ap.parse_args()
+    cfg = dict(DEFAULTS)
+    cfg.update(load_json(a.config))
+    from rendering_evaluation import build_pipeline
+    from sdfest_amd import AnnotatedRedwoodDataset
+    from sdfest_amd.evaluation import evaluate_annotated
+    dataset = AnnotatedRedwoodDataset({k: cfg[k] for k in DATASET_KEYS if k in cfg})
+    pipelines = {}
+    for category, source in cfg["category_configs"].items():
+        own = dict(cfg)
+        own.update(load_json(source))
+        pipelines[category] = build_pipeline(own, own.get("vae_weights", os.path.join(GOLDEN, "mug_decoder_weights.npz")),
+                                             own.get("init_weights"))
+    thresholds = cfg["pose_thresholds"]
+    if thresholds is not None:
+        thresholds = {name: tuple(pair) for name, pair in thresholds.items()}
+    result = evaluate_annotated(pipelines, dataset, int(cfg["samples"]), int(cfg["seed"]), cfg["metrics"], thresholds,
+                                cfg["symmetry_axes"], int(cfg["frames_per_call"]), bool(cfg["shape_optimization"]),
+                                cfg["indices"])
+    text = json.dumps(result)
+    if a.out:
+        with open(a.out, "w") as fh:
+            fh.write(text + "\n")
+    else:
+        print(text)
+
+
+if __name__ == "__main__":
+    main()
