@@ -87,6 +87,8 @@
  *        sdfr_similarity_ransac[_workspace_bytes], sdfr_nocs_sample_indices
  *  13. [unstable] FRAME ANNOTATION: the visibility mask of an annotated RGB-D frame (AnnotatedRedwoodDataset)
  *        sdfr_visible_mask
+ *  14. [unstable] POSE INFORMATION: the Gauss-Newton normal matrix of the depth residual (SDFPipeline.pose_uncertainty)
+ *        sdfr_render_information[_workspace_bytes]
  * (Within the file the groups follow the order in which the reference's code runs; every declaration carries the
  * reference file:line it replaces.)
  */
@@ -1412,6 +1414,39 @@ SDFR_API int sdfr_nocs_sample_indices(const long long* offsets, int K, unsigned 
  * allocation, no host synchronisation: the call can be captured into a graph. */
 SDFR_API int sdfr_visible_mask(const float* rendered, const float* observed, int B, int H, int W, float margin,
                                unsigned char* mask, float* masked, int* counts, int device, void* stream);
+
+/* ==== 14. POSE INFORMATION ==================================================================== */
+/* ---- how well a depth image determines the pose it was rendered at.  The reference's estimator returns a point
+ * estimate only and names an unobservable rotation in its metrics alone (rotational_symmetry_axis); this is the
+ * quantity behind a covariance of (position, rotation, scale): per view, the Gram matrix of the per-pixel feature
+ * vector f = (d0 .. d7, r, 1),
+ *     d   d depth / d (px, py, pz, qx, qy, qz, qw, inv_scale) of the pixel -- the vector sdfr_render_backward
+ *         multiplies by its upstream gradient and sums away, in the same arithmetic
+ *     r   depth - target (fp32)
+ * over the INCLUDED pixels: depth > 0 && target > 0 (the overlap of estimation/simple_setup.py:125), and, for
+ * inlier_threshold > 0, fabsf(target - depth) / target < inlier_threshold (_compute_inlier_ratio, :183-184) with an
+ * IEEE fp32 subtraction and division -- numpy float32 gives the same set.  inlier_threshold = 0: the whole overlap.
+ *   depth   [B][H][W] the rendered estimate at (pos, quat, inv_scale); its non-zero pixels are the hit pixels
+ *   target  [B][H][W] the observation
+ *   gram    [B][10][10] doubles, overwritten: [:8][:8] = J^T J, [:8][8] = J^T r, [8][8] = sum r^2, [9][9] = the number
+ *           of included pixels (exact), [:8][9] = sum d, [8][9] = sum r; exactly symmetric; all zeros for a view
+ *           without an included pixel
+ * Pixels outside the projection of the bounding sphere of the grid's cube (centre pos, radius sqrt(3) / inv_scale) are
+ * not read: no ray hits the grid there, and the forward leaves them 0.
+ * Pose, intrinsics and sdf_view_stride as in sdfr_render_backward.  Two launches on the caller's stream -- the image
+ * tiles of all views, then a fixed-order sum of each view's tile records in double --, no allocation, no host
+ * synchronisation.  Every sum has one order: two calls on the same inputs give the same bits, a view's matrix does not
+ * depend on the other views of the call, and the workspace may hold anything on entry.
+ * B, W, H >= 1 (B <= 65535, W H <= 2^31 - 1), 2 <= R <= 1023, inlier_threshold >= 0 and finite, the workspace 128-byte
+ * and gram 8-byte aligned.  Every argument error -- a NULL pointer and a workspace that is too small included -- is
+ * SDFR_E_INVALID with a message, before anything touches the GPU; _workspace_bytes answers 0 for sizes the call
+ * refuses. */
+SDFR_API size_t sdfr_render_information_workspace_bytes(int B, int W, int H);
+SDFR_API int sdfr_render_information(const float* depth, const float* target, const float* sdf, int R,
+                                     long long sdf_view_stride, const float* pos, const float* quat,
+                                     const float* inv_scale, int B, int W, int H, float cx, float cy, float fx,
+                                     float fy, float inlier_threshold, double* gram, void* workspace,
+                                     size_t workspace_bytes, int device, void* stream);
 
 #ifdef __cplusplus
 }

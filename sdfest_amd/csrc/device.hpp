@@ -28,6 +28,28 @@ __device__ __forceinline__ V3 rot_f(const ViewSetup& s, V3 v) {  // R v
             fmaf(s.rot[6], v.x, fmaf(s.rot[7], v.y, s.rot[8] * v.z)));
 }
 
+// grid-space hit point of a pixel of depth z: the arithmetic of the reference's backward (cu:334-345) in the object
+// frame.  ONE function for the bounds pass and the main pass of a tile: the same instruction sequence on the same
+// inputs chooses the same cell in both.
+struct HitPoint {
+  V3 d;        // unit ray, camera frame
+  V3 o;        // hit point, object frame
+  float t;
+  float gx, gy, gz;
+};
+__device__ __forceinline__ HitPoint hit_point(const ViewSetup& s, int row, int col, float z, float cx, float cy,
+                                              float rfx, float rfy, float isc, float h) {
+  HitPoint p;
+  p.d = pixel_ray(row, col, cx, cy, rfx, rfy);
+  const V3 dobj = rot_t(s, p.d);
+  p.t = z * __builtin_amdgcn_rcpf(-p.d.z);  // -z / d.z   (cu:339)
+  p.o = mk(fmaf(p.t, dobj.x, -s.e[0]), fmaf(p.t, dobj.y, -s.e[1]), fmaf(p.t, dobj.z, -s.e[2]));
+  p.gx = fmaf(p.o.x * isc, h, h);
+  p.gy = fmaf(p.o.y * isc, h, h);
+  p.gz = fmaf(p.o.z * isc, h, h);
+  return p;
+}
+
 // v_min_f32 / v_max_f32 as they are (IEEE mode: the result is the non-NaN operand, a signalling NaN comes out
 // quiet): fminf / fmaxf compile to the same instruction PLUS a canonicalising v_max(x, x) per operand the compiler
 // cannot prove quiet.

@@ -913,28 +913,6 @@ __host__ __device__ constexpr int tile_fixed_bits(int pixels, int table_bits) {
 template <typename Hash> struct HashIs32 { static constexpr bool value = false; };
 template <int SLOTS> struct HashIs32<PairRunHash<SLOTS>> { static constexpr bool value = true; };
 
-// grid-space hit point of a pixel of depth z: the arithmetic of the reference's backward (cu:334-345) in the object
-// frame.  ONE function for the bounds pass and the main pass of a tile: the same instruction sequence on the same
-// inputs chooses the same cell in both.
-struct HitPoint {
-  V3 d;        // unit ray, camera frame
-  V3 o;        // hit point, object frame
-  float t;
-  float gx, gy, gz;
-};
-__device__ __forceinline__ HitPoint hit_point(const ViewSetup& s, int row, int col, float z, float cx, float cy,
-                                              float rfx, float rfy, float isc, float h) {
-  HitPoint p;
-  p.d = pixel_ray(row, col, cx, cy, rfx, rfy);
-  const V3 dobj = rot_t(s, p.d);
-  p.t = z * __builtin_amdgcn_rcpf(-p.d.z);  // -z / d.z   (cu:339)
-  p.o = mk(fmaf(p.t, dobj.x, -s.e[0]), fmaf(p.t, dobj.y, -s.e[1]), fmaf(p.t, dobj.z, -s.e[2]));
-  p.gx = fmaf(p.o.x * isc, h, h);
-  p.gy = fmaf(p.o.y * isc, h, h);
-  p.gz = fmaf(p.o.z * isc, h, h);
-  return p;
-}
-
 // (sum, count) of one forward tile from its record of four per-wave pairs (forward_tile, LOSS): the one association
 // every reader uses
 __device__ __forceinline__ float2 loss_tile_record(const float* __restrict__ part, size_t tile) {

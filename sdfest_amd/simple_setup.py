@@ -32,7 +32,8 @@ from . import _lib
 from .differentiable_renderer import Camera, parse_sdf_grad_mode, render_depth_gpu
 from .mesh import Mesh, extract_mesh
 from .init_network import NoDepthError, ResidentInit, SDFPoseNet, adjust_categorical_posterior, nn_init
-from .pipeline import FusedRenderAndCompare, MultiObjectRenderAndCompare, _selection_strategy, preprocess_depth
+from .pipeline import (FusedRenderAndCompare, MultiObjectRenderAndCompare, _selection_strategy, preprocess_depth,
+                       quaternion_apply, quaternion_invert, quaternion_multiply)
 from .vae import SDFDecoder
 
 __all__ = ["SDFPipeline", "NoDepthError"]
@@ -285,6 +286,7 @@ class SDFPipeline:
                 # (:780-781 -- known only now: the counts were never waited for in front of the launches)
                 raise NoDepthError
         self._last_loop = loop
+        self._last_estimate = loop
         # :583-596 -- "best_inlier_ratio" returns the tensors the reference stored, which its optimiser went on
         # updating in place: the last iterate as well (pipeline._BestEstimate); the snapshot at the best ratio is
         # self.best_estimate()
@@ -380,6 +382,7 @@ class SDFPipeline:
             scale = scale.reshape(K)
         out = loop(position, orientation, scale, latent)
         self._last_multi_loop = loop
+        self._last_estimate = loop
         if resident is not None and resident.empty_views():
             raise NoDepthError
         if V > 1 and bool((loop.counts == 0).any()):     # (the initialisation saw the first views only)
@@ -471,6 +474,7 @@ class SDFPipeline:
             row = sel["row"]
             out = row[0:3][None].clone(), row[3:7][None].clone(), row[7:8].clone(), row[8:][None].clone()
         self._last_multi_loop = loop
+        self._last_estimate = loop
         self._last_hypotheses = dict(loop=loop, index=index, probability=probability)
         return out
 
@@ -568,6 +572,69 @@ class SDFPipeline:
         return dict(index=clone(last["index"]), probability=clone(last["probability"]),
                     inlier_ratio=self._hypothesis_scores(loop)[0].clone(), winner=int(loop.selection["index"].item()),
                     initial=loop.selection["initial"].clone(), final=loop.params.clone())
+
+    def pose_uncertainty(self, inlier_threshold=None, rcond: float = 1e-6, depth_sigma: Optional[float] = None):
+        """How well the last call's observation determines its estimate (``sdfest_amd.uncertainty``): valid after
+        ``__call__``, ``estimate_objects``, ``estimate_frames`` or ``estimate_hypotheses`` (``RuntimeError`` before any of
+        them).  The reference returns a point estimate only and names an unobservable rotation in its metrics alone
+        (rotational_symmetry_axis).
+
+        From the last loop's bound targets and cameras and its final parameters: the final latents are decoded (the
+        batched decode), the estimate is rendered (the forward), ONE ``sdfr_render_information`` call over all K V views
+        gives every view's Gauss-Newton matrix of the depth residual, and each object's views are added in the WORLD
+        tangent -- position (m), rotation vector (rad, ``q <- exp(w / 2) (x) q``), log-scale.  Returns
+        ``uncertainty.PoseUncertainty`` with leading dimension K (1 after ``__call__``; the N rows after
+        ``estimate_hypotheses``): information, covariance, sigma2, rank, position_std, rotation_std_deg, scale_rel_std,
+        unobserved.  A direction the depth does not constrain (a symmetric body's spin) lowers ``rank`` and is listed in
+        ``unobserved`` instead of being inverted.
+        inlier_threshold: None = all overlap pixels; True = the pipeline's ``relative_inlier_threshold``; a number = that
+        relative threshold (simple_setup.py:183-184).  rcond, depth_sigma: ``uncertainty.pose_covariance``.
+        Reads the loop's buffers only: a following call returns what it would have returned."""
+        from .uncertainty import pose_covariance, render_information, tangent_information
+        thr = 0.0 if inlier_threshold is None else float(
+            self._relative_inlier_threshold if inlier_threshold is True else inlier_threshold)
+        with torch.no_grad():
+            v = self._uncertainty_views()
+            K, V = v["K"], v["V"]
+            gram = render_information(v["depth"], v["target"], v["sdf"], v["position"], v["orientation"], v["inv_scale"],
+                                      self.cam, thr)
+            info = tangent_information(gram, v["orientation"], v["inv_scale"], v["camera_orientations"])
+            per_object = lambda t: t.reshape((K, V) + tuple(t.shape[1:])).sum(dim=1)
+            return pose_covariance(per_object(info), per_object(gram[:, 8, 8]), per_object(gram[:, 9, 9]), rcond=rcond,
+                                   depth_sigma=depth_sigma)
+
+    def _uncertainty_views(self) -> Dict:
+        """the K V views ``pose_uncertainty`` looks at, object-major (view k V + v is object k from camera v, as in the
+        loops): the last loop's targets and cameras, its final parameters as camera-frame poses
+        (pipeline.RenderAndCompare.losses), the decoded volumes and the rendered estimate"""
+        from .differentiable_renderer import forward_raw
+        loop = getattr(self, "_last_estimate", None)
+        if loop is None:
+            raise RuntimeError("pose_uncertainty() needs an estimate: call the pipeline (or estimate_objects, "
+                               "estimate_frames, estimate_hypotheses) first")
+        if isinstance(loop, MultiObjectRenderAndCompare):
+            K, params = loop.K, loop.params
+        else:
+            if loop.group is not None:
+                raise NotImplementedError("pose_uncertainty() after a loop sharded over ranks")
+            K, params = 1, loop.params[None]
+        V, cam_pos, cam_quat = loop.V, loop.cam_pos, loop.cam_quat
+        H, W = int(self.cam.height), int(self.cam.width)
+        with torch.no_grad():
+            position, scale, latent = params[:, 0:3], params[:, 7], params[:, 8:]
+            orientation = params[:, 3:7] / torch.linalg.norm(params[:, 3:7], dim=-1, keepdim=True)
+            q_w2c = quaternion_invert(cam_quat)[None].expand(K, V, 4)
+            pos_c = quaternion_apply(q_w2c, position[:, None, :] - cam_pos[None]).reshape(K * V, 3).contiguous()
+            quat_c = quaternion_multiply(q_w2c, orientation[:, None, :].expand(K, V, 4)).reshape(K * V, 4).contiguous()
+            inv_scale = (1.0 / scale)[:, None].expand(K, V).reshape(K * V).contiguous()
+            sdf = self.vae.decode(latent.contiguous())[:, 0]
+            # one object: its views share the grid; else every view its own copy
+            sdf = (sdf[0] if K == 1 else sdf.repeat_interleave(V, dim=0) if V > 1 else sdf).contiguous()
+            fx, fy, cx, cy, _ = self.cam.get_pinhole_camera_parameters(0.5)
+            depth = forward_raw(sdf, pos_c, quat_c, inv_scale, W, H, cx, cy, fx, fy, self.config["threshold"])
+        return dict(K=K, V=V, depth=depth, target=loop.target.reshape(K * V, H, W), sdf=sdf, position=pos_c,
+                    orientation=quat_c, inv_scale=inv_scale,
+                    camera_orientations=cam_quat[None].expand(K, V, 4).reshape(K * V, 4))
 
     def best_estimates(self):
         """K entries (ratio, 1-based iteration, (position, orientation, scale, latent)), one per object: the parameters
