@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._graphs import BoundedCache, capture
 from .differentiable_renderer import Camera
 from .pipeline import depth_to_pointcloud, quaternion_apply, quaternion_multiply
 from .so3grid import SO3Grid
@@ -434,7 +435,7 @@ class ResidentInit:
             self.hyp_index = torch.zeros(self.hypotheses, **i32)
             self.hyp_prob = torch.zeros(self.hypotheses, **f32)
             self.params_h = torch.zeros((self.hypotheses, 8 + net.shape_dimension), **f32)
-        self._graphs = {}
+        self._graphs = BoundedCache(4)      # (a caller that hands other tensors every call: re-capture, no hoard)
         self._host_counts = torch.zeros(self.V, dtype=torch.int32).pin_memory()
         self._counts_event = None
 
@@ -538,24 +539,15 @@ class ResidentInit:
             self.prior.copy_(prior_orientation_distribution.reshape(self.V, self.C))
         if has_train:
             self.train_prior.copy_(training_orientation_distribution.reshape(self.C))
+        def sequence():
+            self._sequence(depth, cam_pos, cam_quat, has_prior, has_train)
+
         if use_graph:
             key = (depth.data_ptr(), cam_pos.data_ptr(), cam_quat.data_ptr(), has_prior, has_train)
-            g = self._graphs.get(key)
-            if g is None:
-                side = torch.cuda.Stream(self.dev)        # warm-up on a side stream (lazy module loads), then capture
-                side.wait_stream(torch.cuda.current_stream(self.dev))
-                with torch.cuda.stream(side):
-                    self._sequence(depth, cam_pos, cam_quat, has_prior, has_train)
-                torch.cuda.current_stream(self.dev).wait_stream(side)
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    self._sequence(depth, cam_pos, cam_quat, has_prior, has_train)
-                if len(self._graphs) >= 4:      # (a caller that hands other tensors every call: re-capture, no hoard)
-                    self._graphs.pop(next(iter(self._graphs)))
-                self._graphs[key] = g
-            g.replay()
+            # (warmed up on a side stream -- lazy module loads --, then captured; the sequence keeps no state between calls)
+            self._graphs.get_or_build(key, lambda: capture(self.dev, (sequence,), sequence)[0]).replay()
         else:
-            self._sequence(depth, cam_pos, cam_quat, has_prior, has_train)
+            sequence()
         # the counts for the empty-cloud check, without waiting for them here
         self._host_counts.copy_(self.counts_all, non_blocking=True)
         self._counts_event = torch.cuda.Event()

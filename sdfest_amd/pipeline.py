@@ -14,7 +14,7 @@ from typing import Dict, List, Optional, Sequence
 
 import torch
 
-from . import _lib
+from . import _graphs, _lib
 from .differentiable_renderer import SDF_GRAD_EXACT, Camera, render_depth_batch
 from .losses import pc_loss_batch, point_constraint_loss
 
@@ -119,6 +119,48 @@ def preprocess_depth(depth_images: torch.Tensor, masks: Optional[torch.Tensor], 
     if copy_to is not None and not same:
         copy_to[0].copy_(depth_images[copy_to[1]:copy_to[2]])
     return depth_images
+
+
+# Adam's learning rates as the update kernels take them: position, orientation, scale, latent
+_ADAM_RATES = (1e-3, 1e-2, 1e-3, 1e-2)
+
+
+def _copy_cameras(cam_pos: torch.Tensor, cam_quat: torch.Tensor, positions: Optional[torch.Tensor],
+                  orientations: Optional[torch.Tensor]) -> None:
+    """a new observation's cameras into a loop's buffers (V,3) / (V,4), in place; default: the origin, looking along
+    the identity quaternion"""
+    if positions is None:
+        cam_pos.zero_()
+    else:
+        cam_pos.copy_(positions.reshape(cam_pos.shape))
+    if orientations is None:
+        cam_quat.zero_()
+        cam_quat[:, 3] = 1.0
+    else:
+        cam_quat.copy_(orientations.reshape(cam_quat.shape))
+
+
+def _target_to_points(loop, views: int) -> None:
+    """the point clouds of a loop's first `views` target images, rebuilt on the device into the buffers its captured
+    graphs already point at (``sdfr_depth_to_points_resident``: counts and offsets stay on the device)"""
+    fx, fy, cx0, cy0, _ = loop.cam.get_pinhole_camera_parameters(0.0)
+    loop.check(loop.L.sdfr_depth_to_points_resident(
+        loop.target.data_ptr(), views, loop.W, loop.H, _lib.ABI["SDFR_POINT_ORDER_TILED"], 1.0 / fx,
+        1.0 / fy, cx0, cy0, loop.counts.data_ptr(), loop.offsets.data_ptr(), loop.ws_points.data_ptr(),
+        loop.ws_points.numel(), loop.points.data_ptr(), loop.dev.index, loop._stream()),
+        "sdfr_depth_to_points_resident")
+
+
+def _capture_iterations(loop, iteration, state, warmup=None, **mode):
+    """(graph of one `iteration`, graph of ``loop.graph_iterations`` of them -- None where that is one), captured
+    behind a warm-up iteration (lazy module loads) with the run's `state` put back (``_graphs.capture``)"""
+    def many():
+        for _ in range(loop.graph_iterations):
+            iteration()
+
+    sequences = (iteration, many) if loop.graph_iterations > 1 else (iteration,)
+    graphs = _graphs.capture(loop.dev, sequences, warmup or iteration, state, **mode)
+    return graphs[0], graphs[1] if len(graphs) > 1 else None
 
 
 class RenderAndCompare:
@@ -485,6 +527,11 @@ class FusedRenderAndCompare:
         self.quat_c = torch.empty((V, 4), **f32)
         self.inv_scale = torch.empty((V,), **f32)
         self.scale_v = torch.empty((V,), **f32)
+        # the argument runs the tail launches and the Adam step share (every buffer keeps its address for good)
+        self._view_poses = (self.pos_c.data_ptr(), self.quat_c.data_ptr(), self.inv_scale.data_ptr(),
+                            self.scale_v.data_ptr())
+        self._adam = (self.params.data_ptr(), self.grads.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
+                      self.step.data_ptr(), n, *_ADAM_RATES, int(self.shape_opt))
         # (the gradient image and the per-point arrays exist only when the losses run as kernels of their own)
         self.grad_est = None if self.fuse_depth_loss else torch.empty((V, H, W), **f32)
         self.loss_depth = torch.zeros((V,), **f32)
@@ -530,7 +577,9 @@ class FusedRenderAndCompare:
         self._con_points = torch.zeros(8, **f32)
         self.pc_source = None
         self.pc_weight = 0.0
-        self._graphs = {}
+        # (at most 4 sets: a caller whose constraint weight changes from call to call re-captures instead of
+        # collecting graphs without bound)
+        self._graphs = _graphs.BoundedCache(4)
         self.graph = self.graph_many = self.graph_tail = None
         self.bound = False
         if depth_images is not None:
@@ -551,27 +600,14 @@ class FusedRenderAndCompare:
         if tuple(depth_images.shape) != (self.V_all, self.H, self.W):
             raise ValueError(f"depth_images must have shape {(self.V_all, self.H, self.W)}, "
                              f"got {tuple(depth_images.shape)}")
-        L, d, st = self.L, self.dev.index, self._stream()
         b, e = self.view_begin, self.view_end
         with torch.no_grad():
             if masks is not None or far_field is not None:
                 preprocess_depth(depth_images, masks, far_field, copy_to=(self.target, b, e))
             else:
                 self.target.copy_(depth_images[b:e])
-            if camera_positions is None:
-                self.cam_pos_all.zero_()
-            else:
-                self.cam_pos_all.copy_(camera_positions.reshape(self.V_all, 3))
-            if camera_orientations is None:
-                self.cam_quat_all.zero_()
-                self.cam_quat_all[:, 3] = 1.0
-            else:
-                self.cam_quat_all.copy_(camera_orientations.reshape(self.V_all, 4))
-            fx, fy, cx0, cy0, _ = self.cam.get_pinhole_camera_parameters(0.0)
-            self.check(L.sdfr_depth_to_points_resident(
-                self.target.data_ptr(), self.V, self.W, self.H, _lib.ABI["SDFR_POINT_ORDER_TILED"], 1.0 / fx,
-                1.0 / fy, cx0, cy0, self.counts.data_ptr(), self.offsets.data_ptr(), self.ws_points.data_ptr(),
-                self.ws_points.numel(), self.points.data_ptr(), d, st), "sdfr_depth_to_points_resident")
+            _copy_cameras(self.cam_pos_all, self.cam_quat_all, camera_positions, camera_orientations)
+            _target_to_points(self, self.V)
             if point_constraint is not None:
                 src, tgt, wgt = point_constraint
                 self._con_points[0:3].copy_(torch.as_tensor(src).reshape(3))
@@ -598,10 +634,6 @@ class FusedRenderAndCompare:
         self._sums_open = False
 
     def _keep_graphs(self):
-        # (at most 4 sets: a caller whose constraint weight changes from call to call re-captures instead of
-        # collecting graphs without bound)
-        if self._graph_key not in self._graphs and len(self._graphs) >= 4:
-            self._graphs.pop(next(iter(self._graphs)))
         self._graphs[self._graph_key] = (self.graph, self.graph_many, self.graph_tail, self.graph_whole_one,
                                          self.graph_whole)
 
@@ -665,7 +697,7 @@ class FusedRenderAndCompare:
             # iteration were left by the previous tail (or by _poses_to_views before the first one)
             # (the depth loss values are reduced inside the backward's launch: no launch between the image kernels)
             if self.fused_render:
-                return self._iteration_one_launch(L, d, st, p, g, sdf)
+                return self._iteration_one_launch(L, d, st, p, sdf)
             self.plan.forward_l1(sdf, self.pos_c, self.quat_c, self.inv_scale, self.cfg["threshold"], self.target,
                                  prepare_backward=True, defer_loss=self.defer_loss)
             self.loss_depth = self.plan.loss
@@ -679,16 +711,11 @@ class FusedRenderAndCompare:
                 self.check(L.sdfr_decoder_backward_latent_deferred(
                     self.dec._h, self.latent.data_ptr(), self.tape.data_ptr(), g_sdf.data_ptr(), self.ws_dec.data_ptr(),
                     self.ws_dec.numel(), st, ctypes.byref(t_mid)), "sdfr_decoder_backward_latent_deferred")
-            con = self.pc_source is not None
             self.check(L.sdfr_loop_tail(
-                p, g, self.m.data_ptr(), self.v.data_ptr(), self.step.data_ptr(), 8 + self.Lz, 1e-3, 1e-2, 1e-3, 1e-2,
-                int(self.shape_opt), self.cam_pos.data_ptr(), self.cam_quat.data_ptr(), self.V,
+                *self._adam, self.cam_pos.data_ptr(), self.cam_quat.data_ptr(), self.V,
                 self.plan.workspace.data_ptr(), self.plan.partials_offset, self.W, self.H, self.ws_pc.data_ptr(),
-                self.offsets.data_ptr(), self.max_pts, self.pos_c.data_ptr(), self.quat_c.data_ptr(),
-                self.inv_scale.data_ptr(), self.scale_v.data_ptr(), self.loss_pc.data_ptr(),
-                self.pc_source.data_ptr() if con else None, self.pc_target.data_ptr() if con else None,
-                self.pc_weight if con else 0.0, self.loss_con.data_ptr() if con else None,
-                self.dec._h if t_mid is not None else None, t_mid, d, st), "sdfr_loop_tail")
+                self.offsets.data_ptr(), self.max_pts, *self._view_poses, self.loss_pc.data_ptr(),
+                *self._constraint_args(), self.dec._h if t_mid is not None else None, t_mid, d, st), "sdfr_loop_tail")
             self._inliers(L, p, d, st)
             return
         self._poses_to_views(st)
@@ -778,12 +805,10 @@ class FusedRenderAndCompare:
             self.check(L.sdfr_decoder_backward_latent(self.dec._h, self.latent.data_ptr(), self.tape.data_ptr(),
                                                       g_sdf.data_ptr(), 1, g + 32, self.ws_dec.data_ptr(),
                                                       self.ws_dec.numel(), st), "sdfr_decoder_backward_latent")
-        self.check(L.sdfr_adam_step(p, g, self.m.data_ptr(), self.v.data_ptr(), self.step.data_ptr(),
-                                    8 + self.Lz, 1e-3, 1e-2, 1e-3, 1e-2, int(self.shape_opt), d, st),
-                   "sdfr_adam_step")
+        self.check(L.sdfr_adam_step(*self._adam, d, st), "sdfr_adam_step")
         self._inliers(L, p, d, st)
 
-    def _iteration_one_launch(self, L, d, st, p, g, sdf):
+    def _iteration_one_launch(self, L, d, st, p, sdf):
         """The tail form with the render pair as ONE launch (``fused_render``): [decoder] -> render forward + backward +
         the sampler's blocks (``sdfr_render_step_fused_l1_pc``; the depth term's sums come out unscaled, beside the view's
         overlap count) -> [decoder VJP on  point-cloud volume + k depth volume, which it clears afterwards] -> the tail
@@ -804,16 +829,12 @@ class FusedRenderAndCompare:
                 self.dec._h, self.latent.data_ptr(), self.tape.data_ptr(), g_pc.data_ptr(), plan.g_depth.data_ptr(),
                 self.V, ws + cnt_off, self.cfg["depth_weight"], self.ws_dec.data_ptr(), self.ws_dec.numel(), st,
                 ctypes.byref(t_mid)), "sdfr_decoder_backward_latent_deferred_scaled")
-        con = self.pc_source is not None
         self.check(L.sdfr_loop_tail_fused(
-            p, g, self.m.data_ptr(), self.v.data_ptr(), self.step.data_ptr(), 8 + self.Lz, 1e-3, 1e-2, 1e-3, 1e-2,
-            int(self.shape_opt), self.cam_pos.data_ptr(), self.cam_quat.data_ptr(), self.V, ws, plan.partials_offset,
+            *self._adam, self.cam_pos.data_ptr(), self.cam_quat.data_ptr(), self.V, ws, plan.partials_offset,
             cnt_off, L.sdfr_render_fused_tile_loss_offset(self.R, self.V, self.W, self.H), self.cfg["depth_weight"],
             plan.loss.data_ptr(), self.W, self.H, self.ws_pc.data_ptr(), self.offsets.data_ptr(), self.max_pts,
-            self.pos_c.data_ptr(), self.quat_c.data_ptr(), self.inv_scale.data_ptr(), self.scale_v.data_ptr(),
-            self.loss_pc.data_ptr(), self.pc_source.data_ptr() if con else None,
-            self.pc_target.data_ptr() if con else None, self.pc_weight if con else 0.0,
-            self.loss_con.data_ptr() if con else None, self.dec._h if t_mid is not None else None, t_mid,
+            *self._view_poses, self.loss_pc.data_ptr(), *self._constraint_args(),
+            self.dec._h if t_mid is not None else None, t_mid,
             self.tape.data_ptr() if self.fc_in_tail else None, self.arrivals.data_ptr() if self.fc_in_tail else None,
             d, st), "sdfr_loop_tail_fused")
         self._sums_open = False
@@ -873,7 +894,7 @@ class FusedRenderAndCompare:
         records, point constraint, Adam, renormalisation -- and this rank's view poses for the next iteration."""
         from .differentiable_renderer import VIEW_RECORD_FLOATS
         L, d, st = self.L, self.dev.index, self._stream()
-        p, g = self.params.data_ptr(), self.grads.data_ptr()
+        p = self.params.data_ptr()
         t_mid = None
         if self.big_exchange:
             g_sdf = self.plan.g_sdf
@@ -884,14 +905,9 @@ class FusedRenderAndCompare:
             self.check(L.sdfr_decoder_backward_latent_deferred(
                 self.dec._h, self.latent.data_ptr(), self.tape.data_ptr(), g_sdf.data_ptr(), self.ws_dec.data_ptr(),
                 self.ws_dec.numel(), st, ctypes.byref(t_mid)), "sdfr_decoder_backward_latent_deferred")
-        con = self.pc_source is not None
         self.check(L.sdfr_loop_tail_records(
-            p, g, self.m.data_ptr(), self.v.data_ptr(), self.step.data_ptr(), 8 + self.Lz, 1e-3, 1e-2, 1e-3, 1e-2,
-            int(self.shape_opt), self.cam_pos_all.data_ptr(), self.cam_quat_all.data_ptr(), self.V_all,
-            self.view_begin, self.V, self.records.data_ptr(), self.pos_c.data_ptr(), self.quat_c.data_ptr(),
-            self.inv_scale.data_ptr(), self.scale_v.data_ptr(),
-            self.pc_source.data_ptr() if con else None, self.pc_target.data_ptr() if con else None,
-            self.pc_weight if con else 0.0, self.loss_con.data_ptr() if con else None,
+            *self._adam, self.cam_pos_all.data_ptr(), self.cam_quat_all.data_ptr(), self.V_all,
+            self.view_begin, self.V, self.records.data_ptr(), *self._view_poses, *self._constraint_args(),
             self.dec._h if t_mid is not None else None, t_mid, d, st), "sdfr_loop_tail_records")
         if self.track_inliers:
             self.check(L.sdfr_inlier_update_record(
@@ -908,55 +924,36 @@ class FusedRenderAndCompare:
             return rec[:, 16], rec[:, 17]
         return self.loss_depth, self.loss_pc
 
+    def _whole_iteration(self):
+        """head | exchange | tail (the exchange is nothing without a group)"""
+        self._head()
+        self._exchange()
+        self._tail()
+
     def _run_records(self, n_iter, use_graph, history):
         state = (self._state,)
+        record = (lambda it: self._record_history(history)) if history is not None else None
         if self.group is None:
-            return self._run_records_single(n_iter, use_graph, history, state)
+            return self._run_records_single(n_iter, use_graph, state, record)
         if use_graph and self.graph is None:
-            # warm up on a side stream (lazy module loads; every rank takes part in the exchange), restore, capture:
-            # the collective stays outside the graphs -- head | all-reduce | tail+head | all-reduce | ... | tail
-            saved = [t.clone() for t in state]
-            side = torch.cuda.Stream(self.dev)
-            side.wait_stream(torch.cuda.current_stream(self.dev))
-            with torch.cuda.stream(side):
-                self._head()
-                self._exchange()
-                self._tail()
-            torch.cuda.current_stream(self.dev).wait_stream(side)
-            for t, c in zip(state, saved):
-                t.copy_(c)
+            # the warm-up: every rank takes part in the exchange.  The collective stays outside the graphs --
+            # head | all-reduce | tail+head | all-reduce | ... | tail
             # (thread-local capture: the process group's watchdog thread may query events while this thread captures)
-            mode = dict(capture_error_mode="thread_local") if self.group is not None else {}
-            self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph, **mode):
-                self._head()
-            self.graph_tail = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph_tail, **mode):
-                self._tail()
-            self.graph_many = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph_many, **mode):
+            mode = dict(capture_error_mode="thread_local")
+
+            def tail_head():
                 self._tail()
                 self._head()
-            for t, c in zip(state, saved):
-                t.copy_(c)
+
+            self.graph, self.graph_tail, self.graph_many = _graphs.capture(
+                self.dev, (self._head, self._tail, tail_head), self._whole_iteration, state, **mode)
             if self.graph_collective:
-                self._capture_with_collective(mode)
-                for t, c in zip(state, saved):
-                    t.copy_(c)
+                self._capture_with_collective(state, mode)
             self._poses_to_views(self._stream())
             self._keep_graphs()
         if use_graph and self.graph_whole_one is not None:
             # the collective is a node of the graphs: whole iterations replay, nothing is issued in between
-            done = 0
-            if history is None and self.graph_whole is not None:
-                for _ in range(n_iter // self.graph_iterations):
-                    self.graph_whole.replay()
-                done = n_iter - n_iter % self.graph_iterations
-            for _ in range(n_iter - done):
-                self.graph_whole_one.replay()
-                if history is not None:
-                    self._record_history(history)
-            return
+            return _graphs.run(n_iter, self.graph_whole_one, self.graph_whole, self.graph_iterations, None, record)
         fused = use_graph and history is None
         for it in range(n_iter):
             if not use_graph:
@@ -973,30 +970,28 @@ class FusedRenderAndCompare:
             if history is not None:
                 self._record_history(history)
 
-    def _capture_with_collective(self, mode):
+    def _capture_with_collective(self, state, mode):
         """the experiment of ``graph_collective``: head | all-reduce | tail as ONE captured sequence"""
         import torch.distributed as dist
         try:
             if dist.get_backend(self.group) != "nccl":
                 raise RuntimeError(f"backend {dist.get_backend(self.group)!r}: only RCCL's collectives are stream work")
-            one = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(one, **mode):
-                self._head()
-                self._exchange()
-                self._tail()
-            many = None
-            if self.graph_iterations > 1:
-                many = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(many, **mode):
-                    for _ in range(self.graph_iterations):
-                        self._head()
-                        self._exchange()
-                        self._tail()
-            self.graph_whole_one, self.graph_whole = one, many
+            # (no second warm-up: the two-graph form's has just run the same launches)
+            self.graph_whole_one, self.graph_whole = _capture_iterations(self, self._whole_iteration, state,
+                                                                         warmup=lambda: None, **mode)
         except Exception as e:      # capture refused: the two-graph form stays
             torch.cuda.synchronize(self.dev)
-            self.graph_whole_one = self.graph_whole = None
             self.graph_collective_error = f"{type(e).__name__}: {e}"
+
+    def _run_records_single(self, n_iter, use_graph, state, record):
+        """the records form without a process group: no collective, so whole iterations are captured -- one graph per
+        iteration, and one of ``graph_iterations`` iterations, as in the tail form"""
+        if use_graph and self.graph is None:
+            self.graph, self.graph_many = _capture_iterations(self, self._whole_iteration, state)
+            self._poses_to_views(self._stream())
+            self._keep_graphs()
+        one, many = (self.graph, self.graph_many) if use_graph else (None, None)
+        _graphs.run(n_iter, one, many, self.graph_iterations, self._whole_iteration, record)
 
     def _record_history(self, history):
         ld, lp = self.view_losses()
@@ -1006,47 +1001,6 @@ class FusedRenderAndCompare:
                         "position": self.position.clone()[None], "orientation": self.orientation.clone()[None],
                         "scale": self.scale.clone(), "latent": self.latent.clone()[None]})
 
-    def _run_records_single(self, n_iter, use_graph, history, state):
-        """the records form without a process group: no collective, so whole iterations are captured -- one graph per
-        iteration, and one of ``graph_iterations`` iterations, as in the tail form"""
-        if use_graph and self.graph is None:
-            saved = [t.clone() for t in state]
-            side = torch.cuda.Stream(self.dev)
-            side.wait_stream(torch.cuda.current_stream(self.dev))
-            with torch.cuda.stream(side):
-                self._head()
-                self._tail()
-            torch.cuda.current_stream(self.dev).wait_stream(side)
-            for t, c in zip(state, saved):
-                t.copy_(c)
-            self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph):
-                self._head()
-                self._tail()
-            if self.graph_iterations > 1:
-                self.graph_many = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self.graph_many):
-                    for _ in range(self.graph_iterations):
-                        self._head()
-                        self._tail()
-            for t, c in zip(state, saved):
-                t.copy_(c)
-            self._poses_to_views(self._stream())
-            self._keep_graphs()
-        done = 0
-        if use_graph and history is None and self.graph_many is not None:
-            for _ in range(n_iter // self.graph_iterations):
-                self.graph_many.replay()
-            done = n_iter - n_iter % self.graph_iterations
-        for _ in range(n_iter - done):
-            if use_graph:
-                self.graph.replay()
-            else:
-                self._head()
-                self._tail()
-            if history is not None:
-                self._record_history(history)
-
     def _tail_form(self) -> bool:
         return (self.merge_tail and self.fuse_depth_loss and self.defer_pose and self.max_pts > 0
                 and 8 + self.Lz <= 256)
@@ -1054,9 +1008,13 @@ class FusedRenderAndCompare:
     def _poses_to_views(self, st):
         p = self.params.data_ptr()
         self.check(self.L.sdfr_pose_to_views(p, p + 12, p + 28, self.cam_pos.data_ptr(), self.cam_quat.data_ptr(),
-                                             self.V, self.pos_c.data_ptr(), self.quat_c.data_ptr(),
-                                             self.inv_scale.data_ptr(), self.scale_v.data_ptr(), self.dev.index, st),
-                   "sdfr_pose_to_views")
+                                             self.V, *self._view_poses, self.dev.index, st), "sdfr_pose_to_views")
+
+    def _constraint_args(self):
+        """the point constraint as the tail launches take it: source, target, weight, where its loss value goes"""
+        if self.pc_source is None:
+            return None, None, 0.0, None
+        return self.pc_source.data_ptr(), self.pc_target.data_ptr(), self.pc_weight, self.loss_con.data_ptr()
 
     def _inliers(self, L, p, d, st):
         if self.track_inliers:
@@ -1095,46 +1053,21 @@ class FusedRenderAndCompare:
         if self._tail_form():
             self._prime()   # every later iteration gets its view poses from the tail before it
         if use_graph and self.graph is None:
-            # warm up on a side stream (lazy module loads), restore the state, then capture
-            state = (self._state,)
-            saved = [t.clone() for t in state]
-            s = torch.cuda.Stream(self.dev)
-            s.wait_stream(torch.cuda.current_stream(self.dev))
-            with torch.cuda.stream(s):
-                self.iteration()
-            torch.cuda.current_stream(self.dev).wait_stream(s)
-            for t, c in zip(state, saved):
-                t.copy_(c)
-            self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph):
-                self.iteration()
-            if self.graph_iterations > 1:
-                self.graph_many = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self.graph_many):
-                    for _ in range(self.graph_iterations):
-                        self.iteration()
-            for t, c in zip(state, saved):
-                t.copy_(c)   # the capture itself does not execute, but keep the state explicit
+            self.graph, self.graph_many = _capture_iterations(self, self.iteration, (self._state,))
             if self._tail_form():
                 self._prime()   # the warm-up's tail left the poses of ITS updated parameters
             self._keep_graphs()
-        done = 0
-        if use_graph and history is None and self.graph_many is not None:
-            for _ in range(n_iter // self.graph_iterations):
-                self.graph_many.replay()
-            done = n_iter - n_iter % self.graph_iterations
-        for _ in range(n_iter - done):
-            if use_graph:
-                self.graph.replay()
-            else:
-                self.iteration()
-            if history is not None:
-                history.append({"loss": (self.cfg["depth_weight"] * self.loss_depth.sum()
-                                         + self.cfg["pc_weight"] * self.loss_pc.sum()
-                                         + self.loss_con.sum()).clone(),
-                                "position": self.position.clone()[None],
-                                "orientation": self.orientation.clone()[None],
-                                "scale": self.scale.clone(), "latent": self.latent.clone()[None]})
+
+        def record(it):
+            history.append({"loss": (self.cfg["depth_weight"] * self.loss_depth.sum()
+                                     + self.cfg["pc_weight"] * self.loss_pc.sum()
+                                     + self.loss_con.sum()).clone(),
+                            "position": self.position.clone()[None],
+                            "orientation": self.orientation.clone()[None],
+                            "scale": self.scale.clone(), "latent": self.latent.clone()[None]})
+
+        one, many = (self.graph, self.graph_many) if use_graph else (None, None)
+        _graphs.run(n_iter, one, many, self.graph_iterations, self.iteration, record if history is not None else None)
         # "best_inlier_ratio": the reference returns the parameter tensors themselves, i.e. the last
         # iterate (_BestEstimate); the snapshot taken at the best ratio is in best_estimate()
         return (self.position.clone()[None], self.orientation.clone()[None], self.scale.clone(),
@@ -1231,6 +1164,8 @@ class MultiObjectRenderAndCompare:
         self.quat_c = torch.empty((B, 4), **f32)
         self.inv_scale = torch.empty((B,), **f32)
         self.scale_v = torch.empty((B,), **f32)
+        self._view_poses = (self.pos_c.data_ptr(), self.quat_c.data_ptr(), self.inv_scale.data_ptr(),
+                            self.scale_v.data_ptr())
         self.loss_pc = torch.zeros((B,), **f32)
         self.sdf_objects = torch.empty((K, 1, R, R, R), **f32)      # what the decoder writes
         self.sdf = self.sdf_objects if V == 1 else torch.empty((B, 1, R, R, R), **f32)     # what the views read
@@ -1289,21 +1224,8 @@ class MultiObjectRenderAndCompare:
                 self.target.copy_(images)
             if V > 1:
                 self.target_last.copy_(self.target.view(K, V, H, W)[:, V - 1])
-            if camera_positions is None:
-                self.cam_pos.zero_()
-            else:
-                self.cam_pos.copy_(camera_positions.reshape(V, 3))
-            if camera_orientations is None:
-                self.cam_quat.zero_()
-                self.cam_quat[:, 3] = 1.0
-            else:
-                self.cam_quat.copy_(camera_orientations.reshape(V, 4))
-            fx, fy, cx0, cy0, _ = self.cam.get_pinhole_camera_parameters(0.0)
-            self.check(self.L.sdfr_depth_to_points_resident(
-                self.target.data_ptr(), B, self.W, self.H, _lib.ABI["SDFR_POINT_ORDER_TILED"], 1.0 / fx,
-                1.0 / fy, cx0, cy0, self.counts.data_ptr(), self.offsets.data_ptr(), self.ws_points.data_ptr(),
-                self.ws_points.numel(), self.points.data_ptr(), self.dev.index, self._stream()),
-                "sdfr_depth_to_points_resident")
+            _copy_cameras(self.cam_pos, self.cam_quat, camera_positions, camera_orientations)
+            _target_to_points(self, B)
         self.bound = True
         return self
 
@@ -1321,8 +1243,7 @@ class MultiObjectRenderAndCompare:
         NEXT iteration's"""
         self.check(self.L.sdfr_pose_to_views_objects(
             self.params.data_ptr(), self.n, self.K, self.cam_pos.data_ptr(), self.cam_quat.data_ptr(), self.V,
-            self.pos_c.data_ptr(), self.quat_c.data_ptr(), self.inv_scale.data_ptr(), self.scale_v.data_ptr(),
-            self.z.data_ptr(), self.dev.index, st), "sdfr_pose_to_views_objects")
+            *self._view_poses, self.z.data_ptr(), self.dev.index, st), "sdfr_pose_to_views_objects")
 
     def iteration(self):
         L, d, st = self.L, self.dev.index, self._stream()
@@ -1346,10 +1267,9 @@ class MultiObjectRenderAndCompare:
                 self.ws_dec.numel(), st, ctypes.byref(t_mid)), "sdfr_decoder_backward_latent_deferred_batch")
         self.check(L.sdfr_loop_tail_objects(
             self.params.data_ptr(), self.grads.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.step.data_ptr(),
-            self.n, self.K, 1e-3, 1e-2, 1e-3, 1e-2, int(self.shape_opt), self.cam_pos.data_ptr(), self.cam_quat.data_ptr(),
+            self.n, self.K, *_ADAM_RATES, int(self.shape_opt), self.cam_pos.data_ptr(), self.cam_quat.data_ptr(),
             self.V, self.plan.workspace.data_ptr(), self.plan.partials_offset, self.W, self.H, self.ws_pc.data_ptr(),
-            self.offsets.data_ptr(), self.max_pts, self.pos_c.data_ptr(), self.quat_c.data_ptr(),
-            self.inv_scale.data_ptr(), self.scale_v.data_ptr(), self.loss_pc.data_ptr(),
+            self.offsets.data_ptr(), self.max_pts, *self._view_poses, self.loss_pc.data_ptr(),
             self.dec._h if self.shape_opt else None, t_mid if self.shape_opt else None, self.z.data_ptr(), d, st),
             "sdfr_loop_tail_objects")
         if self.track_inliers:
@@ -1395,40 +1315,19 @@ class MultiObjectRenderAndCompare:
             self._decode(st, False)
         n_iter = self.cfg["max_iterations"]
         if use_graph and self.graph is None:
-            saved = [t.clone() for t in state]
-            side = torch.cuda.Stream(self.dev)
-            side.wait_stream(torch.cuda.current_stream(self.dev))
-            with torch.cuda.stream(side):
-                self.iteration()
-            torch.cuda.current_stream(self.dev).wait_stream(side)
-            self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph):
-                self.iteration()
-            if self.graph_iterations > 1:
-                self.graph_many = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self.graph_many):
-                    for _ in range(self.graph_iterations):
-                        self.iteration()
-            for t, c in zip(state, saved):
-                t.copy_(c)
+            self.graph, self.graph_many = _capture_iterations(self, self.iteration, state)
             self._poses_to_views(self._stream())     # (the warm-up's tail left the poses of ITS updated parameters)
-        done = 0
-        if use_graph and history is None and self.graph_many is not None:
-            for _ in range(n_iter // self.graph_iterations):
-                self.graph_many.replay()
-            done = n_iter - n_iter % self.graph_iterations
-        for it in range(done, n_iter):
-            if use_graph:
-                self.graph.replay()
-            else:
-                self.iteration()
-            if history is not None:
-                ld, lp = self.view_losses()
-                entry = {"loss_depth": ld.clone(), "loss_pc": lp.clone(), "params": self.params.clone()}
-                if self.track_inliers:
-                    entry["depth"] = self.last_view_depth().clone()
-                    entry["inlier_ratio"] = self.inlier_history[:, it].clone()
-                history.append(entry)
+
+        def record(it):
+            ld, lp = self.view_losses()
+            entry = {"loss_depth": ld.clone(), "loss_pc": lp.clone(), "params": self.params.clone()}
+            if self.track_inliers:
+                entry["depth"] = self.last_view_depth().clone()
+                entry["inlier_ratio"] = self.inlier_history[:, it].clone()
+            history.append(entry)
+
+        one, many = (self.graph, self.graph_many) if use_graph else (None, None)
+        _graphs.run(n_iter, one, many, self.graph_iterations, self.iteration, record if history is not None else None)
         p = self.params
         return p[:, 0:3].clone(), p[:, 3:7].clone(), p[:, 7].clone(), p[:, 8:].clone()
 

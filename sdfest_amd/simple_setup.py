@@ -29,6 +29,7 @@ from typing import Dict, List, Mapping, Optional, Tuple
 import torch
 
 from . import _lib
+from ._graphs import BoundedCache
 from .differentiable_renderer import Camera, parse_sdf_grad_mode, render_depth_gpu
 from .mesh import Mesh, extract_mesh
 from .init_network import NoDepthError, ResidentInit, SDFPoseNet, adjust_categorical_posterior, nn_init
@@ -103,13 +104,16 @@ class SDFPipeline:
             sdf, pos, quat, i_s, None, None, None, config["threshold"], self.cam, self.sdf_grad_mode)
         self.config = config
         self.log_data = []
-        self._loops = {}     # (views, shape_optimization) -> the captured loop, re-bound per call
+        limit = self.MAX_CACHED_LOOPS
+        self._loops = BoundedCache(limit)     # (views, shape_optimization) -> the captured loop, re-bound per call
         # resident_init: the initialisation network as a captured launch sequence with nothing read back
         # (init_network.ResidentInit) where its architecture allows; False: the host-driven nn_init (two host reads)
         self._resident_wanted = bool(resident_init)
-        self._residents = {}
-        self._multi_loops, self._resident_objects = {}, {}     # estimate_objects: per (K, shape_optimization, V, tracking) / per (K, V)
-        self._resident_hypotheses, self._last_hypotheses = {}, None     # estimate_hypotheses: per N / the last call's record
+        self._residents = BoundedCache(limit)
+        # estimate_objects: per (K, shape_optimization, V, tracking) / per (K, V)
+        self._multi_loops, self._resident_objects = BoundedCache(limit), BoundedCache(limit)
+        # estimate_hypotheses: per N / the last call's record
+        self._resident_hypotheses, self._last_hypotheses = BoundedCache(limit), None
         self._ignored_warned = False
 
     def _parse_config(self, config: Dict) -> None:
@@ -148,14 +152,15 @@ class SDFPipeline:
         """the captured form of ``_nn_init`` for `views` images, or None where only the host-driven form applies"""
         if not self._resident_wanted or self._nn_init_override is not None or not isinstance(self.init_network, SDFPoseNet):
             return None
-        if views not in self._residents:
-            self._bounded(self._residents, self.MAX_CACHED_LOOPS)
-            try:
-                self._residents[views] = ResidentInit(self.init_network, self.cam, views, self.config,
-                                                      normalize_pose=bool(self.init_config.get("normalize_pose", False)))
-            except NotImplementedError:
-                self._residents[views] = None
-        return self._residents[views]
+        return self._residents.get_or_build(views, lambda: self._new_resident(views, self.config))
+
+    def _new_resident(self, views: int, config: Dict, **kwargs):
+        """a ``ResidentInit`` of this pipeline's network, or None where its architecture only allows the host-driven form"""
+        try:
+            return ResidentInit(self.init_network, self.cam, views, config,
+                                normalize_pose=bool(self.init_config.get("normalize_pose", False)), **kwargs)
+        except NotImplementedError:
+            return None
 
     def generate_depth(self, position, orientation, scale, latent) -> torch.Tensor:
         """simple_setup.py:609-619"""
@@ -192,25 +197,15 @@ class SDFPipeline:
             m.update_scale(float(s), rel_scale=True)
         return meshes
 
-    MAX_CACHED_LOOPS = 4     # per kind: a loop holds its point clouds at capacity (3.7 MB per 640x480 view) and its graphs
-
-    @staticmethod
-    def _bounded(cache: dict, limit: int) -> None:
-        """drop the least recently built entry before a new one goes in (a caller whose number of views or objects
-        varies from call to call re-builds instead of collecting buffers without bound)"""
-        while len(cache) >= limit:
-            cache.pop(next(iter(cache)))
+    # per kind (a caller whose number of views or objects varies from call to call re-builds instead of collecting
+    # buffers without bound): a loop holds its point clouds at capacity (3.7 MB per 640x480 view) and its graphs
+    MAX_CACHED_LOOPS = 4
 
     def _loop(self, views: int, shape_optimization: bool) -> FusedRenderAndCompare:
         key = (int(views), bool(shape_optimization))
-        loop = self._loops.get(key)
-        if loop is None:
-            self._bounded(self._loops, self.MAX_CACHED_LOOPS)
-            loop = FusedRenderAndCompare(self.vae, self.cam, self.config, views=views,
-                                         shape_optimization=shape_optimization, device=self._dev,
-                                         sdf_grad_mode=self.sdf_grad_mode)
-            self._loops[key] = loop
-        return loop
+        return self._loops.get_or_build(key, lambda: FusedRenderAndCompare(
+            self.vae, self.cam, self.config, views=views, shape_optimization=shape_optimization, device=self._dev,
+            sdf_grad_mode=self.sdf_grad_mode))
 
     def __call__(self, depth_images: torch.Tensor, masks: torch.Tensor, color_images: torch.Tensor,
                  visualize: bool = False, camera_positions: Optional[torch.Tensor] = None,
@@ -343,13 +338,9 @@ class SDFPipeline:
         """the K-row loop of ``estimate_objects`` and ``estimate_frames``, built on first use and kept"""
         track = self.result_selection_strategy == "best_inlier_ratio"
         key = (K, bool(shape_optimization), V, track)
-        loop = self._multi_loops.get(key)
-        if loop is None:
-            self._bounded(self._multi_loops, self.MAX_CACHED_LOOPS)
-            loop = self._multi_loops[key] = MultiObjectRenderAndCompare(
-                self.vae, self.cam, self.config, K, shape_optimization=shape_optimization, device=self._dev,
-                sdf_grad_mode=self.sdf_grad_mode, views=V, track_inliers=track)
-        return loop
+        return self._multi_loops.get_or_build(key, lambda: MultiObjectRenderAndCompare(
+            self.vae, self.cam, self.config, K, shape_optimization=shape_optimization, device=self._dev,
+            sdf_grad_mode=self.sdf_grad_mode, views=V, track_inliers=track))
 
     def _run_objects(self, loop: MultiObjectRenderAndCompare, prior_orientation_distribution,
                      training_orientation_distribution) -> tuple:
@@ -359,15 +350,8 @@ class SDFPipeline:
         resident = None
         if self._resident_wanted and self._nn_init_override is None and isinstance(self.init_network, SDFPoseNet):
             # (per (K, V): its captured sequence holds the addresses of K images V images apart)
-            if (K, V) not in self._resident_objects:
-                self._bounded(self._resident_objects, self.MAX_CACHED_LOOPS)
-                try:
-                    self._resident_objects[K, V] = ResidentInit(
-                        self.init_network, self.cam, K, dict(self.config, init_view="first"),
-                        normalize_pose=bool(self.init_config.get("normalize_pose", False)), objects=True)
-                except NotImplementedError:
-                    self._resident_objects[K, V] = None
-            resident = self._resident_objects[K, V]
+            resident = self._resident_objects.get_or_build((K, V), lambda: self._new_resident(
+                K, dict(self.config, init_view="first"), objects=True))
         if resident is not None:
             latent, position, scale, orientation = resident(first, loop.cam_pos, loop.cam_quat,
                                                             prior_orientation_distribution,
@@ -438,15 +422,17 @@ class SDFPipeline:
         # (the inlier bookkeeping always runs: it is the score; "hypotheses" keeps these loops apart from
         # estimate_objects' loops of the same K)
         key = ("hypotheses", N, bool(shape_optimization), V)
-        loop = self._multi_loops.get(key)
-        if loop is None:
-            self._bounded(self._multi_loops, self.MAX_CACHED_LOOPS)
-            loop = self._multi_loops[key] = MultiObjectRenderAndCompare(
+
+        def build():
+            loop = MultiObjectRenderAndCompare(
                 self.vae, self.cam, self.config, N, shape_optimization=shape_optimization, device=self._dev,
                 sdf_grad_mode=self.sdf_grad_mode, views=V, track_inliers=True)
             f32 = dict(dtype=torch.float32, device=self._dev)
             loop.selection = dict(row=torch.zeros(loop.n, **f32), index=torch.zeros(1, dtype=torch.int32, device=self._dev),
                                   score=torch.zeros(1, **f32), initial=torch.zeros((N, loop.n), **f32))
+            return loop
+
+        loop = self._multi_loops.get_or_build(key, build)
         H, W = loop.H, loop.W
         with torch.no_grad():
             # (frames + masks: every row gets its own masked copy, the caller's depth is only read)
@@ -535,12 +521,9 @@ class SDFPipeline:
             raise ValueError("orientation hypotheses with several views start from the first view (init_view: first), "
                              f"not init_view: {self.config.get('init_view')}")
         loop = self._hypothesis_loop(depth_images, masks, N, camera_positions, camera_orientations, shape_optimization)
-        if N not in self._resident_hypotheses:
-            self._bounded(self._resident_hypotheses, self.MAX_CACHED_LOOPS)
-            self._resident_hypotheses[N] = ResidentInit(
-                self.init_network, self.cam, 1, dict(self.config, init_view="first"),
-                normalize_pose=bool(self.init_config.get("normalize_pose", False)), hypotheses=N)
-        resident = self._resident_hypotheses[N]
+        resident = self._resident_hypotheses.get_or_build(N, lambda: ResidentInit(
+            self.init_network, self.cam, 1, dict(self.config, init_view="first"),
+            normalize_pose=bool(self.init_config.get("normalize_pose", False)), hypotheses=N))
         with torch.no_grad():
             prior = prior_orientation_distribution
             if prior is not None:
