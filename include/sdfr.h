@@ -42,7 +42,7 @@
  * code (the Python modules under sdfest_amd/), follow its needs from round to round (arguments were added in every round so far), and are
  * exported only because that host code is Python over ctypes; bind to them at your own risk, pinned to one SDFR_VERSION.
  *
- * CONTENTS -- nine groups; a binding from another language needs group 1 only
+ * CONTENTS -- the groups; a binding from another language needs group 1 only
  *   1. CORE: the reference boundary (what sdf_renderer_cpp, losses.pc_loss and SDFDecoder.forward are replaced by)
  *        sdfr_version, sdfr_last_error
  *        sdfr_render_forward[_workspace_bytes], sdfr_render_backward[_workspace_bytes]
@@ -89,6 +89,8 @@
  *        sdfr_visible_mask
  *  14. [unstable] POSE INFORMATION: the Gauss-Newton normal matrix of the depth residual (SDFPipeline.pose_uncertainty)
  *        sdfr_render_information[_workspace_bytes]
+ *  15. [unstable] BOXES: the oriented box of an estimate without its mesh, and the exact 3D IoU of oriented boxes
+ *        sdfr_sdf_bounds, sdfr_box_iou
  * (Within the file the groups follow the order in which the reference's code runs; every declaration carries the
  * reference file:line it replaces.)
  */
@@ -1447,6 +1449,52 @@ SDFR_API int sdfr_render_information(const float* depth, const float* target, co
                                      const float* inv_scale, int B, int W, int H, float cx, float cy, float fx,
                                      float fy, float inlier_threshold, double* gram, void* workspace,
                                      size_t workspace_bytes, int device, void* stream);
+
+/* ==== 15. BOXES =============================================================================== */
+/* ---- the bounds of a grid's iso-surface: what amin / amax of sdfr_mesh_emit's vertices give, without counting,
+ * scanning or emitting a mesh.  Grids, `complete`, `level`, the inside rule (v < level), the axis order and the vertex
+ * position are group 5's; per grid
+ *   bounds  [N][6] float, overwritten: lo x, y, z, hi x, y, z = per axis the minimum and maximum, over ALL crossed edges
+ *           of the (padded) volume, of the vertex sdfr_mesh_emit places on that edge -- the same bits (one statement of
+ *           the arithmetic, csrc/mesh_grid.hpp); lo = +inf, hi = -inf for a grid without a crossed edge
+ *   crossed [N] int32, overwritten: the number of crossed edges (the V of sdfr_mesh_count's totals)
+ * Minima, maxima (atomics on an order-preserving integer image of the float) and an integer count: the same bits on
+ * every call, and for a grid alone or among N.  The outputs may hold anything on entry.  Three launches on the caller's
+ * stream, no workspace, no allocation, no host synchronisation: the call can be captured into a graph.
+ * 2 <= R <= 256, 0 <= N <= 65535 (N = 0 does nothing), level finite, all pointers 4-byte aligned; every argument error is
+ * SDFR_E_INVALID with a message, before anything touches the GPU.  Only finite grids are specified. */
+SDFR_API int sdfr_sdf_bounds(const float* sdf, int N, int R, int complete, float level,
+                             float* bounds /* [N][6]: lo xyz then hi xyz */, int* crossed /* [N] */,
+                             int device, void* stream);
+
+/* ---- the 3D IoU of oriented boxes (the reference leaves it a TODO: estimation/metrics.py:66-70), in fp64.
+ * A box is 10 doubles: centre (3), quaternion x, y, z, w (4; normalised inside), full side lengths (3); it is the set
+ * c + R(q) x, |x_i| <= e_i / 2.
+ *   boxes_a [N][10], boxes_b [M][10]
+ *   mode    SDFR_BOX_IOU_MATRIX: iou [N][M], every a against every b;  SDFR_BOX_IOU_PAIRED: N == M, iou [N]
+ *   iou     V / (V_a + V_b - V), V = the volume of the intersection; intersection (nullable, same shape): V
+ *   symmetry_axis 0 | 1 | 2 with symmetry_steps = S >= 1 (<= 65536): box b is also turned about ITS OWN axis by
+ *           2 pi s / S, s = 0 .. S - 1, and the largest V (hence the largest IoU) is returned -- a category whose turn
+ *           about that axis cannot be observed (correct_thresh's rotational_symmetry_axis); -1: one evaluation
+ *           (symmetry_steps is not read); S = 1 gives the bits of -1
+ * V is the sum over the 12 face planes of (plane distance x area of the clipped rectangle) / 3, with L = |e_a| + |e_b| +
+ * |c_b - c_a|: a signed distance of at most 1e-12 L counts as zero, so coplanar faces -- fp32-rounded multiples of 90
+ * degrees included -- are counted once; boxes whose bounding spheres are apart give exactly 0; 0 <= V <= min(V_a, V_b).
+ * Accuracy: within 1e-12 L^3 of the exact volume for boxes in general position, for coplanar faces and for parallel
+ * ones (identical boxes give 1, boxes that only touch 0, to that bound).  NOT for two faces that cross at an angle d
+ * below about 1e-5 rad without being coplanar to 1e-12 L: each is cut by the other's plane, the cut line is placed by
+ * the rounding of distances of about 1e-17 L / d, and the two cuts need not agree -- measured 1e-9 of the volume at d =
+ * 1e-7, 1e-7 at d = 1e-8, more as d falls towards 1e-12 L / side.
+ * A box with a non-finite entry, a non-positive side length or a quaternion whose squared norm is 0 or not finite gives
+ * NaN in every entry it takes part in.  An entry depends on its own two boxes alone: MATRIX [i][j] is bitwise the
+ * PAIRED result of (a_i, b_j), in any batch.  N = 0 or M = 0 does nothing.  One launch on the caller's stream, no
+ * workspace, no allocation, no host synchronisation.  All pointers 8-byte aligned; every argument error is
+ * SDFR_E_INVALID with a message, before anything touches the GPU. */
+#define SDFR_BOX_IOU_MATRIX 0   /* iou [N][M] */
+#define SDFR_BOX_IOU_PAIRED 1   /* N == M, iou [N] */
+SDFR_API int sdfr_box_iou(const double* boxes_a, int N, const double* boxes_b, int M, int mode,
+                          int symmetry_axis, int symmetry_steps,
+                          double* iou, double* intersection /* nullable */, int device, void* stream);
 
 #ifdef __cplusplus
 }

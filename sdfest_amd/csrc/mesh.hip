@@ -22,6 +22,7 @@
 #include <hip/hip_runtime.h>
 
 #include "common.hpp"
+#include "mesh_grid.hpp"
 #include "mesh_tables.hpp"
 
 namespace sdfr {
@@ -61,32 +62,6 @@ __constant__ signed char c_tri_table[256 * 16] = {SDFR_X64(0), SDFR_X64(64), SDF
 #undef SDFR_X4
 #undef SDFR_X16
 #undef SDFR_X64
-
-struct MeshGrid {
-  const float* sdf;   // grid n's volume: sdf + n R^3
-  int R, M, pad;      // pad = 1: the complete mesh's virtual border (M = R + 2)
-  float level;
-};
-
-// value at padded coordinates (i, j, k) of grid `g`; 1.0 on the virtual border
-__device__ __forceinline__ float mesh_at(const float* __restrict__ g, const MeshGrid& p, int i, int j, int k) {
-  if (p.pad) {
-    i -= 1, j -= 1, k -= 1;
-    if ((unsigned)i >= (unsigned)p.R || (unsigned)j >= (unsigned)p.R || (unsigned)k >= (unsigned)p.R) return 1.0f;
-  }
-  return g[((size_t)i * p.R + j) * p.R + k];
-}
-
-// the crossed owned edges of point (i, j, k): bit a = edge along axis a
-__device__ __forceinline__ unsigned mesh_owned_edges(const float* __restrict__ g, const MeshGrid& p, int i, int j,
-                                                     int k, float v0) {
-  const bool in0 = v0 < p.level;
-  unsigned m = 0;
-  if (i + 1 < p.M && (mesh_at(g, p, i + 1, j, k) < p.level) != in0) m |= 1u;
-  if (j + 1 < p.M && (mesh_at(g, p, i, j + 1, k) < p.level) != in0) m |= 2u;
-  if (k + 1 < p.M && (mesh_at(g, p, i, j, k + 1) < p.level) != in0) m |= 4u;
-  return m;
-}
 
 // the case index of the cell with minimum corner (i, j, k) (all < M - 1)
 __device__ __forceinline__ unsigned mesh_cell_case(const float* __restrict__ g, const MeshGrid& p, int i, int j,
@@ -262,16 +237,12 @@ __global__ void __launch_bounds__(kMeshThreads) mesh_vertices_kernel(MeshGrid p,
     if (!(m & (1u << a))) continue;
     const int di = a == 0, dj = a == 1, dk = a == 2;
     const float v1 = mesh_at(g, p, i + di, j + dj, k + dk);
-    const float t = (p.level - v0) / (v1 - v0);
-    // (idx - (M - 1) / 2) is exact; t is added once, then scaled once
-    float x = (float)i - h, y = (float)j - h, z = (float)k - h;
-    if (a == 0) x += t;
-    if (a == 1) y += t;
-    if (a == 2) z += t;
+    const float t = mesh_edge_t(v0, v1, p.level);
+    const V3 pos = mesh_edge_vertex(i, j, k, a, t, s, h);
     float* vo = vertices + 3 * row;
-    vo[0] = x * s;
-    vo[1] = y * s;
-    vo[2] = z * s;
+    vo[0] = pos.x;
+    vo[1] = pos.y;
+    vo[2] = pos.z;
     if (normals) {
       const V3 gb = mesh_gradient(g, p, i + di, j + dj, k + dk);
       const V3 gn = ga + t * (gb - ga);
@@ -328,7 +299,6 @@ inline int mesh_check(const char* fn, int N, int R, int complete) {
   return 0;
 }
 
-inline int mesh_side(int R, int complete) { return complete ? R + 2 : R; }
 inline int mesh_blocks(int M) { return (int)(((long long)M * M * M + kMeshThreads - 1) / kMeshThreads); }
 inline size_t mesh_partials_bytes(int N, int M) { return (size_t)N * mesh_blocks(M) * sizeof(int4); }
 
@@ -385,9 +355,7 @@ extern "C" int sdfr_mesh_emit(const float* sdf, int N, int R, int complete, floa
   const MeshGrid p{sdf, R, M, complete, level};
   const int4* partials = (const int4*)workspace;
   unsigned* vbase = (unsigned*)((char*)workspace + mesh_partials_bytes(N, M));
-  // index units -> the reference's frame: idx s - s (M - 1) / 2, s = 2 / (R - 1) (simple_setup.py:647-658)
-  const float s = 2.0f / (float)(R - 1);
-  const float h = (float)(M - 1) * 0.5f;
+  const float s = mesh_vertex_scale(R), h = mesh_vertex_half(M);
   hipLaunchKernelGGL(mesh_vertices_kernel, dim3(nblk, N), dim3(kMeshThreads), 0, (hipStream_t)stream, p, partials,
                      nblk, totals, vbase, s, h, vertices, normals);
   hipLaunchKernelGGL(mesh_faces_kernel, dim3(nblk, N), dim3(kMeshThreads), 0, (hipStream_t)stream, p, partials, nblk,

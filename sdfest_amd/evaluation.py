@@ -17,7 +17,7 @@ import torch
 from .generated_views import sample_uniform_quaternions
 from .mesh import Mesh, extract_mesh, render_mesh_depth, sample_points
 from .init_network import NoDepthError
-from .metrics import _Quat, correct_thresh, evaluate_metrics
+from .metrics import _Quat, correct_thresh, evaluate_metrics, iou_3d
 from .pipeline import quaternion_apply, quaternion_invert, quaternion_multiply
 from .pointset_utils import change_orientation_camera_convention, change_position_camera_convention
 from .sdf_utils import mesh_to_sdf, normalized_mesh
@@ -227,7 +227,7 @@ def _annotated_groups(dataset, indices: List[int], pipelines, frames_per_call: i
 def evaluate_annotated(pipelines, dataset, samples: int, seed: int, metrics_config: Optional[dict] = None,
                        pose_thresholds: Optional[dict] = None, symmetry_axes: Optional[dict] = None,
                        frames_per_call: int = 1, shape_optimization: bool = True,
-                       indices: Optional[List[int]] = None) -> dict:
+                       indices: Optional[List[int]] = None, iou_thresholds: Optional[dict] = None) -> dict:
     """The evaluation over annotated real frames: every sample of `dataset` (``AnnotatedRedwoodDataset``, or anything
     with its sample dictionary, ``load_mesh`` and ``_config``) -> the pipeline on a clone of its depth under its mask
     -> ``pipeline.generate_mesh(latent, scale, True)`` posed with the estimate, and ``dataset.load_mesh(obj_path)``
@@ -242,7 +242,13 @@ def evaluate_annotated(pipelines, dataset, samples: int, seed: int, metrics_conf
     symmetry_axes: {category_str: 0 | 1 | 2}, the ``rotational_symmetry_axis`` of such a category's rotation error and
     flags.  frames_per_call = K: runs of up to K consecutive samples of one category go through ``estimate_frames``
     together (a run in which a frame has no depth is done again frame by frame).  indices: these samples, in this
-    order (default: all).
+    order (default: all).  iou_thresholds: {name: IoU}, e.g. {"iou25": 0.25, "iou50": 0.5} -- every sample also gets
+    "iou_3d", the 3D IoU (``metrics.iou_3d``; the category's symmetry axis applies) of the annotated box (the frame's
+    "extents", or ``dataset.annotation(i)["extents"]``, at the ground-truth pose) and the estimate's
+    (``out_mesh.oriented_box`` of the mesh generated anyway, at the estimate's pose in the precision the pipeline returned
+    it), one "correct" flag per entry (IoU >= the threshold), "stats" the IoU's and the top-level "correct" the flags'
+    shares;
+    None (default): none of these, the result is what it was without the argument.
 
     Returns {"samples": [{"index", "category_str", "metrics": {name: float}, "position_error", "rotation_error",
     "correct": {name: 0 | 1}}], "stats": {category_str and "all": ``metric_stats`` of the metrics and the two errors},
@@ -285,22 +291,23 @@ def evaluate_annotated(pipelines, dataset, samples: int, seed: int, metrics_conf
                     skipped.append({"index": i, "category_str": category, "reason": "no valid depth under the mask"})
                     continue
             entries[i] = _annotated_entry(pipeline, dataset, i, frame, estimate, convention, samples, seed,
-                                          metrics_config, pose_thresholds, symmetry_axes.get(category))
+                                          metrics_config, pose_thresholds, symmetry_axes.get(category), iou_thresholds)
     done = [entries[i] for i in indices if i in entries]
-    rows = lambda es: [dict(e["metrics"], position_error=e["position_error"], rotation_error=e["rotation_error"])
-                       for e in es]
+    rows = lambda es: [dict(e["metrics"], position_error=e["position_error"], rotation_error=e["rotation_error"],
+                            **({"iou_3d": e["iou_3d"]} if iou_thresholds is not None else {})) for e in es]
     stats = {c: metric_stats(rows([e for e in done if e["category_str"] == c]))
              for c in dict.fromkeys(e["category_str"] for e in done)}
     stats["all"] = metric_stats(rows(done))
     correct = {name: (sum(e["correct"][name] for e in done) / len(done) if done else float("nan"))
-               for name in pose_thresholds}
+               for name in list(pose_thresholds) + list(iou_thresholds or {})}
     order = {i: n for n, i in enumerate(indices)}
     return {"samples": done, "stats": stats, "correct": correct,
             "skipped": sorted(skipped, key=lambda s: order[s["index"]])}
 
 
 def _annotated_entry(pipeline, dataset, index: int, frame: dict, estimate: tuple, convention: str, samples: int,
-                     seed: int, metrics_config: dict, pose_thresholds: dict, symmetry_axis: Optional[int]) -> dict:
+                     seed: int, metrics_config: dict, pose_thresholds: dict, symmetry_axis: Optional[int],
+                     iou_thresholds: Optional[dict] = None) -> dict:
     position, orientation, scale, latent = estimate
     out_mesh = pipeline.generate_mesh(latent, scale, True)
     if out_mesh is None:
@@ -321,5 +328,15 @@ def _annotated_entry(pipeline, dataset, index: int, frame: dict, estimate: tuple
                                         position_threshold=metres, degree_threshold=degrees,
                                         rotational_symmetry_axis=symmetry_axis))
                for name, (degrees, metres) in pose_thresholds.items()}
-    return {"index": index, "category_str": frame["category_str"], "metrics": metrics,
-            "position_error": position_error, "rotation_error": rotation_error, "correct": correct}
+    entry = {"index": index, "category_str": frame["category_str"], "metrics": metrics,
+             "position_error": position_error, "rotation_error": rotation_error, "correct": correct}
+    if iou_thresholds is not None:
+        # (the estimate's pose as the pipeline returned it: the mesh's own pose attributes are float32)
+        center, box_orientation, extents = out_mesh.oriented_box(position[0], orientation[0])
+        # (the annotation's side lengths: a sample of AnnotatedRedwoodDataset carries its "scale" only)
+        gt_extents = frame["extents"] if "extents" in frame else dataset.annotation(index)["extents"]
+        entry["iou_3d"] = iou_3d(gt_position, gt_orientation, gt_extents, center, box_orientation, extents,
+                                 rotational_symmetry_axis=symmetry_axis)
+        for name, threshold in iou_thresholds.items():
+            correct[name] = int(entry["iou_3d"] >= threshold)
+    return entry

@@ -6,7 +6,7 @@ does with ``rel_scale=True``: an unscaled mesh in the SDF's normalised frame plu
 is classic table marching cubes with a face-consistent case table, not skimage's Lewiner variant: the vertices lie on
 the same crossed grid edges, the triangles between them may differ in ambiguous cells.
 """
-from typing import List, Optional, Union
+from typing import List, Optional, Tuple, Union
 
 import numpy as np
 import torch
@@ -79,6 +79,27 @@ class Mesh:
         v = self.scaled_vertices()
         q = self.orientation.to(v).reshape(1, 4).expand(v.shape[0], 4)
         return quaternion_apply(q, v) + self.position.to(v).reshape(1, 3)
+
+    def bounding_box(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(lo (3,), hi (3,)): the axis-aligned bounds of the scaled vertices, in the mesh's own frame (before its
+        pose).  ``ValueError`` for a mesh without vertices.  Plain torch: works on CPU tensors."""
+        if self.vertices.shape[0] == 0:
+            raise ValueError("an empty mesh has no bounding box")
+        v = self.scaled_vertices()
+        return v.amin(0), v.amax(0)
+
+    def oriented_box(self, position=None, orientation=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """(center (3,), orientation (4,), extents (3,)) as float64 tensors: ``bounding_box`` with the pose applied -- the
+        box ``position + R(orientation) x``, x in [lo, hi], as ``boxes.box_iou`` takes it.  The pose is the mesh's own
+        (float32) or the given `position` (3,) / `orientation` (4,), which keep their precision: the algebra runs in
+        float64, so a float64 pose gives the box of exactly that pose.  The centre is turned by the NORMALISED quaternion,
+        as ``box_iou`` normalises the one it is given."""
+        lo, hi = self.bounding_box()
+        lo, hi = lo.double(), hi.double()
+        pose = lambda given, own: (own if given is None else torch.as_tensor(given)).detach().to(lo.device, torch.float64)
+        p, q = pose(position, self.position).reshape(3), pose(orientation, self.orientation).reshape(4)
+        center = p + quaternion_apply((q / q.norm()).reshape(1, 4), ((lo + hi) / 2).reshape(1, 3))[0]
+        return center, q, hi - lo
 
     def numpy(self, transformed: bool = False):
         """(vertices (V,3) float32 -- scaled, and posed if `transformed` --, faces (F,3) int32, normals or None)"""

@@ -20,7 +20,7 @@ import torch
 from . import _lib
 
 __all__ = ["mean_accuracy", "mean_completeness", "symmetric_chamfer", "accuracy_thresh", "completeness_thresh",
-           "reconstruction_fscore", "extent", "correct_thresh", "reconstruction_metrics", "evaluate_metrics", "nearest_neighbors"]
+           "reconstruction_fscore", "extent", "correct_thresh", "iou_3d", "reconstruction_metrics", "evaluate_metrics", "nearest_neighbors"]
 
 _MAX_T = _lib.ABI["SDFR_NN_MAX_THRESHOLDS"]
 _STATS = _lib.ABI["SDFR_NN_STATS"]   # sum, max, count, NaN count, _MAX_T counts, _MAX_T normalised counts
@@ -272,6 +272,20 @@ def _rotation(r):
     return _Quat(r)
 
 
+def iou_3d(position_gt, orientation_gt, extent_gt, position_prediction, orientation_prediction, extent_prediction,
+           rotational_symmetry_axis: Optional[int] = None, symmetry_steps: int = 20) -> float:
+    """The 3D IoU of the ground-truth and the predicted oriented bounding box (``boxes.box_iou`` for one pair, exact
+    in float64 on the GPU): positions (3,), extents (3,) full side lengths, orientations as in ``correct_thresh``
+    (scipy ``Rotation``-like objects or scalar-last quaternions).  rotational_symmetry_axis: the largest IoU over the
+    prediction turned about its own axis in `symmetry_steps` equal steps."""
+    from .boxes import box_iou
+    quat = lambda r: r.as_quat() if hasattr(r, "as_quat") else r
+    iou = box_iou(position_gt, quat(orientation_gt), extent_gt, position_prediction, quat(orientation_prediction),
+                  extent_prediction, paired=True, rotational_symmetry_axis=rotational_symmetry_axis,
+                  symmetry_steps=symmetry_steps)
+    return float(iou[0])
+
+
 def correct_thresh(position_gt, position_prediction, orientation_gt, orientation_prediction, extent_gt=None,
                    extent_prediction=None, points_gt=None, points_prediction=None,
                    position_threshold: Optional[float] = None, degree_threshold: Optional[float] = None,
@@ -279,7 +293,9 @@ def correct_thresh(position_gt, position_prediction, orientation_gt, orientation
                    rotational_symmetry_axis: Optional[int] = None) -> int:
     """1 if the pose (and, with `fscore_threshold`, the reconstruction's F-score at 0.01) is within every given
     threshold, else 0.  Orientations are scipy ``Rotation`` objects (duck-typed: ``apply``, ``*``, ``inv``,
-    ``magnitude``) or scalar-last quaternions.  3D IoU is not implemented (as in the reference)."""
+    ``magnitude``) or scalar-last quaternions.  `iou_3d_threshold` needs both `extent_gt` and `extent_prediction` (the
+    boxes' full side lengths; ``iou_3d`` with `rotational_symmetry_axis` passed through); without them it raises
+    ``NotImplementedError``, as the reference always does."""
     if position_threshold is not None:
         to_np = lambda v: np.asarray(v.detach().cpu() if isinstance(v, torch.Tensor) else v, dtype=np.float64)
         position_error = np.linalg.norm(to_np(position_gt) - to_np(position_prediction))
@@ -302,7 +318,12 @@ def correct_thresh(position_gt, position_prediction, orientation_gt, orientation
         if rad_error > rad_threshold:
             return 0
     if iou_3d_threshold is not None:
-        raise NotImplementedError("3D IoU is not impemented yet.")
+        if extent_gt is None or extent_prediction is None:
+            raise NotImplementedError("3D IoU is not impemented yet. (without extent_gt and extent_prediction: the "
+                                      "boxes' side lengths are needed)")
+        if iou_3d(position_gt, orientation_gt, extent_gt, position_prediction, orientation_prediction,
+                  extent_prediction, rotational_symmetry_axis) < iou_3d_threshold:
+            return 0
     if fscore_threshold is not None:
         fscore = reconstruction_fscore(points_gt, points_prediction, 0.01)
         if fscore < fscore_threshold:

@@ -30,6 +30,7 @@ import torch
 
 from . import _lib
 from ._graphs import BoundedCache
+from .boxes import sdf_bounds
 from .differentiable_renderer import Camera, parse_sdf_grad_mode, render_depth_gpu
 from .mesh import Mesh, extract_mesh
 from .init_network import NoDepthError, ResidentInit, SDFPoseNet, adjust_categorical_posterior, nn_init
@@ -196,6 +197,34 @@ class SDFPipeline:
         for m, s in zip(meshes, scales.reshape(-1).tolist()):
             m.update_scale(float(s), rel_scale=True)
         return meshes
+
+    def bounding_boxes(self, position: torch.Tensor, orientation: torch.Tensor, scale: torch.Tensor,
+                       latent: torch.Tensor, complete_mesh: bool = True):
+        """The oriented bounding boxes of K estimates -- the 4-tuple of ``__call__`` (K = 1) or the rows of
+        ``estimate_objects`` / ``estimate_frames``: position (K,3), orientation (K,4), scale (K,), latent (K,L) ->
+        (center (K,3), orientation (K,4), extents (K,3)) float64 on the device, the boxes ``generate_meshes(latent, scale,
+        complete_mesh)[k]`` posed with row k returns from ``oriented_box()``: center = position + R(q) (scale (lo + hi)
+        / 2), extents = scale (hi - lo).  One batched decode and one ``sdfr_sdf_bounds`` call (``boxes.sdf_bounds``):
+        no mesh is made.  None if the config has no ``iso_threshold``, as ``generate_mesh``; ``ValueError`` naming the
+        row whose decoded SDF the level does not cross (where ``generate_mesh`` raises).  The reference has none."""
+        with torch.no_grad():
+            sdf = self.vae.decode(latent)
+            try:
+                level = self.config["iso_threshold"]
+            except KeyError:
+                return None
+            lo, hi, crossed = sdf_bounds(sdf[:, 0], level, complete=complete_mesh)
+            empty = torch.nonzero(crossed == 0).flatten().tolist()
+            if empty:
+                raise ValueError(f"Surface level must be within volume data range (row {empty[0]}: no grid edge of the "
+                                 f"decoded SDF crosses the level {level})")
+            # float64 from here: the boxes are what box_iou reads, and an fp32 centre would carry the position's rounding
+            lo, hi = lo.double(), hi.double()
+            s = scale.detach().reshape(-1, 1).to(lo)
+            q = orientation.detach().reshape(-1, 4).to(lo)
+            unit = q / q.norm(dim=1, keepdim=True)      # as box_iou normalises the quaternion it is given
+            center = position.detach().reshape(-1, 3).to(lo) + quaternion_apply(unit, s * ((lo + hi) / 2))
+            return center, q, s * (hi - lo)
 
     # per kind (a caller whose number of views or objects varies from call to call re-builds instead of collecting
     # buffers without bound): a loop holds its point clouds at capacity (3.7 MB per 640x480 view) and its graphs

@@ -17,7 +17,7 @@ visualisation and no logs.
                        category_str, occlusion_margin, camera (default: the Redwood camera, 640 x 480, f = 525)
     pipeline keys      threshold, max_iterations, iso_threshold, shape_optimization
     of this project    seed, frames_per_call, symmetry_axes {category_str: 0 | 1 | 2}, pose_thresholds {name:
-                       [degrees, metres]}, indices
+                       [degrees, metres]}, iou_thresholds {name: IoU} (3D IoU of the oriented boxes), indices
 The decoder's architecture is the mug decoder's of tests/golden (``vae_weights``: a state dict for it); the
 initialisation network's trained weights are not part of either repository, so without ``init_weights`` the stand-in of
 ``synthetic.plausible_init_network_state`` answers (as in tools/rendering_evaluation.py).
@@ -34,7 +34,7 @@ GOLDEN = os.path.join(ROOT, "tests", "golden")
 REDWOOD_CAMERA = {"width": 640, "height": 480, "fx": 525.0, "fy": 525.0, "cx": 319.5, "cy": 239.5, "pixel_center": 0.0}
 DEFAULTS = {"camera": REDWOOD_CAMERA, "threshold": 0.005, "max_iterations": 30, "samples": 20000,
             "iso_threshold": 0.02, "shape_optimization": True, "seed": 0, "metrics": None, "frames_per_call": 1,
-            "symmetry_axes": None, "pose_thresholds": None, "indices": None, "category_configs": {}}
+            "symmetry_axes": None, "pose_thresholds": None, "iou_thresholds": None, "indices": None, "category_configs": {}}
 DATASET_KEYS = ("root_dir", "ann_dir", "mask_pointcloud", "camera_convention", "scale_convention", "orientation_repr",
                 "orientation_grid_resolution", "remap_x_axis", "remap_y_axis", "category_str", "occlusion_margin",
                 "camera", "device")
@@ -69,7 +69,7 @@ def main():
         thresholds = {name: tuple(pair) for name, pair in thresholds.items()}
     result = evaluate_annotated(pipelines, dataset, int(cfg["samples"]), int(cfg["seed"]), cfg["metrics"], thresholds,
                                 cfg["symmetry_axes"], int(cfg["frames_per_call"]), bool(cfg["shape_optimization"]),
-                                cfg["indices"])
+                                cfg["indices"], cfg["iou_thresholds"])
     text = json.dumps(result)
     if a.out:
         with open(a.out, "w") as fh:
