@@ -55,6 +55,16 @@ __device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long k)
   }
   return k;
 }
+// dot(w, in) over n floats by one wave, every lane gets it: lane-strided fmaf chains, then the xor butterfly.  The order
+// of every fmaf and every add IS the result: the single-set and the batched head (initnet.hip), the trainers' row
+// products (initnet_train.hip, vae_train.hip) and the encoder's linear layers give the same bits because they call this.
+__device__ __forceinline__ float wave_dot(const float* __restrict__ in, const float* __restrict__ w, int n, int lane) {
+  float acc = 0.0f;
+  for (int i = lane; i < n; i += 64) acc = fmaf(w[i], in[i], acc);
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 64);
+  return acc;
+}
 
 // Per-view record written once by the set-up kernel and then read through the
 // scalar cache by every workgroup of that view.

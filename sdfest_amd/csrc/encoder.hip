@@ -173,15 +173,6 @@ __device__ __forceinline__ void relu_items(const float* __restrict__ src, float*
   for (long long i = t0; i < count; i += tstep) dst[i] = fmaxf(src[i], 0.0f);
 }
 
-// dot(w[row], in) + b over F features by one wave: fixed per-lane order, fixed butterfly; lane 0's value is the result
-__device__ __forceinline__ float wave_dot(const float* __restrict__ in, const float* __restrict__ w, int F, int lane) {
-  float acc = 0.0f;
-  for (int f = lane; f < F; f += 64) acc = fmaf(w[f], in[f], acc);
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 64);
-  return acc;
-}
-
 __device__ __forceinline__ void linear_rows(const float* __restrict__ src, float* __restrict__ dst, const EncOp& op,
                                             const float* __restrict__ prm, int wave, int nwaves, int lane) {
   for (int o = wave; o < op.cout; o += nwaves) {

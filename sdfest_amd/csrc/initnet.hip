@@ -13,6 +13,9 @@
 //     maximum over the set in the epilogue -- the (M, 2C) concatenation of a dense link never exists: its
 //     second half is the same vector for every point, so W[:, C:] . max goes into the layer's bias;
 //   * the last backbone layer (M x 1024) is never written: only its column maximum leaves the kernel.
+// The per-point layer's tile is initnet_tile.hpp (the batched layer of initnet_eval.hip runs the same one); the head
+// and the dense links' biases are one kernel, linear_rows_kernel, behind sdfr_linear_vec (one row) and
+// sdfr_linear_rows (N rows).
 #include "common.hpp"
 #include "initnet_tile.hpp"
 
@@ -21,106 +24,23 @@
 namespace sdfr {
 namespace {
 
-// Y = relu((X W^T + c) * s + t), optionally F_out = F_res + Y, and colmax[col] = max over the points.
-//   x [M][ldx] (K = cin columns used), w [cout][ldw] (first cin columns used), c / s / t [cout]
-// grid (ceil(M / 64), cout / 64); a wave = 16 points x 64 columns (4 accumulator tiles).
+// The per-point layer (pointnet_tile, initnet_tile.hpp) on ONE set: x [M][ldx], colmax[col] = max over the points.
+// grid (row blocks, ceil(cout / 64)): row block b takes the row tiles b, b + gridDim.x, ...
 __global__ __launch_bounds__(256) void pointnet_layer_kernel(
     const float* __restrict__ x, int M, int cin, int ldx, const float* __restrict__ w, int ldw,
     const float* __restrict__ cvec, const float* __restrict__ bn_scale, const float* __restrict__ bn_shift,
     const float* __restrict__ resid, float* __restrict__ y, int ldy, int cout, int* __restrict__ colmax,
     const int* __restrict__ row_count) {
-  // K runs in chunks of kChunk columns staged in LDS (X tile and W tile, rows padded by one float: a row
-  // stride of a multiple of 32 floats would put the 16 rows a wave-instruction reads into one bank)
-  __shared__ float xs[kPtsPerBlock * (kChunk + 1)];
-  __shared__ float ws[kColsPerBlock * (kChunk + 1)];
+  __shared__ float xs[kPtsPerBlock * kTileLd];
+  __shared__ float ws[kColsPerBlock * kTileLd];
   __shared__ int wave_max[4][kColsPerBlock];
-  constexpr int ld = kChunk + 1;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   // row_count (sdfr_pointnet_layer_counted): the number of points lives on the device and M is the buffers' capacity;
   // the grid's row blocks stride over the real rows (workgroup-uniform loop)
   if (row_count) M = min(max(row_count[0], 0), M);
-  const int c0 = blockIdx.y * kColsPerBlock;
-  const int row = lane & 15, kq = lane >> 4;
-  // (rows of X and W 16 bytes apart and aligned: the staging's vector form -- workgroup-uniform)
-  const bool vec_ok = ((ldx | ldw) & 3) == 0 && (((uintptr_t)x | (uintptr_t)w) & 15) == 0;
   for (int p0 = blockIdx.x * kPtsPerBlock; p0 < M; p0 += gridDim.x * kPtsPerBlock) {
-  if (p0 != (int)blockIdx.x * kPtsPerBlock) __syncthreads();   // (the previous block's LDS reads are done)
-  f32x4 acc[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) acc[j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-  const float* xa = xs + (wave * 16 + row) * ld + kq;
-  const float* wb = ws + row * ld + kq;
-  for (int kc = 0; kc < cin; kc += kChunk) {
-    const int kn = min(kChunk, cin - kc), kp = (kn + 3) & ~3;  // this chunk, padded to the MFMA's 4
-    if (kc) __syncthreads();
-    if (vec_ok && (kn & 3) == 0) {
-      // 16-byte loads, no division: thread -> (row tid / 4, vectors tid % 4, + 4, ...): four threads walk a row's 512
-      // bytes 64 at a time, and eight loads (four of X, four of W) are in flight per thread before the first LDS store
-      // (the element-wise form below: 124 dependent iterations of a divide, two 4-byte loads and two stores per thread
-      // -- 27 us per 128 -> 128 layer over 21 k points, most of it here)
-      const int r = tid >> 2, sub = tid & 3, kv = kn >> 2;
-      const bool xr = p0 + r < M, wr = c0 + r < cout;
-      const f32x4* xg = reinterpret_cast<const f32x4*>(x + (size_t)(p0 + r) * ldx + kc);
-      const f32x4* wg = reinterpret_cast<const f32x4*>(w + (size_t)(c0 + r) * ldw + kc);
-      const f32x4 zero4 = {0.0f, 0.0f, 0.0f, 0.0f};
-      for (int v0 = sub; v0 < kv; v0 += 16) {
-        f32x4 xv[4], wv[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const int v = v0 + 4 * u;
-          xv[u] = (xr && v < kv) ? xg[v] : zero4;
-          wv[u] = (wr && v < kv) ? wg[v] : zero4;
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const int v = v0 + 4 * u;
-          if (v < kv) {
-            float* xd = xs + r * ld + 4 * v;
-            float* wd = ws + r * ld + 4 * v;
-            xd[0] = xv[u].x; xd[1] = xv[u].y; xd[2] = xv[u].z; xd[3] = xv[u].w;
-            wd[0] = wv[u].x; wd[1] = wv[u].y; wd[2] = wv[u].z; wd[3] = wv[u].w;
-          }
-        }
-      }
-    } else {
-      for (int i = tid; i < kPtsPerBlock * kp; i += 256) {
-        const int r = i / kp, k = i - r * kp;
-        xs[r * ld + k] = (p0 + r < M && k < kn) ? x[(size_t)(p0 + r) * ldx + kc + k] : 0.0f;
-        ws[r * ld + k] = (c0 + r < cout && k < kn) ? w[(size_t)(c0 + r) * ldw + kc + k] : 0.0f;
-      }
-    }
-    __syncthreads();
-    for (int k0 = 0; k0 < kp; k0 += 4) {
-      const float a = xa[k0];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, wb[j * 16 * ld + k0], acc[j], 0, 0, 0);
-    }
-  }
-  // epilogue: the accumulator holds D[point 4 * kq + r][column row] of each tile
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int col = c0 + j * 16 + row;
-    const bool col_ok = col < cout;
-    const float cv = col_ok ? cvec[col] : 0.0f, s = col_ok ? bn_scale[col] : 0.0f, t = col_ok ? bn_shift[col] : 0.0f;
-    // ReLU output is >= 0 or NaN (torch's relu and max propagate NaN: pointnet.py:64-96); non-negative floats
-    // order as ints and the canonical positive NaN lies above +inf, so the set maximum is taken on the bit patterns
-    int vmax = 0;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int p = p0 + wave * 16 + kq * 4 + r;
-      const float v = relu_nan(fmaf(acc[j][r] + cv, s, t));
-      if (p < M && col_ok) {
-        vmax = max(vmax, __float_as_int(v));
-        if (y) y[(size_t)p * ldy + col] = resid ? resid[(size_t)p * ldy + col] + v : v;
-      }
-    }
-    vmax = max(vmax, __shfl_xor(vmax, 16, 64));
-    vmax = max(vmax, __shfl_xor(vmax, 32, 64));
-    if (kq == 0) wave_max[wave][j * 16 + row] = vmax;
-  }
-  __syncthreads();
-  if (tid < kColsPerBlock && c0 + tid < cout)
-    atomicMax(&colmax[c0 + tid], max(max(wave_max[0][tid], wave_max[1][tid]), max(wave_max[2][tid], wave_max[3][tid])));
+    if (p0 != (int)blockIdx.x * kPtsPerBlock) __syncthreads();   // (the previous tile's LDS reads are done)
+    pointnet_tile<false, true>(xs, ws, wave_max, nullptr, x, M, p0, cin, ldx, w, ldw, cvec, bn_scale, bn_shift, resid, y,
+                               ldy, cout, colmax);
   }
 }
 
@@ -184,24 +104,21 @@ __global__ void init_estimate_kernel(const float* __restrict__ head, int L, cons
   for (int k = 0; k < L; ++k) params[8 + k] = mean_shape ? 0.0f : head[k];
 }
 
-// y[col] = act((W[col][koff .. koff + k) . x + bias[col]) * s[col] + t[col]); one wave per column.
-__global__ __launch_bounds__(256) void linear_vec_kernel(const float* __restrict__ w, int ldw, int koff,
-                                                         const float* __restrict__ x, int k,
-                                                         const float* __restrict__ bias,
-                                                         const float* __restrict__ bn_scale,
-                                                         const float* __restrict__ bn_shift, int relu,
-                                                         float* __restrict__ y, int cout) {
+// y[n][col] = act((W[col][koff .. koff + k) . x[n] + bias[col]) * s[col] + t[col]); one wave per (row n = blockIdx.y,
+// column): the head and a dense link's per-set bias, for one set (sdfr_linear_vec) or N (sdfr_linear_rows)
+__global__ __launch_bounds__(256) void linear_rows_kernel(const float* __restrict__ w, int ldw, int koff,
+                                                          const float* __restrict__ x, int ldx, int k,
+                                                          const float* __restrict__ bias,
+                                                          const float* __restrict__ bn_scale,
+                                                          const float* __restrict__ bn_shift, int relu,
+                                                          float* __restrict__ y, int ldy, int cout) {
   const int col = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (col >= cout) return;
-  const float* wr = w + (size_t)col * ldw + koff;
-  float acc = 0.0f;
-  for (int i = lane; i < k; i += 64) acc = fmaf(wr[i], x[i], acc);
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, 64);
+  const float acc = wave_dot(x + (size_t)blockIdx.y * ldx, w + (size_t)col * ldw + koff, k, lane);
   if (lane == 0) {
     float v = acc + (bias ? bias[col] : 0.0f);
     if (bn_scale) v = fmaf(v, bn_scale[col], bn_shift[col]);
-    y[col] = relu ? relu_nan(v) : v;
+    y[(size_t)blockIdx.y * ldy + col] = relu ? relu_nan(v) : v;
   }
 }
 
@@ -389,8 +306,24 @@ extern "C" int sdfr_linear_vec(const float* w, int ldw, int koff, const float* x
   if (!w || !y || (k > 0 && !x) || ((bn_scale == nullptr) != (bn_shift == nullptr)))
     return fail(SDFR_E_NULL, "sdfr_linear_vec: NULL pointer argument");
   SDFR_HIP_TRY(hipSetDevice(device));
-  hipLaunchKernelGGL(linear_vec_kernel, dim3((unsigned)((cout + 3) / 4)), dim3(256), 0, (hipStream_t)stream, w, ldw,
-                     koff, x, k, bias, bn_scale, bn_shift, relu, y, cout);
+  hipLaunchKernelGGL(linear_rows_kernel, dim3((unsigned)((cout + 3) / 4), 1), dim3(256), 0, (hipStream_t)stream, w, ldw,
+                     koff, x, k, k, bias, bn_scale, bn_shift, relu, y, cout, cout);
+  SDFR_HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+extern "C" int sdfr_linear_rows(const float* w, int ldw, int koff, const float* x, int ldx, int k, const float* bias,
+                                const float* bn_scale, const float* bn_shift, int relu, float* y, int ldy, int cout,
+                                int N, int device, void* stream) {
+  if (N < 1 || N > 65535) return fail(SDFR_E_INVALID, "sdfr_linear_rows: N=%d rows (1 <= N <= 65535)", N);
+  if (cout < 1 || k < 0 || koff < 0 || ldw < koff + k || ldx < k || ldy < cout)
+    return fail(SDFR_E_INVALID, "sdfr_linear_rows: bad sizes cout=%d k=%d koff=%d ldw=%d ldx=%d ldy=%d", cout, k, koff,
+                ldw, ldx, ldy);
+  if (!w || !y || (k > 0 && !x) || ((bn_scale == nullptr) != (bn_shift == nullptr)))
+    return fail(SDFR_E_NULL, "sdfr_linear_rows: NULL pointer argument");
+  SDFR_HIP_TRY(hipSetDevice(device));
+  hipLaunchKernelGGL(linear_rows_kernel, dim3((unsigned)((cout + 3) / 4), (unsigned)N), dim3(256), 0,
+                     (hipStream_t)stream, w, ldw, koff, x, ldx, k, bias, bn_scale, bn_shift, relu, y, ldy, cout);
   SDFR_HIP_TRY(hipGetLastError());
   return 0;
 }

@@ -1,12 +1,12 @@
 // initnet_eval.hip -- the initialisation network under eval() on N point sets at once, and the validation numbers of
 // the reference's trainer (sdfest/initialization/scripts/train.py:344-374, :439-481):
-//   sdfr_pointnet_layer_batch   the per-point layer of initnet.hip with the set index in the grid: one launch per layer
-//                               for the whole batch, ragged sets, a per-set cvec (a dense link's b + W[:, cin:] . max[n])
-//   sdfr_linear_rows            sdfr_linear_vec on N rows: the head on [N][C_last], the per-set cvec of dense links
+//   sdfr_pointnet_layer_batch   the per-point layer with the set index in the grid: one launch per layer for the whole
+//                               batch, ragged sets, a per-set cvec (a dense link's b + W[:, cin:] . max[n])
 //   sdfr_pose_metrics           position / scale / geodesic / NLL sums of one batch into an fp64 record
-// Same tile, same k chunks and the same reductions as the single-set kernels (initnet_tile.hpp): row n of a batch has
-// the bits of the single-set call on set n.  Unlike the trainer's forward (initnet_train.hip) nothing is kept for a
-// backward: no tape, running statistics folded into a scale and a shift, and the last layer leaves only its maxima.
+// The layer is the tile of initnet_tile.hpp, the one the single-set kernel runs: row n of a batch has the bits of the
+// single-set call on set n (the head and the per-set cvec are sdfr_linear_rows, initnet.hip).  Unlike the trainer's
+// forward (initnet_train.hip) nothing is kept for a backward: no tape, running statistics folded into a scale and a
+// shift, and the last layer leaves only its maxima.
 #include "common.hpp"
 #include "initnet_tile.hpp"
 
@@ -15,29 +15,21 @@
 namespace sdfr {
 namespace {
 
-// an int that orders as the float does (negative floats too; -0 below +0); a NaN becomes the canonical positive one,
-// above +inf.  INT_MIN is no float's key: "no row yet".
-__device__ __forceinline__ int order_key(float v) {
-  if (v != v) return 0x7fc00000;
-  const int b = __float_as_int(v);
-  return b >= 0 ? b : b ^ 0x7fffffff;
-}
-
-// pointnet_layer_kernel (initnet.hip) for set blockIdx.z of x [N][M][ldx]: Y = relu((X W^T + c[n]) * s + t), optionally
+// The per-point layer (pointnet_tile) for set blockIdx.z of x [N][M][ldx]: Y = relu((X W^T + c[n]) * s + t), optionally
 // y = resid + Y, and colmax[n][col] = max over the set's rows of Y -- or of resid + Y (pool_resid: a residual link into
 // the LAST layer, whose pooled values may be negative: order keys, decoded by pool_decode_kernel).
 // grid (ceil(M / 64), ceil(cout / 64), N); a row tile lies inside one set; rows >= counts[n] are neither read into a
 // result nor written.
+template <bool pool_resid>
 __global__ __launch_bounds__(256) void pointnet_layer_batch_kernel(
     const float* __restrict__ x, const int* __restrict__ counts, int M, int cin, int ldx, const float* __restrict__ w,
     int ldw, const float* __restrict__ cvec, int cvec_stride, const float* __restrict__ bn_scale,
     const float* __restrict__ bn_shift, const float* __restrict__ resid, float* __restrict__ y, int ldy, int cout,
-    int* __restrict__ colmax, int pool_resid) {
-  __shared__ float xs[kPtsPerBlock * (kChunk + 1)];
-  __shared__ float ws[kColsPerBlock * (kChunk + 1)];
+    int* __restrict__ colmax) {
+  __shared__ float xs[kPtsPerBlock * kTileLd];
+  __shared__ float ws[kColsPerBlock * kTileLd];
   __shared__ int wave_max[4][kColsPerBlock];
-  constexpr int ld = kChunk + 1;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  f32x4 acc[4];                                 // (pointnet_tile's accumulator: own_acc)
   const int n = blockIdx.z;
   const int rows = counts ? min(max(counts[n], 0), M) : M;
   const int p0 = blockIdx.x * kPtsPerBlock;
@@ -47,81 +39,8 @@ __global__ __launch_bounds__(256) void pointnet_layer_batch_kernel(
   if (resid) resid += (size_t)n * M * ldy;
   cvec += (size_t)n * cvec_stride;
   colmax += (size_t)n * cout;
-  const int c0 = blockIdx.y * kColsPerBlock;
-  const int row = lane & 15, kq = lane >> 4;
-  const bool vec_ok = ((ldx | ldw) & 3) == 0 && (((uintptr_t)x | (uintptr_t)w) & 15) == 0;
-  f32x4 acc[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) acc[j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-  const float* xa = xs + (wave * 16 + row) * ld + kq;
-  const float* wb = ws + row * ld + kq;
-  for (int kc = 0; kc < cin; kc += kChunk) {
-    const int kn = min(kChunk, cin - kc), kp = (kn + 3) & ~3;  // this chunk, padded to the MFMA's 4
-    if (kc) __syncthreads();
-    if (vec_ok && (kn & 3) == 0) {
-      // the 16-byte staging of pointnet_layer_kernel: thread -> (row tid / 4, vectors tid % 4, + 4, ...)
-      const int r = tid >> 2, sub = tid & 3, kv = kn >> 2;
-      const bool xr = p0 + r < rows, wr = c0 + r < cout;
-      const f32x4* xg = reinterpret_cast<const f32x4*>(x + (size_t)(p0 + r) * ldx + kc);
-      const f32x4* wg = reinterpret_cast<const f32x4*>(w + (size_t)(c0 + r) * ldw + kc);
-      const f32x4 zero4 = {0.0f, 0.0f, 0.0f, 0.0f};
-      for (int v0 = sub; v0 < kv; v0 += 16) {
-        f32x4 xv[4], wv[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const int v = v0 + 4 * u;
-          xv[u] = (xr && v < kv) ? xg[v] : zero4;
-          wv[u] = (wr && v < kv) ? wg[v] : zero4;
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const int v = v0 + 4 * u;
-          if (v < kv) {
-            float* xd = xs + r * ld + 4 * v;
-            float* wd = ws + r * ld + 4 * v;
-            xd[0] = xv[u].x; xd[1] = xv[u].y; xd[2] = xv[u].z; xd[3] = xv[u].w;
-            wd[0] = wv[u].x; wd[1] = wv[u].y; wd[2] = wv[u].z; wd[3] = wv[u].w;
-          }
-        }
-      }
-    } else {
-      for (int i = tid; i < kPtsPerBlock * kp; i += 256) {
-        const int r = i / kp, k = i - r * kp;
-        xs[r * ld + k] = (p0 + r < rows && k < kn) ? x[(size_t)(p0 + r) * ldx + kc + k] : 0.0f;
-        ws[r * ld + k] = (c0 + r < cout && k < kn) ? w[(size_t)(c0 + r) * ldw + kc + k] : 0.0f;
-      }
-    }
-    __syncthreads();
-    for (int k0 = 0; k0 < kp; k0 += 4) {
-      const float a = xa[k0];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, wb[j * 16 * ld + k0], acc[j], 0, 0, 0);
-    }
-  }
-  // epilogue: the accumulator holds D[point 4 * kq + r][column row] of each tile
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int col = c0 + j * 16 + row;
-    const bool col_ok = col < cout;
-    const float cv = col_ok ? cvec[col] : 0.0f, s = col_ok ? bn_scale[col] : 0.0f, t = col_ok ? bn_shift[col] : 0.0f;
-    int vmax = pool_resid ? INT_MIN : 0;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int p = p0 + wave * 16 + kq * 4 + r;
-      const float v = relu_nan(fmaf(acc[j][r] + cv, s, t));
-      if (p < rows && col_ok) {
-        const float o = resid ? resid[(size_t)p * ldy + col] + v : v;
-        if (y) y[(size_t)p * ldy + col] = o;
-        vmax = max(vmax, pool_resid ? order_key(o) : __float_as_int(v));
-      }
-    }
-    vmax = max(vmax, __shfl_xor(vmax, 16, 64));
-    vmax = max(vmax, __shfl_xor(vmax, 32, 64));
-    if (kq == 0) wave_max[wave][j * 16 + row] = vmax;
-  }
-  __syncthreads();
-  if (tid < kColsPerBlock && c0 + tid < cout)
-    atomicMax(&colmax[c0 + tid], max(max(wave_max[0][tid], wave_max[1][tid]), max(wave_max[2][tid], wave_max[3][tid])));
+  pointnet_tile<pool_resid, false>(xs, ws, wave_max, &acc, x, rows, p0, cin, ldx, w, ldw, cvec, bn_scale, bn_shift, resid,
+                                   y, ldy, cout, colmax);
 }
 
 static __global__ void fill_int_kernel(int* __restrict__ p, size_t n, int value) {
@@ -135,29 +54,6 @@ static __global__ void pool_decode_kernel(int* __restrict__ p, size_t n) {
   if (i >= n) return;
   const int k = p[i];
   p[i] = k == INT_MIN ? 0 : (k >= 0 ? k : k ^ 0x7fffffff);
-}
-
-// linear_vec_kernel (initnet.hip) on row blockIdx.y: one wave per (row, column), the same lane-strided fmaf chain and
-// the same butterfly
-__global__ __launch_bounds__(256) void linear_rows_kernel(const float* __restrict__ w, int ldw, int koff,
-                                                          const float* __restrict__ x, int ldx, int k,
-                                                          const float* __restrict__ bias,
-                                                          const float* __restrict__ bn_scale,
-                                                          const float* __restrict__ bn_shift, int relu,
-                                                          float* __restrict__ y, int ldy, int cout) {
-  const int col = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (col >= cout) return;
-  const float* wr = w + (size_t)col * ldw + koff;
-  const float* xr = x + (size_t)blockIdx.y * ldx;
-  float acc = 0.0f;
-  for (int i = lane; i < k; i += 64) acc = fmaf(wr[i], xr[i], acc);
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, 64);
-  if (lane == 0) {
-    float v = acc + (bias ? bias[col] : 0.0f);
-    if (bn_scale) v = fmaf(v, bn_scale[col], bn_shift[col]);
-    y[(size_t)blockIdx.y * ldy + col] = relu ? relu_nan(v) : v;
-  }
 }
 
 // One wave per sample: sample[n] = {|p - p*|, |s - s*|, 2 acos(clip(|q . q*|, 0, 1)), logsumexp(logits) - logits[target]}
@@ -249,27 +145,11 @@ extern "C" int sdfr_pointnet_layer_batch(const float* x, const int* counts, int 
                      pool_resid ? INT_MIN : 0);
   const unsigned row_blocks = (unsigned)((M_capacity + kPtsPerBlock - 1) / kPtsPerBlock);
   const unsigned col_blocks = (unsigned)((cout + kColsPerBlock - 1) / kColsPerBlock);
-  hipLaunchKernelGGL(pointnet_layer_batch_kernel, dim3(row_blocks, col_blocks, (unsigned)N), dim3(256), 0, st, x, counts,
-                     M_capacity, cin, ldx, w, ldw, cvec, cvec_stride, bn_scale, bn_shift, resid, y, ldy, cout, cm,
-                     pool_resid ? 1 : 0);
+  hipLaunchKernelGGL(pool_resid ? pointnet_layer_batch_kernel<true> : pointnet_layer_batch_kernel<false>,
+                     dim3(row_blocks, col_blocks, (unsigned)N), dim3(256), 0, st, x, counts, M_capacity, cin, ldx, w, ldw,
+                     cvec, cvec_stride, bn_scale, bn_shift, resid, y, ldy, cout, cm);
   if (pool_resid)
     hipLaunchKernelGGL(pool_decode_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, st, cm, words);
-  SDFR_HIP_TRY(hipGetLastError());
-  return 0;
-}
-
-extern "C" int sdfr_linear_rows(const float* w, int ldw, int koff, const float* x, int ldx, int k, const float* bias,
-                                const float* bn_scale, const float* bn_shift, int relu, float* y, int ldy, int cout,
-                                int N, int device, void* stream) {
-  if (N < 1 || N > 65535) return fail(SDFR_E_INVALID, "sdfr_linear_rows: N=%d rows (1 <= N <= 65535)", N);
-  if (cout < 1 || k < 0 || koff < 0 || ldw < koff + k || ldx < k || ldy < cout)
-    return fail(SDFR_E_INVALID, "sdfr_linear_rows: bad sizes cout=%d k=%d koff=%d ldw=%d ldx=%d ldy=%d", cout, k, koff,
-                ldw, ldx, ldy);
-  if (!w || !y || (k > 0 && !x) || ((bn_scale == nullptr) != (bn_shift == nullptr)))
-    return fail(SDFR_E_NULL, "sdfr_linear_rows: NULL pointer argument");
-  SDFR_HIP_TRY(hipSetDevice(device));
-  hipLaunchKernelGGL(linear_rows_kernel, dim3((unsigned)((cout + 3) / 4), (unsigned)N), dim3(256), 0,
-                     (hipStream_t)stream, w, ldw, koff, x, ldx, k, bias, bn_scale, bn_shift, relu, y, ldy, cout);
   SDFR_HIP_TRY(hipGetLastError());
   return 0;
 }

@@ -391,12 +391,7 @@ __global__ __launch_bounds__(256) void train_rows_linear_kernel(const float* __r
   const int lane = threadIdx.x & 63;
   if (o >= (long long)N * C) return;
   const int n = (int)(o / C), col = (int)(o % C);
-  const float* wr = w + (size_t)col * ldw + koff;
-  const float* xr = x + (size_t)n * K;
-  float acc = 0.0f;
-  for (int i = lane; i < K; i += 64) acc = fmaf(wr[i], xr[i], acc);
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, 64);
+  const float acc = wave_dot(x + (size_t)n * K, w + (size_t)col * ldw + koff, K, lane);
   if (lane == 0) y[o] = acc + bias[col];
 }
 

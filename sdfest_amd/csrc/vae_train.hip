@@ -139,15 +139,6 @@ __global__ __launch_bounds__(kThreads) void train_conv_forward_kernel(const floa
   }
 }
 
-// dot(w, in) over F features by one wave: fixed per-lane order, fixed butterfly
-__device__ __forceinline__ float train_wave_dot(const float* __restrict__ in, const float* __restrict__ w, int F, int lane) {
-  float acc = 0.0f;
-  for (int f = lane; f < F; f += 64) acc = fmaf(w[f], in[f], acc);
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 64);
-  return acc;
-}
-
 // a wave per (sample, output row), grid-stride
 __global__ __launch_bounds__(kThreads) void train_linear_forward_kernel(const float* __restrict__ in, float* __restrict__ out,
                                                                         TrainOp op, const float* __restrict__ prm, int N) {
@@ -156,7 +147,7 @@ __global__ __launch_bounds__(kThreads) void train_linear_forward_kernel(const fl
   for (long long it = (long long)blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6); it < total; it += waves) {
     const long long nb = it / op.cout;
     const int o = (int)(it - nb * op.cout);
-    float r = train_wave_dot(in + (size_t)nb * op.cin, prm + op.w_off + (size_t)o * op.cin, op.cin, lane) +
+    float r = wave_dot(in + (size_t)nb * op.cin, prm + op.w_off + (size_t)o * op.cin, op.cin, lane) +
               prm[op.b_off + o];
     if (op.relu) r = fmaxf(r, 0.0f);
     if (lane == 0) out[(size_t)nb * op.cout + o] = r;
@@ -233,8 +224,8 @@ __global__ __launch_bounds__(kThreads) void train_heads_forward_kernel(const flo
   for (long long it = (long long)blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6); it < total; it += waves) {
     const int nb = (int)(it / L), j = (int)(it - (long long)nb * L);
     const float* hin = h + (size_t)nb * F;
-    const float mu = train_wave_dot(hin, prm + hm_w + (size_t)j * F, F, lane) + prm[hm_b + j];
-    const float lv = train_wave_dot(hin, prm + hl_w + (size_t)j * F, F, lane) + prm[hl_b + j];
+    const float mu = wave_dot(hin, prm + hm_w + (size_t)j * F, F, lane) + prm[hm_b + j];
+    const float lv = wave_dot(hin, prm + hl_w + (size_t)j * F, F, lane) + prm[hl_b + j];
     if (lane == 0) {
       means[it] = mu;
       log_var[it] = lv;

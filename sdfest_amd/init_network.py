@@ -14,7 +14,8 @@ Weights come as the state dict of the reference's ``SDFPoseNet`` (keys ``_backbo
 scale and a shift per channel.  The trained weights of the paper are not in the reference repository
 (download URLs only, mug.yaml:115-116); tests use seeded random weights of the mug architecture.
 """
-from typing import Dict, List, Optional, Sequence, Tuple
+from types import MappingProxyType
+from typing import Dict, Mapping, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -84,6 +85,7 @@ class SDFPoseNet:
         self.head = [_Layer(state_dict, f"_head._linear_layers.{i}", f"_head._bn_layers.{i}" if bn_h else None, self.dev)
                      for i in range(len(head["mlp_out_sizes"]))]
         self.final = _Layer(state_dict, "_head._final_layer", None, self.dev)
+        self._backbone_plan = None                  # backbone_plan(), at its first call
         self.shape_dimension = int(shape_dimension)
         self.orientation_repr = head.get("orientation_repr", "quaternion")
         if self.orientation_repr == "discretized":
@@ -99,8 +101,10 @@ class SDFPoseNet:
     def _st(self):
         return torch.cuda.current_stream(self.dev).cuda_stream
 
-    def _vec(self, layer: _Layer, koff: int, x: Optional[torch.Tensor], k: int, bn: bool, relu: bool) -> torch.Tensor:
-        y = torch.empty(layer.cout, dtype=torch.float32, device=self.dev)
+    def _vec(self, layer: _Layer, koff: int, x: Optional[torch.Tensor], k: int, bn: bool, relu: bool,
+             out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """act(bn(W[:, koff:koff + k] x + b)) of one vector (cout,), into `out` if given"""
+        y = out if out is not None else torch.empty(layer.cout, dtype=torch.float32, device=self.dev)
         rc = self.L.sdfr_linear_vec(layer.w.data_ptr(), layer.cin_total, koff, x.data_ptr() if x is not None else None, k,
                                     layer.b.data_ptr(), layer.scale.data_ptr() if bn else None,
                                     layer.shift.data_ptr() if bn else None, int(relu), y.data_ptr(), layer.cout,
@@ -108,65 +112,8 @@ class SDFPoseNet:
         _lib.check(rc, "sdfr_linear_vec")
         return y
 
-    def features(self, points: torch.Tensor) -> torch.Tensor:
-        """VanillaPointNet.forward on ONE set (M, in_size) -> (C_last,) (pointnet.py:61-96)."""
-        x = points.to(device=self.dev, dtype=torch.float32).contiguous()
-        if x.dim() != 2 or x.shape[1] != self.in_size or x.shape[0] < 1:
-            raise RuntimeError(f"points must have shape (M >= 1, {self.in_size})")
-        M = x.shape[0]
-        F, F_width = x, self.in_size          # the per-point part of `prev_out`
-        G = None                              # the broadcast part of `prev_out` (dense links)
-        prev_width = self.in_size             # width of prev_out including a concatenated maximum
-        n = len(self.pn)
-        for i, layer in enumerate(self.pn):
-            last = i == n - 1
-            if layer.cin_total != F_width + (G.numel() if G is not None else 0):
-                raise RuntimeError("state dict does not match the backbone configuration")
-            # bias of the layer, plus the constant the concatenated maximum contributes to every point
-            cvec = self._vec(layer, F_width, G, G.numel(), False, False) if G is not None else layer.b
-            out_width = layer.cout * (2 if (self.dense and not last) else 1)
-            use_res = self.residual and prev_width == out_width     # `prev_out.shape == out.shape` (:88-90)
-            colmax = torch.empty(layer.cout, dtype=torch.float32, device=self.dev)
-            store = not last or use_res
-            Y = torch.empty((M, layer.cout), dtype=torch.float32, device=self.dev) if store else None
-            res_F = None
-            if use_res and F_width == layer.cout:
-                res_F = F
-            elif use_res:
-                # prev_out = [F | G] (a dense link) into a last layer as wide as both halves together
-                res_F = torch.cat([F, G.reshape(1, -1).expand(M, -1)], dim=1).contiguous()
-            rc = self.L.sdfr_pointnet_layer(F.data_ptr(), M, F_width, F.shape[1], layer.w.data_ptr(), layer.cin_total,
-                                            cvec.data_ptr(), layer.scale.data_ptr(), layer.shift.data_ptr(),
-                                            res_F.data_ptr() if res_F is not None else None,
-                                            Y.data_ptr() if Y is not None else None, layer.cout, layer.cout,
-                                            colmax.data_ptr(), self.dev.index, self._st())
-            _lib.check(rc, "sdfr_pointnet_layer")
-            if self.dense and not last:
-                # out = cat(out, max(out)); a residual adds prev_out = [F | G] to both halves
-                G = colmax + G if (use_res and G is not None) else colmax
-            else:
-                G = None
-            if last:
-                # torch.max over the points of the final `out` (after a residual, if any)
-                return colmax if not use_res else Y.max(dim=0).values
-            F, F_width, prev_width = Y, layer.cout, out_width
-        raise AssertionError
-
-    def head_forward(self, feature: torch.Tensor):
-        """SDFPoseHead.forward on one feature vector (sdf_pose_network.py:70-115): (latent (1,L), position
-        (1,3), scale (1,), orientation (1,4) normalised quaternion or (1,C) logits)."""
-        out = feature
-        for layer in self.head:
-            out = self._vec(layer, 0, out, layer.cin_total, True, True)
-        out = self._vec(self.final, 0, out, self.final.cin_total, False, False)[None]
-        sd = self.shape_dimension
-        orientation = out[:, sd + 4:]
-        if self.orientation_repr == "quaternion":
-            orientation = orientation / torch.sqrt(torch.sum(orientation ** 2, 1, keepdim=True))
-        return out[:, 0:sd], out[:, sd:sd + 3], out[:, sd + 3], orientation
-
     def _rows(self, layer: _Layer, koff: int, x: torch.Tensor, k: int, bn: bool, relu: bool) -> torch.Tensor:
-        """``_vec`` on the N rows of x (N, >= k): (N, cout)"""
+        """``_vec`` on the N rows of x (N, >= k): (N, cout) -- the same kernel, a row per ``blockIdx.y``"""
         N = x.shape[0]
         y = torch.empty((N, layer.cout), dtype=torch.float32, device=self.dev)
         rc = self.L.sdfr_linear_rows(layer.w.data_ptr(), layer.cin_total, koff, x.data_ptr(), x.shape[1], k,
@@ -176,6 +123,95 @@ class SDFPoseNet:
         _lib.check(rc, "sdfr_linear_rows")
         return y
 
+    def backbone_plan(self) -> Tuple[Mapping, ...]:
+        """What VanillaPointNet.forward (pointnet.py:61-96) decides per layer, decided once -- one record per layer:
+        ``layer``; ``F_width`` / ``G_width``, the per-point and the broadcast part (a dense link's set maximum) of its
+        input `prev_out`; ``out_width``, its output including a concatenated maximum; ``use_res``, a residual link
+        (`prev_out.shape == out.shape`, :88-90); ``res_cat``, that residual is [F | G] concatenated (a dense link into
+        a last layer as wide as both halves together), not F alone; ``last``.  Built at the first call (a state dict
+        that does not match the configuration raises there), then the same read-only records every time."""
+        if self._backbone_plan is None:
+            plan = []
+            F_width, G_width, prev_width, n = self.in_size, 0, self.in_size, len(self.pn)
+            for i, layer in enumerate(self.pn):
+                last = i == n - 1
+                if layer.cin_total != F_width + G_width:
+                    raise RuntimeError("state dict does not match the backbone configuration")
+                out_width = layer.cout * (2 if (self.dense and not last) else 1)
+                use_res = self.residual and prev_width == out_width
+                plan.append(MappingProxyType(dict(
+                    layer=layer, F_width=F_width, G_width=G_width, out_width=out_width, use_res=use_res,
+                    res_cat=use_res and F_width != layer.cout, last=last)))
+                G_width = layer.cout if (self.dense and not last) else 0
+                F_width, prev_width = layer.cout, out_width
+            self._backbone_plan = tuple(plan)
+        return self._backbone_plan
+
+    def _backbone(self, x: torch.Tensor, cnt: Optional[torch.Tensor], single: bool) -> torch.Tensor:
+        """the backbone on the N sets x (N, M, in_size) -> (N, C_last).  single (N = 1, no counts): the single-set
+        kernel, and torch pools a residual into the last layer; otherwise one batched launch per layer, whose kernel
+        pools that residual itself (``pool_resid``)."""
+        N, M = x.shape[0], x.shape[1]
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        F, G = x, None       # the per-point part of `prev_out`, and its broadcast part (N, G_width): one row per set
+        for p in self.backbone_plan():
+            layer, F_width, last = p["layer"], p["F_width"], p["last"]
+            # bias of the layer, plus the constant the concatenated maximum contributes to every point
+            cvec = self._rows(layer, F_width, G, p["G_width"], False, False) if G is not None else layer.b
+            pool = last and p["use_res"]
+            colmax = torch.empty((N, layer.cout), dtype=torch.float32, device=self.dev)
+            # the last layer stores nothing but its maxima, unless torch is to pool its residual sum
+            store = not last or (pool and single)
+            Y = torch.empty((N, M, layer.cout), dtype=torch.float32, device=self.dev) if store else None
+            res_F = None
+            if p["res_cat"]:
+                res_F = torch.cat([F, G[:, None, :].expand(-1, M, -1)], dim=2).contiguous()
+            elif p["use_res"]:
+                res_F = F
+            if single:
+                rc = self.L.sdfr_pointnet_layer(F.data_ptr(), M, F_width, F.shape[2], layer.w.data_ptr(), layer.cin_total,
+                                                cvec.data_ptr(), layer.scale.data_ptr(), layer.shift.data_ptr(),
+                                                ptr(res_F), ptr(Y), layer.cout, layer.cout, colmax.data_ptr(),
+                                                self.dev.index, self._st())
+                _lib.check(rc, "sdfr_pointnet_layer")
+            else:
+                rc = self.L.sdfr_pointnet_layer_batch(
+                    F.data_ptr(), ptr(cnt), N, M, F_width, F.shape[2], layer.w.data_ptr(), layer.cin_total,
+                    cvec.data_ptr(), layer.cout if G is not None else 0, layer.scale.data_ptr(), layer.shift.data_ptr(),
+                    ptr(res_F), ptr(Y), layer.cout, layer.cout, int(pool), colmax.data_ptr(), self.dev.index, self._st())
+                _lib.check(rc, "sdfr_pointnet_layer_batch")
+            if last:
+                # torch.max over the points of the final `out` (after a residual, if any)
+                return Y.max(dim=1).values if Y is not None else colmax
+            # out = cat(out, max(out)); a residual adds prev_out = [F | G] to both halves
+            G = (colmax + G if (p["use_res"] and G is not None) else colmax) if self.dense else None
+            F = Y
+        raise AssertionError
+
+    def features(self, points: torch.Tensor) -> torch.Tensor:
+        """VanillaPointNet.forward on ONE set (M, in_size) -> (C_last,) (pointnet.py:61-96)."""
+        x = points.to(device=self.dev, dtype=torch.float32).contiguous()
+        if x.dim() != 2 or x.shape[1] != self.in_size or x.shape[0] < 1:
+            raise RuntimeError(f"points must have shape (M >= 1, {self.in_size})")
+        return self._backbone(x[None], None, True)[0]
+
+    def _split(self, out: torch.Tensor):
+        """the head's output rows (N, L + 4 + C) or (N, L + 8) -> (latent (N,L), position (N,3), scale (N,), orientation:
+        (N,C) logits, or the (N,4) quaternion normalised) (sdf_pose_network.py:93-115)"""
+        sd = self.shape_dimension
+        orientation = out[:, sd + 4:]
+        if self.orientation_repr == "quaternion":
+            orientation = orientation / torch.sqrt(torch.sum(orientation ** 2, 1, keepdim=True))
+        return out[:, 0:sd], out[:, sd:sd + 3], out[:, sd + 3], orientation
+
+    def head_forward(self, feature: torch.Tensor):
+        """SDFPoseHead.forward on one feature vector (sdf_pose_network.py:70-115): (latent (1,L), position
+        (1,3), scale (1,), orientation (1,4) normalised quaternion or (1,C) logits)."""
+        out = feature
+        for layer in self.head:
+            out = self._vec(layer, 0, out, layer.cin_total, True, True)
+        return self._split(self._vec(self.final, 0, out, self.final.cin_total, False, False)[None])
+
     def features_batch(self, points: torch.Tensor, counts=None) -> torch.Tensor:
         """VanillaPointNet.forward on N sets (N, M, in_size) -> (N, C_last): one launch per per-point layer, one
         ``sdfr_linear_rows`` per dense link, no synchronisation.  `counts` (int tensor or list, N entries): the real
@@ -184,46 +220,12 @@ class SDFPoseNet:
         x = points.to(device=self.dev, dtype=torch.float32).contiguous()
         if x.dim() != 3 or x.shape[2] != self.in_size or x.shape[0] < 1 or x.shape[1] < 1:
             raise RuntimeError(f"points must have shape (N >= 1, M >= 1, {self.in_size})")
-        N, M = x.shape[0], x.shape[1]
         cnt = None
         if counts is not None:
             cnt = torch.as_tensor(counts).to(device=self.dev, dtype=torch.int32).contiguous()
-            if cnt.shape != (N,):
-                raise RuntimeError(f"counts must have {N} entries")
-        F, F_width = x, self.in_size          # as in `features`; G is (N, width): one broadcast part per set
-        G = None
-        prev_width = self.in_size
-        n = len(self.pn)
-        for i, layer in enumerate(self.pn):
-            last = i == n - 1
-            if layer.cin_total != F_width + (G.shape[1] if G is not None else 0):
-                raise RuntimeError("state dict does not match the backbone configuration")
-            cvec = self._rows(layer, F_width, G, G.shape[1], False, False) if G is not None else layer.b
-            out_width = layer.cout * (2 if (self.dense and not last) else 1)
-            use_res = self.residual and prev_width == out_width
-            colmax = torch.empty((N, layer.cout), dtype=torch.float32, device=self.dev)
-            # the last layer stores nothing but its maxima: with a residual the kernel pools resid + Y itself
-            Y = torch.empty((N, M, layer.cout), dtype=torch.float32, device=self.dev) if not last else None
-            res_F = None
-            if use_res and F_width == layer.cout:
-                res_F = F
-            elif use_res:
-                res_F = torch.cat([F, G[:, None, :].expand(-1, M, -1)], dim=2).contiguous()
-            rc = self.L.sdfr_pointnet_layer_batch(
-                F.data_ptr(), cnt.data_ptr() if cnt is not None else None, N, M, F_width, F.shape[2], layer.w.data_ptr(),
-                layer.cin_total, cvec.data_ptr(), layer.cout if G is not None else 0, layer.scale.data_ptr(),
-                layer.shift.data_ptr(), res_F.data_ptr() if res_F is not None else None,
-                Y.data_ptr() if Y is not None else None, layer.cout, layer.cout, int(last and use_res),
-                colmax.data_ptr(), self.dev.index, self._st())
-            _lib.check(rc, "sdfr_pointnet_layer_batch")
-            if last:
-                return colmax
-            if self.dense:
-                G = colmax + G if (use_res and G is not None) else colmax
-            else:
-                G = None
-            F, F_width, prev_width = Y, layer.cout, out_width
-        raise AssertionError
+            if cnt.shape != (x.shape[0],):
+                raise RuntimeError(f"counts must have {x.shape[0]} entries")
+        return self._backbone(x, cnt, False)
 
     def rows_batch(self, points: torch.Tensor, counts=None) -> torch.Tensor:
         """the head's output rows (N, L + 4 + C) or (N, L + 8) -- the quaternion before its normalisation -- of N sets:
@@ -236,12 +238,7 @@ class SDFPoseNet:
     def forward_batch(self, points: torch.Tensor, counts=None):
         """SDFPoseNet.forward on a batch (N, M, in_size): (latent (N,L), position (N,3), scale (N,), orientation (N,4)
         normalised quaternion or (N,C) logits)."""
-        out = self.rows_batch(points, counts)
-        sd = self.shape_dimension
-        orientation = out[:, sd + 4:]
-        if self.orientation_repr == "quaternion":
-            orientation = orientation / torch.sqrt(torch.sum(orientation ** 2, 1, keepdim=True))
-        return out[:, 0:sd], out[:, sd:sd + 3], out[:, sd + 3], orientation
+        return self._split(self.rows_batch(points, counts))
 
     def grid_quats(self) -> Optional[torch.Tensor]:
         """the orientation of every cell (C, 4) on the device, built once; None for the quaternion head"""
@@ -385,24 +382,14 @@ class ResidentInit:
         H, W = camera.height, camera.width
         self.H, self.W, M = H, W, H * W
         f32 = dict(dtype=torch.float32, device=self.dev)
-        # the plan of the backbone: what `features` decides per call, decided once
-        self.plan = []
-        F_width, G_width, prev_width, n = net.in_size, 0, net.in_size, len(net.pn)
-        for i, layer in enumerate(net.pn):
-            last = i == n - 1
-            if layer.cin_total != F_width + G_width:
-                raise RuntimeError("state dict does not match the backbone configuration")
-            out_width = layer.cout * (2 if (net.dense and not last) else 1)
-            use_res = net.residual and prev_width == out_width
-            if use_res and F_width != layer.cout:
+        self.plan = net.backbone_plan()
+        for p in self.plan:
+            if p["res_cat"]:
                 raise NotImplementedError("a residual link over a concatenated dense input: use nn_init")
-            if last and use_res:
+            if p["last"] and p["use_res"]:
                 raise NotImplementedError("a residual link into the last backbone layer: use nn_init")
-            self.plan.append(dict(layer=layer, F_width=F_width, G_width=G_width, use_res=use_res, last=last,
-                                  store=not last))
-            G_width = layer.cout if (net.dense and not last) else 0
-            F_width, prev_width = layer.cout, out_width
-        width = max([p["layer"].cout for p in self.plan if p["store"]] + [4])
+        # (so every layer but the last stores its output, and the last leaves only its maxima)
+        width = max([p["layer"].cout for p in self.plan if not p["last"]] + [4])
         self.points = torch.zeros((M, 3), **f32)
         self.act = [torch.zeros((M, width), **f32) for _ in range(2)]       # ping-pong per-point activations
         self.colmax = [torch.zeros(p["layer"].cout, **f32) for p in self.plan]
@@ -439,18 +426,11 @@ class ResidentInit:
         self._host_counts = torch.zeros(self.V, dtype=torch.int32).pin_memory()
         self._counts_event = None
 
-    def _vec(self, layer, koff, x, k, bn, relu, out):
-        rc = self.L.sdfr_linear_vec(layer.w.data_ptr(), layer.cin_total, koff, x.data_ptr() if x is not None else None, k,
-                                    layer.b.data_ptr(), layer.scale.data_ptr() if bn else None,
-                                    layer.shift.data_ptr() if bn else None, int(relu), out.data_ptr(), layer.cout,
-                                    self.dev.index, self._st)
-        _lib.check(rc, "sdfr_linear_vec")
-
     def _sequence(self, depth: torch.Tensor, cam_pos: torch.Tensor, cam_quat: torch.Tensor, has_prior: bool,
                   has_train: bool):
         """the launches, on the current stream; depth (V,H,W) float32 contiguous on the device"""
         L, net, d = self.L, self.net, self.dev.index
-        self._st = st = torch.cuda.current_stream(self.dev).cuda_stream
+        st = torch.cuda.current_stream(self.dev).cuda_stream     # (the one `net._vec` launches on)
         fx, fy, cx0, cy0, _ = self.cam.get_pinhole_camera_parameters(0.0)
         W, H, M = self.W, self.H, self.W * self.H
         ws = self.ws[(-self.ws.data_ptr()) % 16:]
@@ -474,11 +454,10 @@ class ResidentInit:
             for i, p in enumerate(self.plan):
                 layer = p["layer"]
                 if G is not None:     # bias + what the concatenated set maximum contributes to every point
-                    self._vec(layer, p["F_width"], G, p["G_width"], False, False, self.cvec[i])
-                    cvec = self.cvec[i]
+                    cvec = net._vec(layer, p["F_width"], G, p["G_width"], False, False, out=self.cvec[i])
                 else:
                     cvec = layer.b
-                Y = self.act[i % 2] if p["store"] else None
+                Y = self.act[i % 2] if not p["last"] else None
                 ldy = Y.shape[1] if Y is not None else layer.cout
                 rc = L.sdfr_pointnet_layer_counted(
                     F.data_ptr(), self.count.data_ptr(), M, p["F_width"], ldF, layer.w.data_ptr(), layer.cin_total,
@@ -498,10 +477,8 @@ class ResidentInit:
                     F, ldF = Y, ldy
             out = self.colmax[-1]
             for j, layer in enumerate(net.head):
-                self._vec(layer, 0, out, layer.cin_total, True, True, self.head_vec[j])
-                out = self.head_vec[j]
-            self._vec(net.final, 0, out, net.final.cin_total, False, False, self.head_vec[-1])
-            head = self.head_vec[-1]
+                out = net._vec(layer, 0, out, layer.cin_total, True, True, out=self.head_vec[j])
+            head = net._vec(net.final, 0, out, net.final.cin_total, False, False, out=self.head_vec[-1])
             sd = net.shape_dimension
             if self.discretized:
                 _lib.check(L.sdfr_orientation_posterior(

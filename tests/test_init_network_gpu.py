@@ -163,6 +163,47 @@ def test_resident_init_matches_the_host_driven_form(gold, mug_net):
     assert ri.empty_views() == []                                      # "first" never looks at view 1
 
 
+@pytest.mark.parametrize("cin", [128, 3])        # 16-byte staging (ldx = 128) / element-wise staging (ldx = 3)
+def test_counted_layer_strides_to_the_bits_of_the_uncounted(cin):
+    """``sdfr_pointnet_layer_counted`` where its grid strides over the row tiles, against ``sdfr_pointnet_layer`` on
+    the counted rows, bit for bit.  cout = 1024 is 16 column blocks, so the counted grid has 1024 / 16 = 64 row blocks
+    = 4096 rows per sweep; a capacity of 8197 rows is two sweeps and a ragged third.  Counts: all of it, a second sweep
+    that ends inside a tile, one tile, one row.  Rows past the count are NaN and must reach nothing; the rows of `y`
+    past it keep what they held."""
+    from sdfest_amd import _lib
+    L, dev = _lib.lib(), torch.device("cuda", torch.cuda.current_device())
+    M, cout, sentinel = 8197, 1024, -7.5
+    g = torch.Generator().manual_seed(cin)
+    rnd = lambda *shape: torch.randn(*shape, generator=g).to(dev)
+    x, w, cvec, resid = rnd(M, cin), rnd(cout, cin) / cin ** 0.5, rnd(cout), rnd(M, cout)
+    scale, shift = 0.5 + torch.rand(cout, generator=g).to(dev), rnd(cout)
+    w[::37] *= 4.0           # (some columns large in magnitude, and ...
+    shift[5::37] = -50.0     # ... some negative on every row before the ReLU: their maximum is the ReLU's 0)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    for count in (M, 4100, 64, 1):
+        xc = x.clone()
+        xc[count:] = float("nan")
+        cnt = torch.tensor([count], dtype=torch.int32, device=dev)
+        for with_y in (True, False):
+            res = resid if with_y else None
+            y = torch.full((M, cout), sentinel, device=dev) if with_y else None
+            y_ref = torch.full((count, cout), sentinel, device=dev) if with_y else None
+            colmax, colmax_ref = torch.empty(cout, device=dev), torch.empty(cout, device=dev)
+            _lib.check(L.sdfr_pointnet_layer_counted(xc.data_ptr(), cnt.data_ptr(), M, cin, cin, w.data_ptr(), cin,
+                                                     cvec.data_ptr(), scale.data_ptr(), shift.data_ptr(), ptr(res), ptr(y),
+                                                     cout, cout, colmax.data_ptr(), dev.index, st),
+                       "sdfr_pointnet_layer_counted")
+            _lib.check(L.sdfr_pointnet_layer(xc.data_ptr(), count, cin, cin, w.data_ptr(), cin, cvec.data_ptr(),
+                                             scale.data_ptr(), shift.data_ptr(), ptr(res), ptr(y_ref), cout, cout,
+                                             colmax_ref.data_ptr(), dev.index, st), "sdfr_pointnet_layer")
+            assert torch.equal(colmax, colmax_ref), (count, with_y)
+            assert float(colmax_ref[5]) == 0.0 and float(colmax_ref.max()) > 0.0
+            if with_y:
+                assert torch.equal(y[:count], y_ref), count
+                assert bool((y[count:] == sentinel).all()), count
+
+
 def test_nan_points_reach_the_outputs(gold, mug_net):
     """torch's relu and max propagate NaN (pointnet.py:64-96): a NaN coordinate (or weight) must come out as NaN, not
     as a plausible pose computed from `fmaxf(NaN, 0) = 0` (round-2 advisor finding)."""
