@@ -91,6 +91,8 @@
  *        sdfr_render_information[_workspace_bytes]
  *  15. [unstable] BOXES: the oriented box of an estimate without its mesh, and the exact 3D IoU of oriented boxes
  *        sdfr_sdf_bounds, sdfr_box_iou
+ *  16. [unstable] AVERAGE PRECISION: pose errors of pairs, detection matching and the AP integral (the evaluation's mAP)
+ *        sdfr_pose_pair_errors, sdfr_ap_match, sdfr_ap_integrate
  * (Within the file the groups follow the order in which the reference's code runs; every declaration carries the
  * reference file:line it replaces.)
  */
@@ -1495,6 +1497,82 @@ SDFR_API int sdfr_sdf_bounds(const float* sdf, int N, int R, int complete, float
 SDFR_API int sdfr_box_iou(const double* boxes_a, int N, const double* boxes_b, int M, int mode,
                           int symmetry_axis, int symmetry_steps,
                           double* iou, double* intersection /* nullable */, int device, void* stream);
+
+/* ==== 16. AVERAGE PRECISION =================================================================== */
+/* Detection matching and average precision over IoU thresholds and over (degrees, distance) thresholds, per class: the
+ * number category-level pose estimation reports.  The reference has no such code; THE PROTOCOL below is this project's
+ * own statement of it, after the published NOCS evaluation -- parity with a third-party script is not claimed.
+ *   Groups.    Detections and ground truths carry a frame id and an integer class id; a GROUP is one (frame, class) and
+ *              only detections and ground truths of one group can match.
+ *   Order.     Inside a group the detections are processed by descending score, ties by the lower input index.
+ *   Pairs.     Every (detection i, ground truth j) of a group has four doubles: 0 iou, 1 degrees, 2 distance (metres),
+ *              3 key, the preference among ground truths.
+ *   Criterion. (iou_min, degrees_max, distance_max); a pair is ADMISSIBLE iff iou >= iou_min && degrees <= degrees_max
+ *              && distance <= distance_max.  -inf / +inf switch a test off; a pair with a NaN entry (the key included) is
+ *              never admissible.
+ *   Matching.  Criteria are independent of each other.  For one criterion, in detection order, a detection takes the
+ *              admissible, still unmatched ground truth with the smallest key (ties: the lower ground-truth index), or
+ *              stays unmatched.  key = -iou with (t, +inf, +inf) is the usual IoU matching; key = degrees + 100 distance
+ *              with (-inf, d, s) the usual degree / cm matching; (0.1, 10, 0.05) says "10 degrees, 5 cm among boxes that
+ *              overlap" directly.
+ *   AP.        For one (class, criterion): all detections of the class over all frames by descending score (ties: the
+ *              lower input index), tp_k = detection k is matched, n_gt = the class's ground truths;
+ *                  precision_k = cumtp_k / (k + 1),  p^_k = max_{j >= k} precision_j,  AP = (sum_{k: tp_k} p^_k) / n_gt
+ *              -- the sum first, then one division: all matched gives exactly 1.0, none matched exactly 0.0.  n_gt == 0:
+ *              NaN; ground truths but no detections: 0.  mAP is the mean over the classes whose AP is not NaN.
+ * All three calls are fp64, enqueue kernels on the caller's stream, allocate nothing, never synchronise the host, and sum
+ * in one fixed order: two calls on the same inputs give the same bits.  Every argument error is SDFR_E_INVALID or (a
+ * required pointer) SDFR_E_NULL with a message, before anything touches the GPU; doubles and long longs need 8-byte, ints
+ * 4-byte alignment.  A count of 0 (N; G, T or P; T or C) does nothing. */
+
+/* ---- rotation and position error of N pose pairs.  A pose is 7 doubles: position (3), quaternion x, y, z, w
+ * (normalised inside).
+ *   distance [N]  |p_a - p_b|
+ *   degrees  [N]  2 atan2(|v|, |w|) of the relative unit quaternion (v, w) = q_a conj(q_b), in degrees: q and -q give the
+ *                 same value, equal poses exactly 0; with symmetry_axis[n] = a in {0, 1, 2} instead
+ *                 atan2(|a1 x a2|, a1 . a2) of the images a1 = R(q_a) e_a, a2 = R(q_b) e_a of that object axis (a turn
+ *                 about it cannot be observed: correct_thresh's rotational_symmetry_axis).  atan2, not acos, which loses
+ *                 half the digits near 0 and 180 degrees.
+ *   symmetry_axis [N] int, nullable (= none); any value but 0, 1, 2 means none
+ * A non-finite entry or a quaternion whose squared norm is 0 or not finite gives NaN in both outputs. */
+SDFR_API int sdfr_pose_pair_errors(const double* pose_a /* [N][7] */, const double* pose_b /* [N][7] */,
+                                   const int* symmetry_axis /* [N] nullable */, int N, double* degrees,
+                                   double* distance, int device, void* stream);
+
+/* ---- greedy matching of G groups under T criteria.
+ *   table       [n_pairs][4] the pair tables of all groups, one after the other
+ *   pred_offset [G + 1] int: the detections of group g are the columns pred_offset[g] .. pred_offset[g + 1] of `matched`,
+ *               ALREADY in processing order (descending score)
+ *   gt_offset   [G + 1] int: group g has ng = gt_offset[g + 1] - gt_offset[g] ground truths (only the differences are used)
+ *   pair_offset [G + 1] long long: pair (i, j) of group g is row pair_offset[g] + i * ng + j of the table
+ *   criteria    [T][3]  iou_min, degrees_max, distance_max
+ *   matched     [T][P] bytes, P = the number of detections: the LOCAL index 0 .. 63 of the ground truth a detection took
+ *               under criterion t, or SDFR_AP_UNMATCHED.  Columns no group covers are not written.
+ *   status      nullable int, OVERWRITTEN: bit 0 = some group was refused
+ * At most SDFR_AP_MAX_GT ground truths per group (the matched set is one 64-bit mask).  A group with more, or whose three
+ * offsets disagree (negative or decreasing, detections beyond P, pairs beyond n_pairs, a pair count that is not nd x ng),
+ * gets SDFR_AP_UNMATCHED in all its rows -- where its columns lie inside [0, P) -- and sets the status bit; the other
+ * groups are not affected, nothing outside [0, n_pairs) is read and nothing outside [0, T P) written.
+ * One thread per (group, criterion), a workgroup being one group and SDFR_AP_CRITERIA_BLOCK consecutive criteria; a
+ * group's result does not depend on the other groups or on T.  0 <= G <= 2^24, 0 <= T <= 2^20. */
+#define SDFR_AP_MAX_GT 64
+#define SDFR_AP_UNMATCHED 255
+#define SDFR_AP_CRITERIA_BLOCK 256
+SDFR_API int sdfr_ap_match(const double* table, long long n_pairs, const int* pred_offset, const int* gt_offset,
+                           const long long* pair_offset, int G, int P, const double* criteria, int T,
+                           unsigned char* matched, int* status /* nullable */, int device, void* stream);
+
+/* ---- the AP integral of T criteria x C classes.
+ *   matched      [T][P] as sdfr_ap_match wrote it
+ *   order        [P] int: the detections (columns of `matched`) class by class, each class's slice by descending score
+ *   class_offset [C + 1] int: class c's slice of `order`
+ *   n_gt         [C] int: the class's ground truths over all frames
+ *   ap           [T][C] doubles, overwritten, by the formula above; NaN for n_gt <= 0 or a class_offset outside [0, P]
+ * An entry of `order` outside [0, P) is not read and counts as unmatched.  One wave per (criterion, class): it counts the
+ * matches, then walks the slice from its end in chunks of 64 with the running maximum of the precision; a lane adds
+ * its terms in walk order and one xor butterfly adds the lanes.  0 <= T <= 2^20, T C <= 2^31 - 1. */
+SDFR_API int sdfr_ap_integrate(const unsigned char* matched, int T, int P, const int* order, const int* class_offset,
+                               const int* n_gt, int C, double* ap, int device, void* stream);
 
 #ifdef __cplusplus
 }

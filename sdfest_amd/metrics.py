@@ -18,9 +18,10 @@ import numpy as np
 import torch
 
 from . import _lib
+from .ap import mean_average_precision
 
 __all__ = ["mean_accuracy", "mean_completeness", "symmetric_chamfer", "accuracy_thresh", "completeness_thresh",
-           "reconstruction_fscore", "extent", "correct_thresh", "iou_3d", "reconstruction_metrics", "evaluate_metrics", "nearest_neighbors"]
+           "reconstruction_fscore", "extent", "correct_thresh", "iou_3d", "mean_average_precision", "reconstruction_metrics", "evaluate_metrics", "nearest_neighbors"]
 
 _MAX_T = _lib.ABI["SDFR_NN_MAX_THRESHOLDS"]
 _STATS = _lib.ABI["SDFR_NN_STATS"]   # sum, max, count, NaN count, _MAX_T counts, _MAX_T normalised counts
