@@ -172,6 +172,8 @@ SDFR_API const char* sdfr_last_error(void);
  *                    in polling rounds, for the forwards on THIS workspace (default 65536; 0: every view set-up takes
  *                    the fall-back path -- tests reach it this way).  Any other word 6 -- a zero-filled or an
  *                    uninitialised workspace -- means the default.  The library only reads them.
+ *   words 8, 9       the stamp of the grid whose face records the workspace holds (RESIDENT GRID, below)
+ *   word 11          SDFR_SYNC_GRID_MISMATCH_WORD: records that SDFR_GRID_RESIDENT_VERIFY found changed; only grows
  * No call writes into another call's part of a shared workspace's sync region. */
 #define SDFR_SYNC_POLLS_MAGIC 0x504F4C4Cu
 SDFR_API size_t sdfr_render_forward_workspace_bytes(int R, int B, int W, int H);
@@ -288,6 +290,44 @@ SDFR_API int sdfr_render_step_forward_resident(const float* sdf, int R, long lon
                                       long long g_sdf_view_stride, void* workspace, size_t workspace_bytes,
                                       unsigned long long* close_views_word, void* resident_state,
                                       size_t resident_state_bytes, int depth_resident, int device, void* stream);
+/* RESIDENT GRID: the two calls above for a caller that renders the SAME grid call after call while the poses move (a
+ * pose-only fitting loop, the orientation hypotheses of one object, one shape seen from many views).  The batch forms
+ * re-pack the grid into face records in the workspace and reduce its plane minima in every call; all of that depends
+ * on the grid alone.  A call that packs now leaves the minima and a stamp in the workspace's sync region beside the
+ * records, and
+ *   grid_resident   non-zero: the caller vouches that the last call on THIS workspace that packed a grid (any batch
+ *                   form over a shared grid: these two, sdfr_render_forward, the step and the depth-L1 forwards)
+ *                   packed the very bytes `sdf` points to now, at this address, with the same R and B, and that
+ *                   nothing has written the workspace's record region since, through any API (in the plain backward
+ *                   layout the tile partials lie where the records do; a step's backward leaves them alone).  The
+ *                   prologue launch then neither packs nor reduces nor waits: its view set-ups read the kept minima.
+ *                   0: no promise -- exactly the call above.
+ * The library cannot compare the bytes.  What it can check costs nothing and is checked on the device, by the launch
+ * itself: the stamp of a completed pack with this R, in the packed form this call takes (sync header words 8 / 9).
+ * Without it -- a workspace that never packed, another R -- the launch packs as if nobody had vouched: never an error.
+ * The poses are not part of the promise: every call sets its views up.  Results are bit for bit the plain call's.
+ * Forms without a packed grid ignore the flag (fewer than 17 views, one grid per view, R > 128); the depth-L1 forward
+ * and the one-launch fused step have no such argument.
+ * Do not vouch in a call that is captured into a graph: the replay would keep the promise over a changed grid.
+ *   SDFR_GRID_RESIDENT_VERIFY  (tests) vouch, and let the launch compare every record it did not re-pack with the
+ *                   grid, bit for bit: records that differ are counted into sync header word
+ *                   SDFR_SYNC_GRID_MISMATCH_WORD (it only ever grows, like word 1).  A separate instantiation: the
+ *                   plain and the vouched launch carry no instruction for it. */
+#define SDFR_GRID_RESIDENT 1
+#define SDFR_GRID_RESIDENT_VERIFY 2
+#define SDFR_SYNC_GRID_MISMATCH_WORD 11
+SDFR_API int sdfr_render_forward_grid_resident(const float* sdf, int R, long long sdf_view_stride, const float* pos,
+                                      const float* quat, const float* inv_scale, int B, int W, int H, float cx,
+                                      float cy, float fx, float fy, float threshold, float* depth, void* workspace,
+                                      size_t workspace_bytes, void* resident_state, size_t resident_state_bytes,
+                                      int depth_resident, int grid_resident, int device, void* stream);
+SDFR_API int sdfr_render_step_forward_grid_resident(const float* sdf, int R, long long sdf_view_stride,
+                                           const float* pos, const float* quat, const float* inv_scale, int B, int W,
+                                           int H, float cx, float cy, float fx, float fy, float threshold,
+                                           float* depth, float* g_sdf, long long g_sdf_view_stride, void* workspace,
+                                           size_t workspace_bytes, unsigned long long* close_views_word,
+                                           void* resident_state, size_t resident_state_bytes, int depth_resident,
+                                           int grid_resident, int device, void* stream);
 /* The same pair for the loss-fused forms (below): sdfr_render_step_forward_l1 = sdfr_render_forward_l1 that also
  * zero-fills g_sdf and leaves the view records; sdfr_render_step_backward_l1_pc = sdfr_render_backward_l1_pc without
  * its prologue launch.  For a few views of the plain grid the forward has no prologue launch either (every

@@ -179,6 +179,16 @@ constexpr int kPackedMaxR = 128;
 // cube because the plane minima did not arrive in time, render.hip) and 6 x kPackedMaxR tagged plane-minimum
 // entries of 16 bytes -- has ONE size and ONE place in the forward, backward, step and loss layouts, so no call
 // that shares a workspace with another ever writes over it.
+//   bytes [0, 128)       header: words 0 epoch, 1 fall-backs, 2 / 4 / 5 close views, 6 / 7 poll bound, 8 / 9 the grid
+//                        stamp {magic, R | form << 16}, SDFR_SYNC_GRID_MISMATCH_WORD the verification count
+//   [128, 128 + 12288)   the plane minima of the grid whose face records the workspace holds.  One-launch form: 6R
+//                        entries of two 64-bit words (x -> i, y -> R + i, z -> 2R + part * R + z: four partial minima
+//                        per z-plane, the reader takes their minimum).  The plane blocks of the launch that packs
+//                        publish them TAGGED {bits, tag}, {~bits, tag} for the set-up blocks of the same launch; the
+//                        image kernel behind it rewrites each as KEPT {bits, 0}, {bits, 0} -- equal words, which never
+//                        read as a tagged entry, and the value a later, RESIDENT call (render.hip) loads plainly.
+//                        Two-launch form: the 3R reduced minima as plain floats (axis * R + i), which nobody wipes.
+//                        The stamp's form says which of the two the bytes are.
 // Behind the sync region: the BAND SPANS, one word per view and band of 8 image rows = the columns [x0, x1) in which
 // the view's may-hit box can be seen in those rows (x0 | x1 << 16), from the outline of the projected box rather than
 // its bounding rectangle (a third of the rectangle's 8 x 8 patches lies outside the outline).  Written by the

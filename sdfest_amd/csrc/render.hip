@@ -345,14 +345,34 @@ __device__ __forceinline__ ResidentRow resident_row(unsigned* __restrict__ rstat
   return rr;
 }
 
+// The RESIDENT GRID (include/sdfr.h, sdfr_render_forward_grid_resident).  A call that packs a grid leaves, beside the
+// face records, the grid's plane minima in the sync region (common.hpp: kept by the image kernel, not wiped) and a stamp in
+// sync header words 8 / 9 = {kGridStampMagic, R | form << 16}.  The stamp is written by the launch AFTER the one that
+// packed (the image kernel; view_setup_kernel in the two-launch form), never by the packing launch itself: a block
+// of a launch that reads the stamp must not see another block of the same launch change it.  A later call whose
+// caller vouches for the bytes finds the stamp of its own R and form and neither packs nor reduces; any other stamp
+// -- a workspace that never packed, another R, the other form -- and it packs as if nobody had vouched.
+constexpr unsigned kGridStampMagic = 0x47524944u;   // "GRID"
+constexpr unsigned kGridFormOneLaunch = 1u, kGridFormTwoLaunch = 2u;
+constexpr int kSyncGridStampWord = 8, kSyncGridMismatchWord = SDFR_SYNC_GRID_MISMATCH_WORD;
+__device__ __forceinline__ bool grid_stamp_holds(const unsigned* __restrict__ sync, int R, unsigned form) {
+  return sync[kSyncGridStampWord] == kGridStampMagic && sync[kSyncGridStampWord + 1] == ((unsigned)R | form << 16);
+}
+__device__ __forceinline__ void stamp_grid(unsigned* __restrict__ sync, int R, unsigned form) {
+  sync[kSyncGridStampWord] = kGridStampMagic;
+  sync[kSyncGridStampWord + 1] = (unsigned)R | form << 16;
+}
+
 __global__ void view_setup_kernel(const float* __restrict__ pos, const float* __restrict__ quat,
                                   const float* __restrict__ inv_scale, int B, int R, int W, int H,
                                   float cx, float cy, float fx, float fy,
                                   ViewSetup* __restrict__ out, const float* __restrict__ plane_min,
                                   float threshold, unsigned* __restrict__ spans, unsigned* __restrict__ rstate,
-                                  int depth_resident) {
+                                  int depth_resident, unsigned* __restrict__ stamp_sync) {
   // one wave per view (the wave shares the scan of the plane minima, lane 0 writes the record)
   const int b = blockIdx.x;
+  // (stamp_sync, nullable: this launch follows pack_cells_kernel -- the grid stamp of the two-launch form, below)
+  if (stamp_sync && b == 0 && threadIdx.x == 0) stamp_grid(stamp_sync, R, kGridFormTwoLaunch);
   if (b < B)
     compute_view_setup<true>(b, pos, quat, inv_scale, R, W, H, cx, cy, fx, fy, out, plane_min, threshold, spans,
                              resident_row(rstate, depth_resident, b, B, W, H));
@@ -501,20 +521,44 @@ __device__ __forceinline__ void plane_min_fast_block(const float* __restrict__ s
 // gathers its corners from 16 x-planes of the grid, which the plane-minimum blocks have just pulled through L2.
 // (Thread = voxel, the grid read in order, would scatter a wave's records over 32 lines 4 KiB apart.)
 // The launches bring R^3 threads: at least as many as there are records (device.hpp).
-__device__ __forceinline__ void pack_cell(const float* __restrict__ sdf, int R, float4* __restrict__ cells, int rix) {
+// (record_corner: corner 00 of record `rix` in the grid, or nullptr for an index that holds no record)
+__device__ __forceinline__ const float* record_corner(const float* __restrict__ sdf, int R, int rix) {
   const int Hyz = R >> 1, X2 = ((R + 1) >> 1) * 2;
   const int q = rix >> 2, x = q % X2, b = q / X2;
   const int y = (b / Hyz) * 2 + ((rix >> 1) & 1), z = (b % Hyz) * 2 + (rix & 1);
-  if (x >= R || y >= R - 1 || z >= R - 1) return;
-  const float* p = sdf + ((size_t)x * R + y) * R + z;
+  if (x >= R || y >= R - 1 || z >= R - 1) return nullptr;
+  return sdf + ((size_t)x * R + y) * R + z;
+}
+__device__ __forceinline__ void pack_cell(const float* __restrict__ sdf, int R, float4* __restrict__ cells, int rix) {
+  const float* p = record_corner(sdf, R, rix);
+  if (!p) return;
   cells[rix] = make_float4(p[0], p[1], p[R], p[R + 1]);
 }
+// The verification switch of the resident grid (SDFR_GRID_RESIDENT_VERIFY): is record `rix` still, bit for bit, what
+// pack_cell would write?  A record that is not counts one into the sync header (kSyncGridMismatchWord).
+__device__ __forceinline__ void verify_cell(const float* __restrict__ sdf, int R, const float4* __restrict__ cells,
+                                            int rix, unsigned* __restrict__ sync) {
+  const float* p = record_corner(sdf, R, rix);
+  if (!p) return;
+  const float4 c = cells[rix];
+  const bool same = __float_as_uint(c.x) == __float_as_uint(p[0]) && __float_as_uint(c.y) == __float_as_uint(p[1]) &&
+                    __float_as_uint(c.z) == __float_as_uint(p[R]) && __float_as_uint(c.w) == __float_as_uint(p[R + 1]);
+  if (!same) atomicAdd(&sync[kSyncGridMismatchWord], 1u);
+}
 
+// GRID (the resident grid, above): 0 = pack; 1 = the caller vouches -- a launch that finds the two-launch form's stamp
+// of this R leaves records and kept minima as they are; 2 = 1, and every record is compared with the grid (verify_cell).
+template <int GRID>
 __global__ __launch_bounds__(256) void pack_cells_kernel(const float* __restrict__ sdf, int R,
                                                          float4* __restrict__ cells, int n_pack_blocks,
-                                                         float* __restrict__ plane_min) {
+                                                         float* __restrict__ plane_min, unsigned* __restrict__ sync) {
   // the plane-minimum blocks come FIRST: they take longest (16 strided loads per thread, a reduction)
   const int n_plane = (int)gridDim.x - n_pack_blocks;
+  if (GRID != 0 && grid_stamp_holds(sync, R, kGridFormTwoLaunch)) {   // (uniform over the launch)
+    if (GRID == 2 && (int)blockIdx.x >= n_plane)
+      verify_cell(sdf, R, cells, ((int)blockIdx.x - n_plane) * (int)blockDim.x + (int)threadIdx.x, sync);
+    return;
+  }
   if ((int)blockIdx.x < n_plane) {
     plane_min_block(sdf, R, (int)blockIdx.x, plane_min);
     return;
@@ -539,6 +583,13 @@ constexpr int kPrologueMaxPolls = 1 << 16;
 // {SDFR_SYNC_POLLS_MAGIC, rounds} override the default for the forwards on that workspace (0 rounds: every view set-up
 // takes the fall-back path -- how the tests reach it); any other word 6, e.g. of a workspace nobody initialised, means
 // the default.  Nothing process-wide.
+// GRID (the resident grid, above view_setup_kernel): 0 = pack, the launch described so far.  1 = the caller vouches for
+// the workspace's records: a launch that finds the one-launch form's stamp of this R has nothing to wait for -- its
+// plane blocks leave at once, its set-up blocks read the KEPT minima with plain loads (no tag, no poll), and the rest
+// only zero-fills; without the stamp it is the packing launch, block for block.  2 = 1, and the zero-fill blocks
+// compare every record with the grid (verify_cell).  The grid is the same in all three, so that the choice can be
+// made where the stamp lives: on the device.
+template <int GRID>
 __global__ __launch_bounds__(256) void forward_prologue_kernel(
     const float* __restrict__ sdf, int R, float4* __restrict__ cells, int n_plane, int n_setup,
     unsigned* __restrict__ sync, const float* __restrict__ pos, const float* __restrict__ quat,
@@ -547,9 +598,10 @@ __global__ __launch_bounds__(256) void forward_prologue_kernel(
     unsigned* __restrict__ spans, unsigned* __restrict__ rstate, int depth_resident) {
   const unsigned tag = sync[0] + 1u;  // the epoch the last forward on this workspace left, + 1
   PlaneEntry* ent = reinterpret_cast<PlaneEntry*>(sync + kSyncHeaderWords);
+  const bool resident = GRID != 0 && grid_stamp_holds(sync, R, kGridFormOneLaunch);   // (uniform over the launch)
   int blk = (int)blockIdx.x;
   if (blk < n_plane) {
-    plane_min_fast_block(sdf, R, blk, ent, tag);
+    if (!resident) plane_min_fast_block(sdf, R, blk, ent, tag);
     return;
   }
   blk -= n_plane;
@@ -566,7 +618,14 @@ __global__ __launch_bounds__(256) void forward_prologue_kernel(
     }
     bool ready = false;
     const int max_polls = sync[6] == SDFR_SYNC_POLLS_MAGIC ? (int)sync[7] : default_polls;   // (workgroup-uniform)
-    for (int poll = 0; poll < max_polls; ++poll) {
+    if (resident && max_polls > 0) {
+      // what the plane blocks of the packing call published, as the image kernel behind it KEPT the entries (its
+      // epoch block): the value in both words, no tag -- plain loads.  (A workspace whose bound is 0 rounds asks for
+      // the fall-back path in every set-up, include/sdfr.h: this form obeys it too.)
+      for (int j = tid; j < n_ent; j += 256) pm_s[j] = __uint_as_float((unsigned)ent[j].a);
+      __syncthreads();
+      ready = true;
+    } else for (int poll = 0; poll < max_polls; ++poll) {
       bool ok = true;
       for (int j = tid; j < n_ent; j += 256) {
         const unsigned long long a = __hip_atomic_load(&ent[j].a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -597,6 +656,10 @@ __global__ __launch_bounds__(256) void forward_prologue_kernel(
   const int lin = blk * 256 + (int)threadIdx.x;
   const size_t vox = (size_t)R * R * R;
   for (size_t i = (size_t)lin; i < n_zero; i += vox) g_zero[i] = 0.0f;   // (lin < vox or the block has no thread)
+  if (resident) {
+    if (GRID == 2) verify_cell(sdf, R, cells, lin, sync);
+    return;
+  }
   pack_cell(sdf, R, cells, lin);
 }
 
@@ -868,10 +931,21 @@ __global__ __launch_bounds__(NW * 64) void render_forward_kernel(
   // the entries that launch published are wiped (equal words never read as an entry: the payloads of a valid one
   // are complementary).  Either alone keeps an entry of this call from reading as ready in a later one; the wipe
   // also covers a caller whose other work overwrote the epoch word with the value it had before.
+  // The launch before this one packed `src` from the grid, or found the stamp that says so: the stamp for the next
+  // call whose caller vouches for the grid (stamp_grid: written here, not by the launch that reads it).
   if (epoch && (blockIdx.x | blockIdx.y | blockIdx.z) == 0) {
-    if (threadIdx.x == 0) epoch[0] += 1u;
+    if (threadIdx.x == 0) {
+      epoch[0] += 1u;
+      stamp_grid(epoch, R, kGridFormOneLaunch);
+    }
     unsigned long long* ent = reinterpret_cast<unsigned long long*>(epoch + kSyncHeaderWords);
-    for (int j = threadIdx.x; j < 2 * 6 * kPackedMaxR; j += NW * 64) ent[j] = 0ull;
+    // (KEPT, not zeroed: {bits, 0} in both words -- equal words, so all of the above holds, and the minimum stays for a
+    // later call on the same grid, the resident grid above view_setup_kernel; an entry kept before stays as it is)
+    for (int j = threadIdx.x; j < 6 * kPackedMaxR; j += NW * 64) {
+      const unsigned long long v = ent[2 * j] & 0xffffffffull;
+      ent[2 * j] = v;
+      ent[2 * j + 1] = v;
+    }
   }
 }
 
@@ -1746,8 +1820,10 @@ int forward_impl(const char* fn, const float* sdf, int R, long long sdf_view_str
                  float fx, float fy, float threshold, float* depth, const float* target, float* loss,
                  float* loss_stats, void* workspace, size_t workspace_bytes, size_t need, const ForwardLayout& lay,
                  float* g_zero, size_t n_zero, int device, void* stream, unsigned long long* close_word = nullptr,
-                 void* resident_state = nullptr, size_t resident_state_bytes = 0, int depth_resident = 0) {
+                 void* resident_state = nullptr, size_t resident_state_bytes = 0, int depth_resident = 0,
+                 int grid_resident = 0) {
   // resident_state (nullable; sdfr_render_forward_resident): the caller's state of THIS depth buffer (common.hpp)
+  // grid_resident (sdfr_render_forward_grid_resident): 0, SDFR_GRID_RESIDENT or SDFR_GRID_RESIDENT_VERIFY
   const bool with_loss = target != nullptr;
   if (int rc = check_common(R, B, W, H, fx, fy)) return rc;
   if (sdf_view_stride != 0 && sdf_view_stride < (long long)R * R * R)
@@ -1786,13 +1862,17 @@ int forward_impl(const char* fn, const float* sdf, int R, long long sdf_view_str
   unsigned* rstate = (rseq && packed && !with_loss && W <= 65535) ? rseq : nullptr;
   const unsigned* rrows = rstate ? rstate + kResidentHeaderWords : nullptr;
   unsigned* epoch = nullptr;
+  // the resident grid: only the forms that pack can skip the pack (the depth-L1 forward always packs)
+  const int grid = (!packed || with_loss || !grid_resident) ? 0 : (grid_resident == SDFR_GRID_RESIDENT_VERIFY ? 2 : 1);
   // (the one-launch prologue reads the grid with 16-byte loads: other grids take the two-launch form)
   if (packed && (R & 3) == 0 && ((uintptr_t)sdf & 15) == 0) {
     const int n_pack = (R * R * R + 255) / 256, n_setup = (B + 3) / 4;
-    hipLaunchKernelGGL(forward_prologue_kernel, dim3(3 * R + n_setup + n_pack), dim3(256), 0, st, sdf, R,
-                       (float4*)cells, 3 * R, n_setup, lay.sync, pos, quat, inv_scale, B, W, H, cx, cy, fx, fy,
-                       setup, threshold, g_zero, n_zero, kPrologueMaxPolls,
-                       lay.spans, rstate, depth_resident);
+#define SDFR_LAUNCH_PROLOGUE(GRID)                                                                                \
+  hipLaunchKernelGGL(forward_prologue_kernel<GRID>, dim3(3 * R + n_setup + n_pack), dim3(256), 0, st, sdf, R,     \
+                     (float4*)cells, 3 * R, n_setup, lay.sync, pos, quat, inv_scale, B, W, H, cx, cy, fx, fy,    \
+                     setup, threshold, g_zero, n_zero, kPrologueMaxPolls, lay.spans, rstate, depth_resident)
+    if (grid == 0) SDFR_LAUNCH_PROLOGUE(0); else if (grid == 1) SDFR_LAUNCH_PROLOGUE(1); else SDFR_LAUNCH_PROLOGUE(2);
+#undef SDFR_LAUNCH_PROLOGUE
     epoch = lay.sync;
   } else if (g_zero && !packed && inline_setup) {
     // a step over a few views of the plain grid: no prologue launch at all (render_forward_kernel, INLINE)
@@ -1807,13 +1887,16 @@ int forward_impl(const char* fn, const float* sdf, int R, long long sdf_view_str
     float* plane_min = nullptr;
     if (packed) {
       const int n_pack = (R * R * R + 255) / 256;
-      plane_min = (float*)(lay.sync + kSyncHeaderWords);
-      hipLaunchKernelGGL(pack_cells_kernel, dim3(n_pack + 3 * R), dim3(256), 0, st, sdf, R,
-                         (float4*)cells, n_pack, plane_min);
+      plane_min = (float*)(lay.sync + kSyncHeaderWords);   // (3R floats: the next launch's, or a later, resident call's)
+#define SDFR_LAUNCH_PACK(GRID)                                                                          \
+  hipLaunchKernelGGL(pack_cells_kernel<GRID>, dim3(n_pack + 3 * R), dim3(256), 0, st, sdf, R, (float4*)cells, n_pack, \
+                     plane_min, lay.sync)
+      if (grid == 0) SDFR_LAUNCH_PACK(0); else if (grid == 1) SDFR_LAUNCH_PACK(1); else SDFR_LAUNCH_PACK(2);
+#undef SDFR_LAUNCH_PACK
     }
     hipLaunchKernelGGL(view_setup_kernel, dim3(B), dim3(64), 0, st, pos, quat, inv_scale, B, R,
                        W, H, cx, cy, fx, fy, setup, plane_min, threshold, lay.spans, packed ? rstate : nullptr,
-                       depth_resident);
+                       depth_resident, packed ? lay.sync : nullptr);
   }
   const bool macro = geom.sx * geom.sy > 1;
   const int ntx = geom.nx(W), nty = geom.ny(H);
@@ -1890,10 +1973,22 @@ extern "C" int sdfr_render_forward_resident(const float* sdf, int R, long long s
                                             void* workspace, size_t workspace_bytes, void* resident_state,
                                             size_t resident_state_bytes, int depth_resident, int device,
                                             void* stream) {
+  return sdfr_render_forward_grid_resident(sdf, R, sdf_view_stride, pos, quat, inv_scale, B, W, H, cx, cy, fx, fy,
+                                           threshold, depth, workspace, workspace_bytes, resident_state,
+                                           resident_state_bytes, depth_resident, 0, device, stream);
+}
+
+extern "C" int sdfr_render_forward_grid_resident(const float* sdf, int R, long long sdf_view_stride, const float* pos,
+                                                 const float* quat, const float* inv_scale, int B, int W, int H,
+                                                 float cx, float cy, float fx, float fy, float threshold, float* depth,
+                                                 void* workspace, size_t workspace_bytes, void* resident_state,
+                                                 size_t resident_state_bytes, int depth_resident, int grid_resident,
+                                                 int device, void* stream) {
   return forward_impl("sdfr_render_forward_resident", sdf, R, sdf_view_stride, pos, quat, inv_scale, B, W, H, cx, cy,
                       fx, fy, threshold, depth, nullptr, nullptr, nullptr, workspace, workspace_bytes,
                       sdfr_render_forward_workspace_bytes(R, B, W, H), plain_forward_layout(workspace, R, B, W, H),
-                      nullptr, 0, device, stream, nullptr, resident_state, resident_state_bytes, depth_resident);
+                      nullptr, 0, device, stream, nullptr, resident_state, resident_state_bytes, depth_resident,
+                      grid_resident);
 }
 
 extern "C" int sdfr_render_forward_l1(const float* sdf, int R, long long sdf_view_stride,
@@ -2106,6 +2201,18 @@ extern "C" int sdfr_render_step_forward_resident(const float* sdf, int R, long l
                                                  size_t workspace_bytes, unsigned long long* close_views_word,
                                                  void* resident_state, size_t resident_state_bytes,
                                                  int depth_resident, int device, void* stream) {
+  return sdfr_render_step_forward_grid_resident(sdf, R, sdf_view_stride, pos, quat, inv_scale, B, W, H, cx, cy, fx, fy,
+                                                threshold, depth, g_sdf, g_sdf_view_stride, workspace, workspace_bytes,
+                                                close_views_word, resident_state, resident_state_bytes, depth_resident,
+                                                0, device, stream);
+}
+
+extern "C" int sdfr_render_step_forward_grid_resident(
+    const float* sdf, int R, long long sdf_view_stride, const float* pos, const float* quat, const float* inv_scale,
+    int B, int W, int H, float cx, float cy, float fx, float fy, float threshold, float* depth, float* g_sdf,
+    long long g_sdf_view_stride, void* workspace, size_t workspace_bytes, unsigned long long* close_views_word,
+    void* resident_state, size_t resident_state_bytes, int depth_resident, int grid_resident, int device,
+    void* stream) {
   const char* fn = "sdfr_render_step_forward";
   if ((uintptr_t)close_views_word % 8) return fail(SDFR_E_INVALID, "%s: close_views_word must be 8-byte aligned", fn);
   const long long vox = (long long)R * R * R;
@@ -2125,7 +2232,7 @@ extern "C" int sdfr_render_step_forward_resident(const float* sdf, int R, long l
   return forward_impl(fn, sdf, R, sdf_view_stride, pos, quat, inv_scale, B, W, H, cx, cy, fx, fy, threshold, depth,
                       nullptr, nullptr, nullptr, workspace, workspace_bytes,
                       sdfr_render_step_workspace_bytes(R, B, W, H), lay, g_sdf, g_words, device, stream,
-                      close_views_word, resident_state, resident_state_bytes, depth_resident);
+                      close_views_word, resident_state, resident_state_bytes, depth_resident, grid_resident);
 }
 
 extern "C" int sdfr_render_step_forward_l1(const float* sdf, int R, long long sdf_view_stride, const float* pos,

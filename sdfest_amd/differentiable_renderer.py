@@ -8,6 +8,7 @@ the C ABI of ``include/sdfr.h``.
 """
 import math
 import threading
+import weakref
 from typing import Optional, Tuple
 
 import torch
@@ -469,11 +470,22 @@ class BatchRenderPlan:
     the version counter; a write through a raw pointer is not (``tensor.data``, a kernel of the caller's, the replay of
     a graph that writes it): **treat the depth buffer as read-only for such writers**.  The images are bit for bit
     what they are without the state.
+
+    **Resident grid.**  The batch forms march the grid through face records that ``forward`` packs into the workspace,
+    and set their views up from the grid's plane minima; both depend on the grid alone, and many loops render one
+    unchanged grid while the poses move.  With ``grid_resident="auto"`` the plan remembers, after a ``forward`` that
+    packed, the tensor and ``(sdf.data_ptr(), sdf._version, R, workspace._version)`` and tells the next ``forward`` that the records
+    are still good (``sdfr_render_forward_grid_resident``, include/sdfr.h) when all four still match and nothing of the
+    plan that writes the record region ran in between (a stand-alone ``backward``, the depth-L1 and fused forms; a
+    step's own backward and ``ring_reset`` do not).  Never while the stream is capturing: the replay would keep the
+    promise over a changed grid.  Poses are never part of it: every call sets its views up.  As with the depth buffer,
+    a write to the grid through a raw pointer (a ctypes kernel, ``tensor.data``) does not move ``_version``: call
+    ``invalidate_grid()`` after one.  Results are bit for bit what they are without it.
     """
 
     def __init__(self, R: int, B: int, camera: Camera, device="cuda", per_view_sdf: bool = False,
                  sdf_grad_mode: int = SDF_GRAD_EXACT, grad_volumes: int = 2, close_views="auto",
-                 grad_tail_words: int = 0):
+                 grad_tail_words: int = 0, grid_resident="auto"):
         """close_views: the ``SDFR_BWD_HALF_GRID`` hint of a step's backward -- half the workgroups when (nearly) all
         views are close (``views_are_close``); same results either way, views that are not close are slower with it.
         True / False: the caller knows.  "auto" (default): nobody looks at the poses on the host -- the step's
@@ -485,6 +497,8 @@ class BatchRenderPlan:
         sharded batch carries d/dSDF and whatever small per-view results ride along."""
         if grad_volumes < 2:
             raise ValueError("grad_volumes must be >= 2")
+        if grid_resident not in ("auto", False):
+            raise ValueError("grid_resident must be 'auto' or False")
         if grad_tail_words < 0 or (grad_tail_words and per_view_sdf):
             raise ValueError("grad_tail_words needs the shared gradient volume")
         self.device = torch.device(device)
@@ -533,6 +547,13 @@ class BatchRenderPlan:
         self._resident_state = torch.zeros(L.sdfr_render_resident_state_bytes(B, self.H), dtype=torch.uint8,
                                            device=self.device)
         self._resident = None
+        # resident grid (class docstring): (sdf.data_ptr(), sdf._version, R, workspace._version) after the last forward
+        # that packed -- None whenever the next forward must pack; `grid_flag`: what the last forward handed down.
+        # It is kept ON the workspace tensor (the `_grid` property): the records are the workspace's, and two plans
+        # that were given one workspace tensor then see each other's packs.
+        self._grid_auto = grid_resident == "auto"
+        self.grid_verify = False     # tests: vouch with SDFR_GRID_RESIDENT_VERIFY (grid_mismatches())
+        self.grid_flag = 0
         self._fixed_layout = None   # deterministic mode: which workspace layout holds the last int64 volume
         self._step_l1 = None        # the volume a forward_l1(prepare_backward=True) zero-filled
         self.partials_offset = 0    # where the last backward_l1_pc left its tile partials (sdfr_loop_tail)
@@ -582,6 +603,43 @@ class BatchRenderPlan:
         self._step = None
         self._step_l1 = None
         self._resident = None
+        # (self._grid stays: nothing here touches the workspace, and the records do not depend on the ring)
+
+    @property
+    def _grid(self):
+        return getattr(self.workspace, "_sdfr_grid", None)
+
+    @_grid.setter
+    def _grid(self, value) -> None:
+        self.workspace._sdfr_grid = value
+
+    def invalidate_grid(self) -> None:
+        """The next ``forward`` packs the grid again, whatever the tensor's address and version say.  For callers that
+        write the grid behind torch's back: a kernel called through ctypes, ``tensor.data``, a graph replay -- none of
+        these bumps ``_version``, and the plan would go on marching the records of the old bytes."""
+        self._grid = None
+
+    def grid_mismatches(self) -> int:
+        """Records that a vouched forward with ``grid_verify`` found different from the grid (sync header word
+        ``SDFR_SYNC_GRID_MISMATCH_WORD``; synchronises).  Only ever grows."""
+        o = self._sync_offset + 4 * _lib.ABI["SDFR_SYNC_GRID_MISMATCH_WORD"]
+        return int(self.workspace[o:o + 4].view(torch.int32).item())
+
+    def _grid_vouch(self, sdf) -> int:
+        """The ``grid_resident`` flag of the forward that is about to run on `sdf`, and the state after it."""
+        seen = self._grid
+        now = (sdf.data_ptr(), sdf._version, self.R, self.workspace._version)
+        # (and the tensor OBJECT, weakly: a grid that was freed and another allocated in its place has the same
+        # address and, fresh from an out-of-place op, the same version)
+        same_tensor = seen is not None and seen[0]() is sdf
+        # (a capturing stream: the flag would be baked into the graph -- and what a replay leaves is not what the
+        # plan saw, so nothing is remembered either)
+        capturing = torch.cuda.is_current_stream_capturing()
+        self._grid = (weakref.ref(sdf),) + now if (self._grid_auto and not capturing and not self.sdf_stride) else None
+        self.grid_flag = 0
+        if same_tensor and seen[1:] == now and self._grid is not None:
+            self.grid_flag = _lib.ABI["SDFR_GRID_RESIDENT_VERIFY" if self.grid_verify else "SDFR_GRID_RESIDENT"]
+        return self.grid_flag
 
     def close_views_seen(self):
         """(forwards counted so far, close views of the latest counted one) as the pinned word holds them right now
@@ -646,24 +704,25 @@ class BatchRenderPlan:
         resident = int(seen is not None and seen[0] is dst
                        and seen[1:] == (dst.data_ptr(), dst._version, self.workspace._version))
         state = self._resident_state
+        grid = self._grid_vouch(sdf)
         if prepare_backward:
             nxt = self._g_sdf_ring[self._g_sdf_next]
-            rc = self._L.sdfr_render_step_forward_resident(
+            rc = self._L.sdfr_render_step_forward_grid_resident(
                 sdf.data_ptr(), self.R, self.sdf_stride, pos.data_ptr(), quat.data_ptr(),
                 inv_scale.data_ptr(), self.B, self.W, self.H, self.cx, self.cy, self.fx, self.fy,
                 threshold, dst.data_ptr(), nxt.data_ptr(), self.sdf_stride, self.workspace.data_ptr(),
                 self.workspace.numel(), self._close_word.data_ptr() if self._close_auto else None,
-                state.data_ptr(), state.numel(), resident, self.device.index, _stream(self.device))
+                state.data_ptr(), state.numel(), resident, grid, self.device.index, _stream(self.device))
             _lib.check(rc, "sdfr_render_step_forward")
             self._step = (self._key(sdf, pos, quat, inv_scale), dst, nxt)
             self._resident = (dst, dst.data_ptr(), dst._version, self.workspace._version)
             return dst
         self._step = None
-        rc = self._L.sdfr_render_forward_resident(
+        rc = self._L.sdfr_render_forward_grid_resident(
             sdf.data_ptr(), self.R, self.sdf_stride, pos.data_ptr(), quat.data_ptr(),
             inv_scale.data_ptr(), self.B, self.W, self.H, self.cx, self.cy, self.fx, self.fy,
             threshold, dst.data_ptr(), self.workspace.data_ptr(), self.workspace.numel(),
-            state.data_ptr(), state.numel(), resident, self.device.index, _stream(self.device))
+            state.data_ptr(), state.numel(), resident, grid, self.device.index, _stream(self.device))
         _lib.check(rc, "sdfr_render_forward")
         self._resident = (dst, dst.data_ptr(), dst._version, self.workspace._version)
         return dst
@@ -702,6 +761,7 @@ class BatchRenderPlan:
             self._fixed_layout = 1
             return self.g_sdf, self.g_pos, self.g_quat, self.g_inv_scale
         self._resident = None   # (a stand-alone backward: not the step's own)
+        self._grid = None       # (its tile partials lie where the forward layout keeps the face records)
         depth = self.depth
         if step is not None:
             # a prepared step whose backward cannot run as such (other tensors, or deferred pose sums): the
@@ -746,6 +806,7 @@ class BatchRenderPlan:
         step's backward follows, on the same tensors."""
         self._step = None   # the workspace is about to be re-used
         self._resident = None
+        self._grid = None   # (it packs ITS grid into the same records, and stamps them: the next forward packs)
         self._check(sdf, pos, quat, inv_scale, target=target)
         if defer_loss and not prepare_backward:
             raise ValueError("defer_loss goes with prepare_backward")
@@ -777,6 +838,7 @@ class BatchRenderPlan:
         ``backward``."""
         self._step = None   # the workspace is about to be re-used
         self._resident = None
+        self._grid = None   # (stand-alone: tile partials over the records)
         prepared, self._step_l1 = self._step_l1, None
         self._check(sdf, pos, quat, inv_scale, target=target)
         if loss_grad is not None:
@@ -838,6 +900,7 @@ class BatchRenderPlan:
         self._step = None
         self._step_l1 = None
         self._resident = None
+        self._grid = None   # (the views' counts live in the face records' place)
         self._check(sdf, pos, quat, inv_scale, target=target)
         rc = self._L.sdfr_render_step_fused_l1_pc(
             sdf.data_ptr(), self.R, self.sdf_stride, pos.data_ptr(), quat.data_ptr(), inv_scale.data_ptr(),
@@ -871,6 +934,7 @@ class BatchRenderPlan:
         ``self.workspace`` and ``pc_workspace`` for ``sdfr_views_to_pose_grad_deferred``."""
         self._step = None   # the workspace is about to be re-used
         self._resident = None
+        self._grid = None   # (stand-alone: tile partials over the records)
         self._check(sdf, pos, quat, inv_scale, target=target)
         dev = self.device
         if not (scale.device == dev and scale.dtype is torch.float32 and scale.shape == self._shape_isc
