@@ -57,6 +57,7 @@
  *        sdfr_render_step_backward_l1, sdfr_render_backward_l1_pc, sdfr_render_step_backward_l1_pc,
  *        sdfr_render_step_fused_l1_pc, sdfr_render_fused_view_count_offset, sdfr_render_fused_tile_loss_offset
  *        sdfr_pc_l1_backward[_accumulate]
+ *        sdfr_decoder_launch_plan
  *   3. [unstable] LOOP: one render-and-compare iteration (SDFPipeline.__call__) as a fixed launch sequence
  *        sdfr_preprocess_depth, sdfr_depth_to_points_resident, sdfr_depth_count[_ordered|_centroid],
  *        sdfr_depth_to_points[_ordered|_shifted], sdfr_depth_points_workspace_bytes, sdfr_depth_centroid_workspace_bytes
@@ -536,6 +537,63 @@ SDFR_API int sdfr_decoder_set_option(sdfr_decoder* decoder, int option, int valu
  * 0 if not, SDFR_E_NULL without a handle.  The one statement of that criterion: what sdfr_loop_tail_fused(decoder_tape)
  * requires, so a caller asks here instead of repeating the arithmetic.  Changes nothing. */
 SDFR_API int sdfr_decoder_fc_one_wave(const sdfr_decoder* decoder);
+/* [unstable, group 2] Read only: the launches a pass over N latents would make on this handle, in order, one
+ * SDFR_DECODER_STEP_* code per launch -- the answer of the planner the calls themselves launch from, for caller
+ * buffers that are 256-byte aligned (a pointer that is not 16-byte aligned can cost a call its 16-byte load forms).
+ * Launches nothing and takes no stream.  pass: SDFR_DECODER_PASS_FORWARD with flags PLAN_TAPE (a taped forward),
+ * PLAN_CLAMP (enforce_tsdf), PLAN_STAGE_1 or PLAN_STAGE_2 (sdfr_decoder_forward_stage's stages 1 / 2; neither: both);
+ * SDFR_DECODER_PASS_VJP with flags PLAN_DEFERRED (the _deferred forms: the last launch is the caller's), PLAN_SCALED_1
+ * or PLAN_SCALED_N (the _deferred_scaled form with one / several views, N = 1).  Returns the number of steps and writes
+ * the first `capacity` of them to steps; 0 for N = 0; SDFR_E_NULL without a handle, SDFR_E_INVALID for an unknown pass
+ * or flags that are not that pass's. */
+#define SDFR_DECODER_PASS_FORWARD 0
+#define SDFR_DECODER_PASS_VJP 1
+#define SDFR_DECODER_PLAN_TAPE 1
+#define SDFR_DECODER_PLAN_CLAMP 2
+#define SDFR_DECODER_PLAN_STAGE_1 4
+#define SDFR_DECODER_PLAN_STAGE_2 8
+#define SDFR_DECODER_PLAN_DEFERRED 16
+#define SDFR_DECODER_PLAN_SCALED_1 32
+#define SDFR_DECODER_PLAN_SCALED_N 64
+/* forward: the Linear stack (NARROW: its one-wave form), alone or with the first convolution (FC_CONV) */
+#define SDFR_DECODER_STEP_FC_STACK 1
+#define SDFR_DECODER_STEP_FC_STACK_NARROW 2
+#define SDFR_DECODER_STEP_FC_STACK_BATCH 3
+#define SDFR_DECODER_STEP_FC_STACK_BATCH_NARROW 4
+#define SDFR_DECODER_STEP_FC_CONV 5
+/* a trilinear resize: gathered, tiled (batches), with a swapped 1x1x1 layer's channel mix */
+#define SDFR_DECODER_STEP_RESIZE 6
+#define SDFR_DECODER_STEP_RESIZE_TILED 7
+#define SDFR_DECODER_STEP_RESIZE_MIX 8
+/* a convolution (VJP: the transposed one): 1x1x1, direct (batches; UP: with the resize in front of it), on the matrix
+ * cores (plain, split-K, z-grouped, input resident in LDS; UP: few latents, with the resize in front of it) */
+#define SDFR_DECODER_STEP_CONV1X1 9
+#define SDFR_DECODER_STEP_CONV1X1_VEC4 10
+#define SDFR_DECODER_STEP_DIRECT 11
+#define SDFR_DECODER_STEP_DIRECT_UP 12
+#define SDFR_DECODER_STEP_MFMA 13
+#define SDFR_DECODER_STEP_MFMA_SPLIT_K 14
+#define SDFR_DECODER_STEP_MFMA_Z_GROUPED 15
+#define SDFR_DECODER_STEP_MFMA_RESIDENT 16
+#define SDFR_DECODER_STEP_MFMA_UP 17
+#define SDFR_DECODER_STEP_COPY 18
+#define SDFR_DECODER_STEP_CLAMP 19
+/* VJP: the scaled form's sum, mask + padding, a transposed resize (tiled: one launch; else z + y, single axes, the x
+ * pass with mask + padding, with the swapped 1x1x1 layer too), a fused stage (transposed resize + convolution), the
+ * transposed Linear layers (the wide one; the leading ones, WAVE: their one-wave form) */
+#define SDFR_DECODER_STEP_SCALED_COMBINE 20
+#define SDFR_DECODER_STEP_PAD_MASK 21
+#define SDFR_DECODER_STEP_RESIZE_T_TILED 22
+#define SDFR_DECODER_STEP_RESIZE_T_ZY 23
+#define SDFR_DECODER_STEP_RESIZE_T_AXIS 24
+#define SDFR_DECODER_STEP_RESIZE_T_X_PAD 25
+#define SDFR_DECODER_STEP_RESIZE_T_X_MIX_PAD 26
+#define SDFR_DECODER_STEP_VJP_STAGE 27
+#define SDFR_DECODER_STEP_FC_LAST_T 28
+#define SDFR_DECODER_STEP_FC_LAST_T_BATCH 29
+#define SDFR_DECODER_STEP_FC_STACK_T 30
+#define SDFR_DECODER_STEP_FC_STACK_T_WAVE 31
+SDFR_API int sdfr_decoder_launch_plan(const sdfr_decoder* decoder, int pass, int N, int flags, int* steps, int capacity);
 /* Vector-Jacobian product of the decoder w.r.t. the latent, weights held constant: what
  * loss.backward() propagates to latent_shape in SDFPipeline.__call__
  * (sdfest/estimation/simple_setup.py:413-414, :456) through SDFDecoder.forward

@@ -1745,330 +1745,7 @@ __global__ __launch_bounds__(64) void fc_stack_backward_wave_kernel(const float*
 
 using namespace sdfr;
 
-namespace {
-// conv3d_mfma_kernel's split-K form: for launches with so few tiles that a wave's K loop is the critical path
-int use_split_k(bool zgrp, int n_tiles, int co_tiles, int N, int kpad) {
-  // (the choice does not depend on N up to 16 samples: small batches decode bit-identically to single latents)
-  return (!zgrp && (long long)n_tiles * co_tiles <= SDFR_SPLITK_MAX_TILES && N <= SDFR_SPLITK_MAX_LATENTS && kpad >= 128) ? 1 : 0;
-}
-
-// A kernel's dynamic-LDS limit (MaxDynamicSharedMemorySize) raised to `bytes` once -- above 64 KiB it must be; `bytes` +
-// the kernel's static LDS <= 160 KiB.  false: the runtime refused, and the caller takes its other form.
-// Keyed by the kernel alone: the first answer holds for every device of the process.  (Per-device keying is a
-// change to this key -- the pair (device, fn) -- and to nothing else.)
-bool raise_lds_limit(const void* fn, size_t bytes) {
-  static std::map<const void*, bool> done;
-  static std::mutex mu;
-  std::lock_guard<std::mutex> lock(mu);
-  auto it = done.find(fn);
-  if (it == done.end()) {
-    const bool ok = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess;
-    if (!ok) (void)hipGetLastError();   // (not an error of the call that asked: it takes the other form)
-    it = done.emplace(fn, ok).first;
-  }
-  return it->second;
-}
-
-// conv3d_mfma_kernel in the form the layer / batch takes (plain, z-grouped, split-K, input resident in LDS)
-void launch_mfma(const float* src, const float* w, const int* tab, const float* bias, float* dst, int cin, int cout,
-                 int n, int m, int kp, int relu, int nt, int co_tiles, int zg, int split, int N, hipStream_t st) {
-  const int tw = nt >= 32768 ? 4 : 1;
-  const size_t in_floats = (size_t)cin * n * n * n, lds_res = ((size_t)kp * 17 + in_floats) * sizeof(float);
-  // (resident: the whole grid is then N * co_tiles workgroups -- only where that still fills the chip)
-  const bool resident = !split && zg == 1 && N * co_tiles >= 128 && nt >= 8 && nt <= 64 && lds_res <= 120 * 1024 &&
-                        (in_floats & 3) == 0 && ((uintptr_t)src & 15) == 0;
-  if (resident && raise_lds_limit(reinterpret_cast<const void*>(&conv3d_mfma_kernel<true>), 120 * 1024)) {
-    hipLaunchKernelGGL(conv3d_mfma_kernel<true>, dim3(1, co_tiles, N), dim3(256), lds_res, st, src, w, tab, bias, dst,
-                       cin, cout, n, m, kp, relu, 1, 1, 0);
-    return;
-  }
-  hipLaunchKernelGGL(conv3d_mfma_kernel<false>, dim3(split ? nt : (nt + 4 * tw - 1) / (4 * tw), co_tiles, N), dim3(256),
-                     (size_t)kp * 17 * sizeof(float) + (split ? 4096 : 0), st, src, w, tab, bias, dst, cin, cout, n, m,
-                     kp, relu, tw, zg, split);
-}
-
-// The direct convolution is for batches (enough tiles to fill the chip).
-// Does a layer / batch qualify for it?  (n: input size, m: output size)
-bool direct_ok(size_t w_off, int n, int m, int N, int* tx = nullptr, int* ty = nullptr, int* zc = nullptr) {
-  if (w_off == 0 || n > 64 || m < 4) return false;
-  const int ZC = (m + 3) / 4;                       // z chunks of 4 outputs per column
-  int zc_pow = 1;
-  while (zc_pow < ZC) zc_pow <<= 1;                 // threads per column (power of two <= 16)
-  if (zc_pow > 16) return false;
-  const int cols = 256 / zc_pow;                    // columns per workgroup, at most
-  // TX x TY <= cols columns per workgroup: the fewest tiles, then the smallest staged patch (30^3 outputs: 5 x 6
-  // columns cover them exactly in 30 tiles of 7 x 8 patch columns; the power-of-two 4 x 8 takes 32 tiles of 6 x 10)
-  int TX = 1, TY = cols;
-  long long best = -1;
-  for (int a = 1; a <= std::min(cols, m); ++a) {
-    const int b = std::min(cols / a, m);
-    const long long tiles = (long long)((m + a - 1) / a) * ((m + b - 1) / b);
-    const long long cost = tiles * 4096 + (a + 2) * (b + 2);
-    if (best < 0 || cost < best) { best = cost; TX = a; TY = b; }
-  }
-  const int tiles = ((m + TX - 1) / TX) * ((m + TY - 1) / TY);
-  // enough workgroups to fill the chip -- or, for the handful of latents of a multi-object frame (8 ... 31: K objects
-  // side by side), a layer of at least 15 tiles from 240 workgroups on: decoder N = 16 forward 162 -> 97 us, the 8- and
-  // 16-object loops +8 % / +24 % objects per second; single latents, small layers and big batches keep their forms
-  // (measured with the plain 240 threshold: N = 1 VJP 123 -> 160 us, N = 256 403 -> 453 us)
-  const long long wgs = (long long)tiles * N;
-  if (wgs < SDFR_DIRECT_MIN_TILES && !(N >= SDFR_DIRECT_MIN_LATENTS_FEW && tiles >= 15 && wgs >= SDFR_DIRECT_MIN_TILES_FEW)) return false;
-  if (tx) *tx = TX;
-  if (ty) *ty = TY;
-  if (zc) *zc = zc_pow;
-  return true;
-}
-// Returns false when the layer / batch does not qualify and the caller falls back to the MFMA kernel.
-// pz: floats between the z-rows of src (n, or more: the padded tensors of the backward pass)
-// mix_*: the 1x1x1 layer applied in the epilogue (conv3d_direct_kernel), or mix_out == NULL
-bool launch_direct(const sdfr_decoder* d, size_t w_off, const float* src, const float* bias, float* dst,
-                   int cin, int cout, int n, int pz, int m, int relu, int N, hipStream_t st,
-                   const float* mix_w = nullptr, const float* mix_b = nullptr, int mix_co = 0, float* mix_out = nullptr) {
-  int TX, TY, ZC;
-  if (!direct_ok(w_off, n, m, N, &TX, &TY, &ZC)) return false;
-  const int tiles = ((m + TX - 1) / TX) * ((m + TY - 1) / TY);
-  // channels per LDS chunk: patch of CK channels <= 24 KB
-  const int per_ch = (TX + 2) * (TY + 2) * ((pz + 3) & ~3);   // (LDS rows are padded to 16 bytes)
-  int CK = std::max(1, std::min(cin, (24 * 1024 / 4) / per_ch));
-  const size_t lds = ((size_t)CK * per_ch + 8) * sizeof(float);  // + the over-read of the last z-run
-  const dim3 grid(tiles, 1, N);
-  const float* w = d->d_params + w_off;
-  // 16-byte loads: runs start and end on 16-byte boundaries, offsets and channel fit the packed word of the prefetch
-  const bool vec4 = (pz & 3) == 0 && ((uintptr_t)src & 15) == 0 && (size_t)CK * n * n * pz < 0xffffff && CK < 127;
-  if (!vec4 && pz != n) return false;   // (the scalar-load form takes dense rows only; callers pad rows only to 16 bytes)
-  dispatch_int_else_last<4, 8, 16>(cout, [&](auto co) {
-    constexpr int CO = decltype(co)::value;
-    if (vec4) hipLaunchKernelGGL((conv3d_direct_kernel<CO, true>), grid, dim3(256), lds, st, src, w, bias, dst, cin, n, pz, m,
-                                 relu, TX, TY, ZC, CK, mix_w, mix_b, mix_co, mix_out);
-    else hipLaunchKernelGGL((conv3d_direct_kernel<CO, false>), grid, dim3(256), lds, st, src, w, bias, dst, cin, n, pz, m,
-                            relu, TX, TY, ZC, CK, mix_w, mix_b, mix_co, mix_out);
-  });
-  return true;
-}
-
-// resize ni -> n (up-sampling) folded into the direct convolution that follows it (conv3d_direct_up_kernel): true if
-// launched.  Same tiling as launch_direct; the chunk is also bounded by the coarse columns a thread prefetches.
-bool launch_direct_up(const sdfr_decoder* d, size_t w_off, const float* src, int ni, const float* bias, float* dst,
-                      int cin, int cout, int n, int m, int relu, int N, hipStream_t st) {
-  const int mode = d->opt_fused_resize.load(std::memory_order_relaxed);
-  if (!mode) return false;
-  if (n < 16 || n > 64 || (n & (n - 1)) != 0 || ni > n || ni < 2) return false;
-  // Measured on 256 mug latents (profiles/r04_decoder_fused_resize.txt): 6 -> 16 in front of the 16 -> 8 layer,
-  // 112 us folded against 96 + 26 as two launches; 14 -> 32 in front of the 8 -> 4 layer, 268 us folded against
-  // 170 + 77 -- there the patch's 1.87x overlap makes every workgroup interpolate what its neighbours interpolate
-  // too, in a kernel that is VALU-bound already.  So: folded up to a fine size of 16 (mode 2, the tests': always).
-  if (mode == 1 && n > 16) return false;
-  int TX, TY, ZC;
-  if (!direct_ok(w_off, n, m, N, &TX, &TY, &ZC)) return false;
-  const int IX = TX + 2, IY = TY + 2;
-  if (IX > 34 || IY > 34) return false;
-  // coarse columns under a patch, worst tile (the kernel's float arithmetic)
-  const int max_cols = host_resize_span(ni, n, m, TX, IX) * host_resize_span(ni, n, m, TY, IY);
-  const int per_ch = IX * IY * n;
-  int CK = std::max(1, std::min(cin, (24 * 1024 / 4) / per_ch));
-  CK = std::min(CK, 2048 / (max_cols * ni));      // <= 8 prefetched values per thread
-  if (CK < 1 || CK >= 127 || (size_t)CK * ni * ni * ni >= 0xffffff) return false;
-  const size_t lds = ((size_t)CK * per_ch + 8 + (size_t)CK * max_cols * ni) * sizeof(float);
-  if (lds > 60 * 1024) return false;
-  int log_n = 0;
-  while ((1 << log_n) < n) ++log_n;
-  const int tiles = ((m + TX - 1) / TX) * ((m + TY - 1) / TY);
-  const dim3 grid(tiles, 1, N);
-  const float* w = d->d_params + w_off;
-  return dispatch_int<4, 8, 16>(cout, [&](auto co) {
-    hipLaunchKernelGGL((conv3d_direct_up_kernel<decltype(co)::value>), grid, dim3(256), lds, st, src, ni, w, bias, dst, cin,
-                       n, log_n, m, relu, TX, TY, ZC, CK, max_cols);
-  });
-}
-
-// ---- few latents: layer pairs as one launch each (decoder_fused.hpp) --------------------------------------------------
-constexpr size_t kFusedLdsMax = 150 * 1024;
-
-// the source ranges of the resize n_in -> n_out: kept per decoder at creation; any other pair is computed into `local`
-const ResizeSources* find_resize_sources(const sdfr_decoder* d, int n_in, int n_out) {
-  for (const ResizeSources& r : d->rs_src)
-    if (r.n_in == n_in && r.n_out == n_out) return &r;
-  return nullptr;
-}
-const ResizeSources& resize_sources_of(const sdfr_decoder* d, int n_in, int n_out, ResizeSources& local) {
-  if (const ResizeSources* r = find_resize_sources(d, n_in, n_out)) return *r;
-  local = host_resize_sources(n_in, n_out);
-  return local;
-}
-
-// resize ni -> n + the 3x3x3 convolution n -> m behind it in one launch (conv3d_mfma_up_kernel): true if launched.
-// Only where the unfused convolution takes its split-K form (the arithmetic this kernel reproduces).
-bool launch_mfma_up(const sdfr_decoder* d, size_t direct_off, const float* src, int ni, const float* w, const float* bias,
-                    float* dst, int cin, int cout, int n, int m, int kpad, int relu, int N, hipStream_t st,
-                    const float* mix_w = nullptr, const float* mix_b = nullptr, int mix_co = 0, float* mix_out = nullptr) {
-  if (!(d->opt_fused_single.load(std::memory_order_relaxed) & 1)) return false;
-  if (ni > n || ni < 1 || m != n - 2 || m < 1 || direct_ok(direct_off, n, m, N)) return false;
-  const int co_tiles = (cout + 15) / 16, ZT = (m + 15) / 16;
-  if (ZT > 4 || !use_split_k(false, (m * m * m + 15) / 16, co_tiles, N, kpad)) return false;
-  int TX, TY;   // columns per workgroup
-  few_latent_tile(m, ZT, (long long)co_tiles * N, TX, TY);
-  const int tiles = TX * TY * ZT, wpt = 4 * tiles <= 16 ? 4 : 1;
-  const int threads = std::max(256, 64 * wpt * tiles);
-  const int IX = TX + 2, IY = TY + 2;
-  const int CX = std::max({1, host_resize_span(ni, n, m, TX, IX), host_resize_span(ni, n, m, TY, IY)});
-  const int PZ = 16 * ZT + 2, patch_n = cin * IX * IY * PZ;
-  const size_t zc_n = (size_t)cin * CX * CX * PZ;
-  if (zc_n >= 65536 || patch_n >= 65536 || threads / PZ < 1 || threads / (IX * IY) < 1) return false;   // (reciprocal divisions)
-  const size_t lds = ((size_t)kpad * 17 + (wpt == 4 ? 4 * threads : 0) + ((patch_n + 3) & ~3) + zc_n) * sizeof(float);
-  const void* fn = wpt == 4 ? reinterpret_cast<const void*>(&conv3d_mfma_up_kernel<4>) : reinterpret_cast<const void*>(&conv3d_mfma_up_kernel<1>);
-  if (lds > kFusedLdsMax || (lds > 64 * 1024 && !raise_lds_limit(fn, kFusedLdsMax))) return false;
-  const dim3 grid(((m + TX - 1) / TX) * ((m + TY - 1) / TY), co_tiles, N);
-  if (mix_out && co_tiles != 1) return false;
-  if (wpt == 4) hipLaunchKernelGGL(conv3d_mfma_up_kernel<4>, grid, dim3(threads), lds, st, src, ni, w, bias, dst, cin, cout, n,
-                                   m, kpad, relu, CX, ZT, TX, TY, mix_w, mix_b, mix_co, mix_out);
-  else hipLaunchKernelGGL(conv3d_mfma_up_kernel<1>, grid, dim3(threads), lds, st, src, ni, w, bias, dst, cin, cout, n, m,
-                          kpad, relu, CX, ZT, TX, TY, mix_w, mix_b, mix_co, mix_out);
-  return true;
-}
-
-// the Linear stack + the first convolution in one launch (fc_conv_kernel): true if launched
-bool launch_fc_conv(const sdfr_decoder* d, const FcDesc& fd, const float* z, float* fc_out, size_t direct_off,
-                    const float* w, const float* bias, float* dst, int cin, int cout, int n, int kpad, int relu, int N,
-                    hipStream_t st) {
-  if (!(d->opt_fused_single.load(std::memory_order_relaxed) & 2)) return false;
-  const int m = n - 2;
-  if (m < 1 || !decoder_fc_one_wave(d, fd) || direct_ok(direct_off, n, m, N)) return false;
-  const int co_tiles = (cout + 15) / 16, ZT = (m + 15) / 16;
-  if (ZT > 4 || !use_split_k(false, (m * m * m + 15) / 16, co_tiles, N, kpad)) return false;
-  const int PZ = 16 * ZT + 2, patch_n = cin * 9 * PZ, items = cin * 9 * n;
-  if (patch_n >= 65536 || fd.width[fd.n_fc - 1] > kFcWaveWidth) return false;
-  // a row of the wide layer per thread where the workgroup size allows
-  int threads = 256 * ZT;
-  while (threads < 1024 && threads < items) threads *= 2;
-  const size_t lds = ((size_t)kpad * 17 + 4 * threads + patch_n) * sizeof(float);
-  const void* fn = reinterpret_cast<const void*>(&fc_conv_kernel);
-  if (lds > 100 * 1024 || (lds > 38 * 1024 && !raise_lds_limit(fn, 100 * 1024))) return false;   // (+ 25 KB static)
-  hipLaunchKernelGGL(fc_conv_kernel, dim3(m * m, co_tiles, N), dim3(threads), lds, st, d->d_params, fd, z, fc_out, w, bias,
-                     dst, cin, cout, n, m, kpad, relu, ZT);
-  return true;
-}
-
-// One stage of the VJP for few latents in one launch (vjp_stage_kernel): the transposed resize n_out -> n_in of C channels
-// (+ ReLU mask, + the swapped 1x1x1 layer C = 1 -> mix_cout channels, + zero padding) and the transposed convolution of
-// layer lc that reads it.  The plan, or ok == false where the pair keeps its two launches.  zin: the stage runs the z pass
-// itself (g is the fine gradient); 0: its producer's epilogue has (g is coarse along z already).
-struct VjpPlan {
-  bool ok = false;
-  int taps = 0, mode = 0, CK = 0, FX = 0, ZT = 0, TX = 1, TY = 1, threads = 0, zin = 1;
-  size_t lds = 0;
-};
-VjpPlan vjp_stage_plan(const sdfr_decoder* d, int lc, int C, int n_in, int n_out, int mix_cout, int N, int zin,
-                       const float* g, bool first) {
-  VjpPlan p;
-  p.zin = zin;
-  // bit 4: the FIRST stage of the VJP (the one that reads the decoder's incoming gradient); bit 8: the stages behind a
-  // fused one as well, chained through the z-pass epilogue (measured: no faster than their two launches each)
-  const int opt = d->opt_fused_single.load(std::memory_order_relaxed);
-  if (!(opt & (first ? 4 : 8))) return p;
-  const int k = d->conv_k[lc], ci_n = d->conv_cin[lc], co_n = d->conv_cout[lc];
-  const int CP = mix_cout > 0 ? mix_cout : C;
-  if (k != 3 || d->conv_swap[lc] || CP != co_n || (mix_cout > 0 && (C != 1 || mix_cout > 4 || !zin))) return p;
-  if (n_in != d->conv_in_size[lc] - k + 1 || n_in > n_out || n_in > 64) return p;
-  if (zin && ((n_out & 3) || ((uintptr_t)g & 15))) return p;
-  // (the tables of this resize: built at creation for the resize in front of layer lc + 1)
-  if (lc + 1 >= d->n_conv || d->rs_tab_off[lc + 1] == 0 || d->conv_prev[lc + 1] != n_in || d->conv_in_size[lc + 1] != n_out) return p;
-  const int pad = k - 1, np = n_in + 2 * pad, nc = np - 2, kpad = d->bwd_kpad[lc], ci_tiles = (ci_n + 15) / 16;
-  // the form the unfused transposed convolution takes: plain or split-K only (not the direct, not the z-grouped one)
-  if (N > SDFR_SPLITK_MAX_LATENTS || direct_ok(d->bwd_direct_off[lc], np, nc, N)) return p;
-  const int split = use_split_k(false, (nc * nc * nc + 15) / 16, ci_tiles, N, kpad);
-  const sdfr_decoder::ZPlan& zp = d->bwd_z[lc];
-  if (!split && zp.zg > 1 && (long long)nc * nc * (nc / zp.zg) * N >= kZGroupMinRows) return p;
-  p.ZT = (nc + 15) / 16;
-  if (p.ZT > 4) return p;
-  ResizeSources local;
-  const ResizeSources& rs = resize_sources_of(d, n_in, n_out, local);
-  if (rs.empty || rs.max_span > 16 || rs.max_taps > kBtTaps) return p;
-  p.taps = rs.max_taps <= 6 ? 6 : 12;
-  few_latent_tile(nc, p.ZT, (long long)ci_tiles * N, p.TX, p.TY);   // columns per workgroup
-#ifdef SDFR_VJP_TUNE   // timing experiments: tile shape and workgroup size from the environment
-  if (const char* e = getenv("SDFR_VJP_TX")) p.TX = atoi(e);
-  if (const char* e = getenv("SDFR_VJP_TY")) p.TY = atoi(e);
-#endif
-  const int tiles = p.TX * p.TY * p.ZT, max_thr = zin ? 512 : 1024;   // (vjp_stage_kernel's launch bounds)
-  if (64 * tiles > max_thr) return p;
-  p.mode = !split ? 0 : (256 * tiles <= max_thr ? 4 : 1);
-  const int IX = p.TX + 2, IY = p.TY + 2;
-  for (int pass = 0; pass < 2; ++pass) {
-    const int T = pass ? p.TY : p.TX, I = pass ? IY : IX;
-    for (int t0 = 0; t0 < nc; t0 += T)
-      p.FX = std::max(p.FX, rs.hi[std::min(t0 - pad + I - 1, n_in - 1)] - rs.lo[std::max(t0 - pad, 0)] + 1);
-  }
-  // channels per round and workgroup size: the whole tensor in one round where the LDS allows
-  const int PZ = 16 * p.ZT + 2, patch_n = CP * IX * IY * PZ, RL = zin ? n_out : n_in;
-  const int min_thr = std::max(256, p.mode == 4 ? 256 * tiles : 64 * tiles);
-  const size_t epi = (size_t)p.TX * p.TY * 16 * nc;   // (the epilogue's rows reuse F)
-  for (int CK = C; CK >= 1; --CK) {
-    const size_t f_n = std::max((size_t)CK * p.FX * p.FX * RL, epi);
-    const size_t units = (size_t)CK * p.FX * p.FX * (zin ? RL / 4 : RL);
-    int threads = min_thr;
-    while (threads < max_thr && (size_t)threads * 8 < units) threads *= 2;
-#ifdef SDFR_VJP_TUNE
-    if (const char* e = getenv("SDFR_VJP_THREADS")) threads = std::max(min_thr, std::min(max_thr, atoi(e)));
-#endif
-    const size_t fixed = (size_t)kpad * 17 + (p.mode == 4 ? 4 * threads : 0) + ((patch_n + 3) & ~3);
-    const size_t lds = (fixed + (((size_t)CK * p.FX * IY * n_in + 3) & ~(size_t)3) + f_n) * sizeof(float);
-    if (lds > kFusedLdsMax - 8 * 1024 || units >= 65536 || (size_t)CK * IX * IY * n_in >= 65536) continue;   // (8 KB static)
-    p.CK = CK;
-    p.lds = lds;
-    p.threads = threads;
-    break;
-  }
-  if (!p.CK || patch_n >= 65536) return p;
-  p.ok = true;
-  return p;
-}
-
-// e_nin > 0: the stage's epilogue applies the z pass of the NEXT stage's transposed resize (nc -> e_nin)
-struct ScaledGrad {   // sdfr_decoder_backward_latent_deferred_scaled
-  float* g2;          // [n][volume]
-  const float* cnt;   // [n]
-  float weight;
-  int n;
-};
-bool launch_vjp_stage(const sdfr_decoder* d, const VjpPlan& p, int lc, const float* g, int C, int n_in, int n_out,
-                      const float* act, const float* mix_w, int mix_cout, int e_nin, float* dst, int N, hipStream_t st,
-                      const ScaledGrad* sg = nullptr) {
-  const int ci_n = d->conv_cin[lc], ci_tiles = (ci_n + 15) / 16, pad = d->conv_k[lc] - 1, nc = n_in + 2 * pad - 2;
-  const float* zb = d->d_params + d->zero_bias_off;
-  VjpStage s;
-  s.g = g; s.act = act; s.mix_w = mix_w; s.mix_b = zb;
-  s.wmat = d->d_params + d->bwd_w_off[lc]; s.bias = zb; s.out = dst;
-  s.C = C; s.n_in = n_in; s.n_out = n_out; s.pad = pad; s.Cc = ci_n; s.kpad = d->bwd_kpad[lc];
-  s.CK = p.CK; s.FX = p.FX; s.ZT = p.ZT; s.TX = p.TX; s.TY = p.TY; s.zin = p.zin; s.e_nin = e_nin;
-  s.tab = d->d_params + d->rs_tab_off[lc + 1];
-  s.e_tab = e_nin > 0 ? d->d_params + d->rs_tab_off[lc] : nullptr;
-  if (sg) {
-    if (!p.zin || ((uintptr_t)sg->g2 & 15)) return false;
-    s.g2 = sg->g2; s.cnt = sg->cnt; s.weight = sg->weight;
-  }
-  const dim3 grid(((nc + p.TX - 1) / p.TX) * ((nc + p.TY - 1) / p.TY), ci_tiles, N), block(p.threads);
-  bool launched = false;
-  auto launch = [&](auto co, auto taps, auto mode, auto zin) {
-    const auto kernel =
-        &vjp_stage_kernel<decltype(co)::value, decltype(taps)::value, decltype(mode)::value, decltype(zin)::value>;
-    if (p.lds > 56 * 1024 && !raise_lds_limit(reinterpret_cast<const void*>(kernel), kFusedLdsMax - 8 * 1024)) return;
-    hipLaunchKernelGGL(kernel, grid, block, p.lds, st, s);
-    launched = true;
-  };
-  // (only the stage without a channel mix has a form that starts behind its producer's z pass)
-  dispatch_int_else_last<0, 1, 2, 3, 4>(mix_cout, [&](auto co) {
-    dispatch_int_else_last<6, 12>(p.taps, [&](auto taps) {
-      dispatch_int_else_last<0, 4, 1>(p.mode, [&](auto mode) {
-        if constexpr (decltype(co)::value == 0) {
-          if (!p.zin) return launch(co, taps, mode, std::false_type{});
-        }
-        launch(co, taps, mode, std::true_type{});
-      });
-    });
-  });
-  return launched;
-}
-}  // namespace
+#include "decoder_plan.hpp"   // a pass is planned (Planner), then launched (launch_plan)
 
 extern "C" int sdfr_decoder_set_option(sdfr_decoder* d, int option, int value) {
   if (!d) return fail(SDFR_E_NULL, "sdfr_decoder_set_option: decoder is NULL");
@@ -2366,6 +2043,9 @@ extern "C" size_t sdfr_decoder_tape_bytes(const sdfr_decoder* d, int N) {
 }
 
 namespace {
+unsigned mod16(const void* p) { return (unsigned)((uintptr_t)p & 15); }
+float* aligned256(void* workspace) { return (float*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255); }   // (the buffers start there)
+
 // stages: 1 the Linear stack only (its output into the tape's slot), 2 the convolutional part from that slot, 3 both
 int decoder_forward_impl(const sdfr_decoder* d, const float* z, int N, int enforce_tsdf,
                          float* out, float* tape, void* workspace,
@@ -2381,245 +2061,14 @@ int decoder_forward_impl(const sdfr_decoder* d, const float* z, int N, int enfor
     return fail(SDFR_E_WORKSPACE, "sdfr_decoder_forward: workspace %zu < %zu bytes", workspace_bytes,
                 sdfr_decoder_workspace_bytes(d, N));
   SDFR_HIP_TRY(hipSetDevice(d->device));
-  hipStream_t st = (hipStream_t)stream;
-  uintptr_t wsp = ((uintptr_t)workspace + 255) & ~(uintptr_t)255;
-  float* buf[2] = {(float*)wsp, (float*)wsp + (size_t)N * d->max_act};
-  int cur = 0;
-
-  FcDesc fd;
-  decoder_fc_desc(d, &fd, nullptr, nullptr);
-  const int last = d->fc_out[d->n_fc - 1];
-  // with a tape, every ReLU'd layer output goes to its own slot (and is read from there)
-  const float* act_in;
-  int l_first = 0;   // the first conv layer the loop below still has to run
-  // few latents: the Linear stack and the first convolution as one launch (fc_conv_kernel) -- a 3x3x3 layer that is not
-  // the last, with a layer behind it that is not a 1x1x1 one swapped with its resize
-  if (stages == 2) {
-    act_in = tape + (size_t)N * d->tape_fc_off;   // (left there by stage 1 -- or by the loop's tail, sdfr_loop_tail_fused)
-    l_first = -1;
-  }
-  if (stages == 3 && d->n_conv >= 2 && !d->conv_swap[0] && d->conv_k[0] == 3 && !(d->conv_swap[1] && d->conv_k[1] == 1) &&
-      N < 32 && d->conv_in_size[0] - 2 != d->volume) {
-    float* fc_dst = tape ? tape + (size_t)N * d->tape_fc_off : nullptr;
-    float* dst0 = tape ? tape + (size_t)N * d->tape_conv_off[0] : buf[cur ^ 1];
-    if (launch_fc_conv(d, fd, z, fc_dst, d->fwd_direct_off[0], d->d_params + d->conv_w_off[0], d->d_params + d->conv_b_off[0], dst0,
-                       d->conv_cin[0], d->conv_cout[0], d->conv_in_size[0], d->conv_kpad[0], d->conv_relu[0], N, st)) {
-      if (dst0 == buf[cur ^ 1]) cur ^= 1;
-      act_in = dst0;
-      l_first = 1;
-    }
-  }
-  if (l_first == 0) {
-    float* fc_dst = tape ? tape + (size_t)N * d->tape_fc_off : buf[cur];
-    int hid = d->latent;   // widest input of a layer
-    for (int l = 0; l + 1 < d->n_fc; ++l) hid = std::max(hid, d->fc_out[l]);
-    constexpr int kFcSamples = 8;
-    const size_t fc_lds = 2 * (size_t)hid * kFcSamples * sizeof(float);
-    if (N >= 4 * kFcSamples && fc_lds <= 32 * 1024 && decoder_fc_one_wave(d, fd))   // batches (small ones keep the form of a single decode)
-      hipLaunchKernelGGL((fc_stack_batch_kernel<kFcSamples, true>),
-                         dim3((last + kFcBlock - 1) / kFcBlock, (N + kFcSamples - 1) / kFcSamples), dim3(kFcBlock),
-                         fc_lds, st, d->d_params, fd, z, N, hid, fc_dst);
-    else if (N >= 4 * kFcSamples && fc_lds <= 48 * 1024)
-      hipLaunchKernelGGL((fc_stack_batch_kernel<kFcSamples, false>),
-                         dim3((last + kFcBlock - 1) / kFcBlock, (N + kFcSamples - 1) / kFcSamples), dim3(kFcBlock),
-                         fc_lds, st, d->d_params, fd, z, N, hid, fc_dst);
-    else if (decoder_fc_one_wave(d, fd))
-      hipLaunchKernelGGL(fc_stack_kernel<true>, dim3((last + kFcBlock - 1) / kFcBlock, N), dim3(kFcBlock), 0, st,
-                         d->d_params, fd, z, fc_dst);
-    else
-      hipLaunchKernelGGL(fc_stack_kernel<false>, dim3((last + kFcBlock - 1) / kFcBlock, N), dim3(kFcBlock), 0, st,
-                         d->d_params, fd, z, fc_dst);
-    act_in = fc_dst;
-  }
-  if (l_first < 0) l_first = 0;
-  if (stages == 1) {
-    SDFR_HIP_TRY(hipGetLastError());
-    return 0;
-  }
-
-  const float clampv = (enforce_tsdf && d->tsdf > 0.0f) ? d->tsdf : 0.0f;
-  int c = d->conv_cin[0], n = d->conv_in_size[0];
-  if (l_first == 1) { c = d->conv_cout[0]; n = d->conv_in_size[0] - d->conv_k[0] + 1; }
-  const size_t vox = (size_t)d->volume * d->volume * d->volume;
-  auto resize = [&](const float* src, int C, int ni, int no, int relu, float clamp, float* dst) {
-    // input columns under an 8 x 8 output patch, worst tile
-    const int max_r = host_resize_span(ni, no, no, kResizeTile, kResizeTile);
-    const size_t lds = ((size_t)max_r * max_r * (ni + no) + 3) * sizeof(float);   // (+3: the second array starts 16-byte aligned)
-    const int tiles = (no + kResizeTile - 1) / kResizeTile;
-    const bool pow2 = no >= 16 && no <= 128 && (no & (no - 1)) == 0;
-    // (a single decode has too few tiles to fill the chip: the gather kernel is faster there)
-    const long long tile_items = (long long)tiles * tiles * C * N;
-    if (pow2 && ni <= no && lds <= 48 * 1024 && (long long)C * N < (1ll << 30) && tile_items >= SDFR_RESIZE_TILED_MIN_ITEMS) {
-      // volumes per workgroup: as many as still leave ~8 workgroups per CU
-      const int items = C * N;
-      // (256 mug latents, us: 14 -> 32 x 8 channels 68.6 / 52.9 / 55.4 / 53.3 at 1 / 2 / 4 / 8 volumes per workgroup,
-      // 30 -> 64 x 1 channel 68.5 / 60.3 / 55.8 / 63.6 -- profiles/r04_decoder_resize_ipw.txt; before this form 70.8 / 66.7)
-      const int ipw = std::max((int)std::max<long long>(1, std::min<long long>(4, tile_items / 2048)), (items + 65534) / 65535);
-      const dim3 grid(tiles * tiles, (items + ipw - 1) / ipw, 1);
-      const bool vec = ((uintptr_t)dst & 15) == 0;
-      int log_no = 4;   // (pow2: no is 16, 32, 64 or 128)
-      while ((1 << log_no) < no) ++log_no;
-      dispatch_int_else_last<4, 5, 6, 7>(log_no, [&](auto log) {
-        constexpr int LOG = decltype(log)::value;
-        if (vec) hipLaunchKernelGGL((resize3_tiled_kernel<LOG, true>), grid, dim3(256), lds, st, src, items, ipw, ni, relu,
-                                    clamp, max_r * max_r, dst);
-        else hipLaunchKernelGGL((resize3_tiled_kernel<LOG, false>), grid, dim3(256), lds, st, src, items, ipw, ni, relu,
-                                clamp, max_r * max_r, dst);
-      });
-      return;
-    }
-    const size_t cnt = (size_t)C * no * no * no;
-    hipLaunchKernelGGL(resize3_kernel, dim3((unsigned)((cnt + 255) / 256), N), dim3(256), 0, st, src, C,
-                       ni, no, relu, clamp, dst);
-  };
-  // where layer l's output goes: straight to `out` (a last layer of the volume's size with no clamp left to apply),
-  // to its tape slot, or (nullptr) to the other buffer
-  // (a ReLU'd last layer of a taped forward goes to its tape slot first -- the VJP reads its mask there -- and is
-  // copied out: until round 6 it went straight to `out` and the VJP masked with whatever the slot held)
-  auto layer_dst_of = [&](int l, bool no_clamp, bool& to_out) -> float* {
-    const int m_out = d->conv_in_size[l] - d->conv_k[l] + 1;
-    to_out = l == d->n_conv - 1 && m_out == d->volume && no_clamp && !(tape && d->conv_relu[l]);
-    return to_out ? out : (tape ? tape + (size_t)N * d->tape_conv_off[l] : nullptr);
-  };
-  // behind the last layer: what is not in `out` yet gets there, resized to the volume or copied, and clamped
-  auto finish = [&](const float* act, int n_act) {
-    if (act == out) return;
-    if (n_act != d->volume) {
-      resize(act, 1, n_act, d->volume, 0, clampv, out);
-    } else {
-      copy_words_async(out, act, (size_t)N * vox, st);
-      if (clampv > 0.0f)
-        hipLaunchKernelGGL(clamp_kernel, dim3((unsigned)(((size_t)N * vox + 255) / 256)), dim3(256), 0, st, out,
-                           (size_t)N * vox, clampv);
-    }
-  };
-  bool premixed = false;   // the previous layer's epilogue has applied this (1x1x1) layer already: act_in is its output
-  for (int l = l_first; l < d->n_conv; ++l) {
-    const bool swap = d->conv_swap[l] != 0, is_last = (l == d->n_conv - 1);
-    const int k = d->conv_k[l], co_n = d->conv_cout[l], kpad = d->conv_kpad[l];
-    // (batches: an up-sampling resize in front of a 3x3x3 layer is folded into that layer's patch load --
-    // conv3d_direct_up_kernel -- and the up-sampled tensor is never written)
-    bool fused_up = false, fused_mixed = false;
-    const int nf = d->conv_in_size[l], mf = nf - k + 1;   // the sizes a fused resize + convolution works at
-    bool to_out_f;
-    float* ldst = layer_dst_of(l, clampv == 0.0f, to_out_f);
-    float* cdst = ldst ? ldst : buf[cur ^ 1];
-    if (!swap && n != d->conv_in_size[l] && k == 3 && d->fwd_direct_off[l] != 0) {
-      fused_up = launch_direct_up(d, d->fwd_direct_off[l], act_in, n, d->d_params + d->conv_b_off[l], cdst, c, co_n,
-                                  nf, mf, d->conv_relu[l], N, st);
-      if (fused_up) n = nf;   // (act_in stays the coarse tensor: the launch has consumed it)
-    }
-    // few latents: the resize inside the split-K MFMA convolution's operand fetch (conv3d_mfma_up_kernel)
-    if (!fused_up && !swap && n != d->conv_in_size[l] && k == 3) {
-      // ... and where a swapped 1x1x1 layer follows (the mug decoder's last: 4 -> 1 channels behind the resize to the
-      // volume), its channel mix in this launch's epilogue: the resize behind it gathers one channel, not four
-      // (resize3_kernel instead of resize3_mix_kernel: bit for bit the same corner values)
-      const bool mix2 = (d->opt_fused_single.load(std::memory_order_relaxed) & 1) && l + 1 < d->n_conv && !to_out_f &&
-                        d->conv_swap[l + 1] && d->conv_k[l + 1] == 1 && d->conv_cout[l + 1] <= 4 && co_n <= 16 &&
-                        d->conv_in_size[l + 1] != mf;
-      fused_up = launch_mfma_up(d, d->fwd_direct_off[l], act_in, n, d->d_params + d->conv_w_off[l],
-                                d->d_params + d->conv_b_off[l], mix2 ? ldst : cdst, c, co_n, nf, mf, kpad, d->conv_relu[l],
-                                N, st, mix2 ? d->d_params + d->conv_w_off[l + 1] : nullptr,
-                                mix2 ? d->d_params + d->conv_b_off[l + 1] : nullptr, mix2 ? d->conv_cout[l + 1] : 0,
-                                mix2 ? buf[cur ^ 1] : nullptr);
-      if (fused_up) {
-        n = nf;
-        fused_mixed = mix2;
-      }
-    }
-    if (!swap && n != d->conv_in_size[l]) {
-      resize(act_in, c, n, d->conv_in_size[l], 0, 0.0f, buf[cur ^ 1]);
-      cur ^= 1;
-      act_in = buf[cur];
-      n = d->conv_in_size[l];
-    }
-    const int m = n - k + 1;                     // swapped: k == 1, the conv keeps the incoming size
-    const int m_out = d->conv_in_size[l] - k + 1;  // size of the layer's output tensor
-    // (a swapped layer's resize applies the clamp itself)
-    bool to_out;
-    float* layer_dst = layer_dst_of(l, swap || clampv == 0.0f, to_out);
-    float* conv_dst = (!swap && layer_dst) ? layer_dst : buf[cur ^ 1];
-    const int conv_relu = swap ? 0 : d->conv_relu[l];
-    const float* wm = d->d_params + d->conv_w_off[l];
-    const float* bs = d->d_params + d->conv_b_off[l];
-    if (!premixed && swap && k == 1 && co_n <= 4 && m_out != n &&
-        (size_t)N * co_n * m_out * m_out * m_out <= kFewElementsMix) {
-      // single latents: the 1x1 mix inside the resize (one launch)
-      float* dst = layer_dst ? layer_dst : buf[cur ^ 1];
-      const size_t vo = (size_t)m_out * m_out * m_out;
-      const dim3 gm((unsigned)((vo + 255) / 256), N);
-      const float clampm = to_out ? clampv : 0.0f;
-      dispatch_int_else_last<1, 2, 3, 4>(co_n, [&](auto co) {
-        hipLaunchKernelGGL((resize3_mix_kernel<decltype(co)::value>), gm, dim3(256), 0, st, act_in, wm, bs, c, n, m_out,
-                           d->conv_relu[l], clampm, dst);
-      });
-      if (dst == buf[cur ^ 1]) cur ^= 1;
-      act_in = dst;
-      c = co_n;
-      n = m_out;
-      if (is_last) finish(act_in, n);
-      continue;
-    }
-    // batches: a swapped 1x1x1 layer behind this one is applied in this layer's epilogue (conv3d_direct_kernel)
-    bool mix_next = false;
-    if (!swap && !fused_up && k == 3 && l + 1 < d->n_conv && d->conv_swap[l + 1] && d->conv_k[l + 1] == 1 &&
-        d->conv_cout[l + 1] <= 4 && d->fwd_direct_off[l] != 0) {
-      const int mo = d->conv_in_size[l + 1], co2 = d->conv_cout[l + 1];
-      const bool few_next = mo != m && (size_t)N * co2 * mo * mo * mo <= kFewElementsMix;   // (takes resize3_mix_kernel)
-      float* act_dst = tape ? tape + (size_t)N * d->tape_conv_off[l] : nullptr;
-      mix_next = !few_next && launch_direct(d, d->fwd_direct_off[l], act_in, bs, act_dst, c, co_n, n, n, m, conv_relu,
-                                            N, st, d->d_params + d->conv_w_off[l + 1], d->d_params + d->conv_b_off[l + 1],
-                                            co2, buf[cur ^ 1]);
-      if (mix_next) conv_dst = buf[cur ^ 1];
-    }
-    if (premixed) {
-      conv_dst = const_cast<float*>(act_in);   // (nothing to launch, no buffer taken)
-      premixed = false;
-    } else if (mix_next) {
-      premixed = true;
-    } else if (fused_up) {
-      // (launched above)
-      if (fused_mixed) {
-        premixed = true;
-        conv_dst = buf[cur ^ 1];
-      }
-    } else if (k == 1 && co_n <= 4) {
-      const int voxn = n * n * n;
-      const dim3 g1((voxn + 255) / 256, N);
-      const bool v4 = N >= 32 && (voxn & 3) == 0 && (((uintptr_t)act_in | (uintptr_t)conv_dst) & 15) == 0;
-      const dim3 g4((voxn / 4 + 255) / 256, N);
-      dispatch_int_else_last<1, 2, 3, 4>(co_n, [&](auto co) {
-        constexpr int CO = decltype(co)::value;
-        if (v4) hipLaunchKernelGGL((conv1x1_vec4_kernel<CO>), g4, dim3(256), 0, st, act_in, wm, bs, c, voxn, conv_relu, conv_dst);
-        else hipLaunchKernelGGL((conv1x1_kernel<CO>), g1, dim3(256), 0, st, act_in, wm, bs, c, voxn, conv_relu, conv_dst);
-      });
-    } else if (!swap && launch_direct(d, d->fwd_direct_off[l], act_in, bs, conv_dst, c, co_n, n, n, m, conv_relu, N, st)) {
-      // (batched: direct VALU convolution)
-    } else {
-      const sdfr_decoder::ZPlan& zp = d->fwd_z[l];
-      // (a single decode is latency-bound: there the finer grid of the ungrouped form wins)
-      // (up to 16 samples the split-K form decides, so that small batches equal single decodes bit for bit)
-      const int split = use_split_k(false, (m * m * m + 15) / 16, (co_n + 15) / 16, N, kpad);
-      const bool zgrp = !split && zp.zg > 1 && !swap && (long long)m * m * (m / zp.zg) * N >= kZGroupMinRows;
-      const int kp = zgrp ? zp.kpad : kpad, rows = m * m * (m / (zgrp ? zp.zg : 1));
-      const int nt = (rows + 15) / 16;
-      launch_mfma(act_in, zgrp ? d->d_params + zp.w_off : wm,
-                  reinterpret_cast<const int*>(d->d_params + (zgrp ? zp.tab_off : d->conv_tab_off[l])), bs, conv_dst, c,
-                  co_n, n, m, kp, conv_relu, nt, zgrp ? 1 : (co_n + 15) / 16, zgrp ? zp.zg : 1, split, N, st);
-    }
-    if (conv_dst == buf[cur ^ 1]) cur ^= 1;
-    act_in = conv_dst;
-    c = co_n;
-    n = m;
-    if (swap) {  // ... then the resize (and the layer's ReLU, and the final clamp when this is it)
-      float* dst = layer_dst ? layer_dst : buf[cur ^ 1];
-      resize(act_in, c, n, m_out, d->conv_relu[l], to_out ? clampv : 0.0f, dst);
-      if (dst == buf[cur ^ 1]) cur ^= 1;
-      act_in = dst;
-      n = m_out;
-    }
-    if (is_last) finish(act_in, n);
-  }
+  Facts f;
+  f.tape = tape != nullptr; f.clamp = enforce_tsdf && d->tsdf > 0.0f; f.stages = stages;
+  f.out_mod = mod16(out); f.tape_mod = mod16(tape);
+  const Plan plan = make_plan(d, N, f, false);
+  if (plan.error) return fail(SDFR_E_INVALID, "sdfr_decoder_forward: %s", plan.error);
+  Tensors t{};
+  t.z = z; t.out = out; t.tape = tape; t.buf[0] = aligned256(workspace); t.buf[1] = t.buf[0] + (size_t)N * d->max_act;
+  launch_plan(d, plan, false, t, N, (hipStream_t)stream);
   SDFR_HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -2686,330 +2135,49 @@ int decoder_backward_impl(const sdfr_decoder* d, const float* z, const float* ta
     return fail(SDFR_E_WORKSPACE, "sdfr_decoder_backward_latent: workspace %zu < %zu bytes",
                 workspace_bytes, sdfr_decoder_backward_workspace_bytes(d, N));
   SDFR_HIP_TRY(hipSetDevice(d->device));
-  hipStream_t st = (hipStream_t)stream;
-  uintptr_t wsp = ((uintptr_t)workspace + 255) & ~(uintptr_t)255;
-  float* buf[2] = {(float*)wsp, (float*)wsp + (size_t)N * d->max_bwd};
-  int cur = 0;
-  const float* g = grad_out;  // gradient w.r.t. the current tensor, [N][c][n^3]
   const size_t vox_in = (size_t)d->volume * d->volume * d->volume;
-  if (sg && (N != 1 || sg->n < 1 || sg->n > 64 || (vox_in & 3) || ((uintptr_t)grad_out & 15) || ((uintptr_t)sg->g2 & 15) ||
-             !sg->g2 || !sg->cnt))
+  if (sg && (N != 1 || sg->n < 1 || sg->n > 64 || (vox_in & 3) || mod16(grad_out) || mod16(sg->g2) || !sg->g2 || !sg->cnt))
     return fail(SDFR_E_INVALID, "sdfr_decoder_backward_latent_deferred_scaled: one latent, 16-byte aligned volumes of a "
                 "multiple of 4 voxels");
-
-  // sizes of the tensor each conv layer produces
-  std::vector<int> out_n(d->n_conv);
-  for (int l = 0; l < d->n_conv; ++l) out_n[l] = d->conv_in_size[l] - d->conv_k[l] + 1;
-  // transpose of a trilinear resize of [N*C] volumes n_out^3 -> n_in^3: z, then y, then x
-  // pad >= 0: the last pass also applies the ReLU mask `act` (may be null) and the zero padding of the
-  // transposed convolution that follows (resize_x_backward_pad_kernel)
-  // Single latents (the captured loop) are bound by the launch count: there the z and y passes share a launch.
-  // mix_w != nullptr: the x pass also applies the transposed 1x1 layer C -> mix_cout channels
-  // (resize_x_backward_mix_pad_kernel; needs pad >= 0).
-  // pz: floats between the z-rows of the padded tensor written (pad >= 0), >= n_in + 2 pad
-  auto resize_backward = [&](int C, int n_in, int n_out, int pad = -1, const float* act = nullptr,
-                             const float* mix_w = nullptr, int mix_cout = 0, int pz = 0) {
-    if (pz == 0) pz = n_in + 2 * std::max(pad, 0);
-    const size_t nc = (size_t)N * C;
-    ResizeSources local;
-    const ResizeSources& rs = resize_sources_of(d, n_in, n_out, local);
-    // (the z + y launch takes candidate ranges, as resize_sources gives them, up to kZyTaps long)
-    const bool few = nc * n_out * n_out * n_out <= kFewElements && rs.max_span <= kZyTaps;
-    // (n_in <= n_out: the z pass writes a row's n_in results over the row's own n_out sources)
-    // (single latents too: one launch of ~9 us instead of two of 6 + 5 in the captured loop, C5 0.144 -> 0.1375 ms)
-    if (d->opt_tiled_vjp.load(std::memory_order_relaxed) && (!mix_w || (C == 1 && pad >= 0)) && n_in <= 64 &&
-        n_in <= n_out && n_out <= 1024 && nc < (1u << 24)) {
-      // the three passes in one launch on an LDS-staged block (resize3_backward_tiled_kernel)
-      const int padv = pad >= 0 ? pad : 0;
-      const int max_taps = rs.max_taps;   // longest exact source range (the candidate ranges: resize_row16 takes <= 16)
-      // tile edge and workgroup size: the pair that stages the fewest fine rows over the launch, among those whose
-      // block fits the registers of the prefetch (kBtLoads vectors per thread) and leaves two workgroups on a CU
-      struct Pick { int tc = 0, threads = 0, max_f = 0, wgs = 0; size_t lds = 0; double cost = 0; } best;
-      const bool aligned = (n_out & 3) == 0 && ((uintptr_t)g & 15) == 0 && max_taps <= kBtTaps && rs.max_span <= 16;
-      // the instantiation this call takes: the channels of the 1x1 layer (0: none), the taps that hold the longest range
-      decltype(&resize3_backward_tiled_kernel<0, 6>) kernel = nullptr;
-      dispatch_int_else_last<0, 1, 2, 3, 4>(!mix_w ? 0 : (mix_cout >= 1 && mix_cout <= 3) ? mix_cout : 4, [&](auto co) {
-        dispatch_int_else_last<6, 8, 12>(max_taps <= 6 ? 6 : max_taps <= 8 ? 8 : 12, [&](auto taps) {
-          kernel = &resize3_backward_tiled_kernel<decltype(co)::value, decltype(taps)::value>;
-        });
-      });
-      const void* fn = reinterpret_cast<const void*>(kernel);
-      static std::map<const void*, int> vgpr_waves;   // waves per SIMD the instantiation's registers allow
-      static std::mutex vgpr_mutex;
-      int waves_simd = 0;
-      if (aligned) {
-        std::lock_guard<std::mutex> lock(vgpr_mutex);
-        auto it = vgpr_waves.find(fn);
-        if (it == vgpr_waves.end()) {
-          // (a block above 64 KiB of dynamic LDS needs the kernel's limit raised)
-          hipFuncAttributes fa;
-          int waves = 0;   // (0: the runtime refused; the three-launch form below is taken)
-          if (raise_lds_limit(fn, 150 * 1024) && hipFuncGetAttributes(&fa, fn) == hipSuccess)
-            waves = std::max(1, std::min(8, 512 / ((std::max(fa.numRegs, 1) + 7) / 8 * 8)));
-          it = vgpr_waves.emplace(fn, waves).first;
-        }
-        waves_simd = it->second;
-      }
-      for (int tc = 2; aligned && tc <= std::min(kBtMaxTile, n_in); ++tc) {
-        if (SDFR_BT_TILE > 0 && tc != std::min(SDFR_BT_TILE, n_in)) continue;
-        int max_f = 1;
-        for (int c0 = 0; c0 < n_in; c0 += tc) max_f = std::max(max_f, rs.hi[std::min(c0 + tc, n_in) - 1] - rs.lo[c0] + 1);
-        const int tiles = (n_in + tc - 1) / tc;
-        const size_t lds = ((size_t)max_f * max_f * n_out + (size_t)max_f * tc * n_in) * sizeof(float);
-        if (lds > 150 * 1024) continue;
-        for (int threads = 256; threads <= kBtMaxThreads; threads *= 2) {
-          if (SDFR_BT_THREADS > 0 && threads != SDFR_BT_THREADS) continue;
-          if ((size_t)max_f * max_f * (n_out >> 2) > (size_t)kBtLoads * threads) continue;
-          const size_t oc = tiles == 1 ? n_in + 2 * padv : tc + padv;   // columns of the padded tensor a tile writes, per axis
-          if (oc * oc * pz > (size_t)kBtOut * threads) continue;
-          // workgroups a CU holds (LDS, registers), and the cost: rows staged over the launch, with a charge for a
-          // thin CU (few waves to hide the chain of a workgroup behind)
-          const int wgs = (int)std::min<size_t>((160 * 1024) / (lds + 6 * 1024), (size_t)(4 * waves_simd) / (threads / 64));
-          if (wgs < 1) continue;
-          const double waves = (double)wgs * threads / 64;
-          const double cost = (double)tiles * tiles * max_f * max_f * (1.0 + 4.0 / waves);
-          if (!best.tc || cost < best.cost) { best.tc = tc; best.threads = threads; best.max_f = max_f; best.lds = lds; best.wgs = wgs; best.cost = cost; }
-        }
-      }
-      if (best.tc) {
-        const int tiles = (n_in + best.tc - 1) / best.tc, tt = tiles * tiles;
-        // channel slots: each workgroup walks over `per` channels (tables and addresses once, the next channel's
-        // rows prefetched); `per` so that the workgroups come in whole rounds of what the chip holds
-        const long long cap = 256LL * best.wgs;
-        int slots = 8;
-        double best_t = 0;
-        for (int per = 1; per <= 32; ++per) {
-          const int sl = (int)(((nc + per - 1) / per + 7) / 8 * 8);
-          const long long rounds = ((long long)tt * sl + cap - 1) / cap;
-          const double t = (double)rounds * (per + 0.7);   // (+ the set-up of a workgroup, in channels)
-          if (per == 1 || t < best_t) { best_t = t; slots = sl; }
-        }
-        const float* wm = mix_w ? mix_w : nullptr;
-        const float* zb = d->d_params + d->zero_bias_off;
-        hipLaunchKernelGGL(kernel, dim3((unsigned)(tt * slots)), dim3(best.threads), best.lds, st, g, n_in, n_out,
-                           pad >= 0 ? act : nullptr, padv, pz, best.tc, best.max_f, (int)nc, slots, wm, zb, buf[cur]);
-        g = buf[cur];
-        cur ^= 1;
-        return;
-      }
-    }
-    struct Pass { size_t outer; size_t inner; } passes[3] = {
-        {nc * n_out * n_out, 1},                  // z:  [nc][no][no][no] -> [nc][no][no][ni]
-        {nc * n_out, (size_t)n_in},               // y:  [nc][no][no][ni] -> [nc][no][ni][ni]
-        {nc, (size_t)n_in * n_in}};               // x:  [nc][no][ni][ni] -> [nc][ni][ni][ni]
-    for (int a = 0; a < 3; ++a) {
-      if (a == 0 && few) {
-        const size_t cnt = nc * n_out * n_in * n_in;
-        hipLaunchKernelGGL(resize_zy_backward_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, g,
-                           nc * n_out, n_in, n_out, buf[cur]);
-        a = 1;
-      } else if (a == 2 && mix_w) {
-        const size_t np = (size_t)n_in + 2 * pad;
-        const dim3 gm((unsigned)((np * np * pz + 255) / 256), N);
-        const float* zb = d->d_params + d->zero_bias_off;
-        dispatch_int_else_last<1, 2, 3, 4>(mix_cout, [&](auto co) {
-          hipLaunchKernelGGL((resize_x_backward_mix_pad_kernel<decltype(co)::value>), gm, dim3(256), 0, st, g, C, n_in,
-                             n_out, mix_w, zb, act, pad, pz, buf[cur]);
-        });
-      } else if (a == 2 && pad >= 0) {
-        const size_t np = (size_t)n_in + 2 * pad, cnt = nc * np * np * pz;
-        hipLaunchKernelGGL(resize_x_backward_pad_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, g, nc,
-                           n_in, n_out, act, pad, pz, buf[cur]);
-      } else {
-        const size_t cnt = passes[a].outer * n_in * passes[a].inner;
-        hipLaunchKernelGGL(resize_axis_backward_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st,
-                           g, passes[a].outer, n_in, n_out, passes[a].inner, buf[cur]);
-      }
-      g = buf[cur];
-      cur ^= 1;
-    }
-  };
-  // z-row pitch of the padded tensor layer l's transposed convolution reads: rows 16 bytes apart when the direct
-  // convolution takes it (its 16-byte loads and register prefetch then apply whatever the size; 34 -> 36 floats)
-  const bool ws_aligned = ((uintptr_t)wsp & 15) == 0;
-  auto pitch_of = [&](int l) {
-    const int k = d->conv_k[l], np = out_n[l] + 2 * (k - 1);
-    const bool direct = ws_aligned && !d->conv_swap[l] && !(k == 1 && d->conv_cin[l] <= 4) &&
-                        direct_ok(d->bwd_direct_off[l], np, d->conv_in_size[l], N);
-    return direct ? (np + 3) & ~3 : np;
-  };
-  bool padded = false;  // g already is layer l's padded, masked output gradient (written by the resize above)
-  // few latents: a transposed resize whose output only the transposed convolution of the layer below reads is not
-  // launched -- it is left pending and runs inside that convolution's launch (conv3d_mfma_tresize_kernel)
-  struct {
-    bool on = false;
-    VjpPlan plan;
-    const float *g = nullptr, *act = nullptr, *mix_w = nullptr;
-    int C = 0, n_in = 0, n_out = 0, mix_cout = 0;
-  } pend;
-  // the scaled form: the fused first stage adds the two volumes on load (it is the launch that reads grad_out when the
-  // last layer is a swapped, ReLU-free 1x1x1 one: the `mix` step of the loop below); any other decoder gets them summed
-  // by a launch of its own first
-  bool sg_in_stage = false;
-  if (sg) {
-    const int l = d->n_conv - 1;
-    if (sg->n == 1 && l > 0 && out_n[l] == d->volume && d->conv_swap[l] && !d->conv_relu[l] && d->conv_k[l] == 1 && d->conv_cin[l] <= 4 &&
-        !d->conv_swap[l - 1] && out_n[l - 1] == d->conv_prev[l] && d->conv_cout[l - 1] == d->conv_cin[l] &&
-        d->conv_prev[l] != d->conv_in_size[l] && ((uintptr_t)sg->g2 & 15) == 0)
-      sg_in_stage = vjp_stage_plan(d, l - 1, d->conv_cout[l], d->conv_prev[l], d->conv_in_size[l], d->conv_cin[l], N, 1,
-                                   grad_out, true).ok;
-    if (!sg_in_stage)
-      hipLaunchKernelGGL(scaled_combine_kernel, dim3((unsigned)((vox_in + 255) / 256)), dim3(256), 0, st,
-                         const_cast<float*>(grad_out), sg->g2, sg->n, sg->cnt, sg->weight, vox_in);
-  }
-  int n = d->volume;
-  if (out_n[d->n_conv - 1] != d->volume) {  // final resize
-    const int ni = out_n[d->n_conv - 1];
-    resize_backward(1, ni, d->volume);
-    n = ni;
-  }
-  for (int l = d->n_conv - 1; l >= 0; --l) {
-    const int k = d->conv_k[l], ci_n = d->conv_cin[l], co_n = d->conv_cout[l];
-    const int nin = d->conv_in_size[l], m = out_n[l];
-    const bool swap = d->conv_swap[l] != 0;
-    const int prev = d->conv_prev[l];
-    const int np = swap ? prev : m + 2 * (k - 1);   // size of the tensor the transposed conv reads
-    const int nconv = swap ? prev : nin;            // ... and of the one it produces
-    const int pz = swap ? np : pitch_of(l);         // ... and the floats between its z-rows
-    // 1. ReLU' and zero padding of the output gradient
-    const float* act = d->conv_relu[l] ? tape + (size_t)N * d->tape_conv_off[l] : nullptr;
-    bool conv_done = false;
-    // (does the resize in front of THIS layer fold into the stage of the layer below?  Then this stage's epilogue runs
-    // that resize's z pass on its output rows, and the stage below starts from them.)
-    const bool fuse_below = !swap && prev != nin && l > 0 && !d->conv_swap[l - 1] && out_n[l - 1] == prev &&
-                            d->conv_cout[l - 1] == ci_n;
-    VjpPlan below;
-    if (pend.on) {   // steps 1 and 2 in one launch with the transposed resize above them
-      pend.on = false;
-      if (fuse_below) below = vjp_stage_plan(d, l - 1, ci_n, prev, nin, 0, N, 0, nullptr, false);
-      if (!launch_vjp_stage(d, pend.plan, l, pend.g, pend.C, pend.n_in, pend.n_out, pend.act, pend.mix_w, pend.mix_cout,
-                            below.ok ? prev : 0, buf[cur], N, st, (sg_in_stage && pend.g == grad_out) ? sg : nullptr))
-        return fail(SDFR_E_INVALID, "sdfr_decoder_backward_latent: the fused stage could not be launched");
-      g = buf[cur];
-      cur ^= 1;
-      n = nconv;
-      conv_done = true;
-    } else if (padded) {
-      padded = false;
-    } else if (!swap || act) {
-      const size_t cntp = (size_t)co_n * (swap ? m : np) * (swap ? m : np) * (swap ? m : pz);
-      hipLaunchKernelGGL(pad_mask_kernel, dim3((unsigned)((cntp + 255) / 256), N), dim3(256), 0, st, g, act,
-                         co_n, m, swap ? 0 : k - 1, swap ? m : pz, buf[cur]);
-      g = buf[cur];
-      cur ^= 1;
-    }
-    // (swapped 1x1 layer: forward was conv -> resize, so the resize is transposed first)
-    // single latents: its last pass also runs the transposed 1x1 layer and writes the padded, masked input of
-    // the transposed convolution below (conv1x1 + pad_mask launches saved)
-    const bool mix = swap && !act && k == 1 && ci_n <= 4 && l > 0 && !d->conv_swap[l - 1] && out_n[l - 1] == prev &&
-                     d->conv_cout[l - 1] == ci_n && prev != nin &&
-                     ((size_t)N * co_n * nin * nin * nin <= kFewElements || co_n == 1);
-    if (mix) {
-      const float* act_below = d->conv_relu[l - 1] ? tape + (size_t)N * d->tape_conv_off[l - 1] : nullptr;
-      pend.plan = vjp_stage_plan(d, l - 1, co_n, prev, nin, ci_n, N, 1, g, g == grad_out);
-      if (sg && sg->n == 1 && g == grad_out && pend.plan.ok != sg_in_stage)
-        return fail(SDFR_E_INVALID, "sdfr_decoder_backward_latent: the scaled form's first stage changed its mind (internal)");
-      if (pend.plan.ok) {
-        pend.on = true;
-        pend.g = g; pend.act = act_below; pend.mix_w = d->d_params + d->bwd_w_off[l];
-        pend.C = co_n; pend.n_in = prev; pend.n_out = nin; pend.mix_cout = ci_n;
-        n = prev;
-        continue;
-      }
-      resize_backward(co_n, prev, nin, d->conv_k[l - 1] - 1,
-                      d->conv_relu[l - 1] ? tape + (size_t)N * d->tape_conv_off[l - 1] : nullptr,
-                      d->d_params + d->bwd_w_off[l], ci_n, pitch_of(l - 1));
-      padded = true;
-      n = prev;
-      continue;
-    }
-    if (swap) resize_backward(co_n, prev, nin);
-    // 2. data gradient = valid conv (kernel k) of the padded tensor with the flipped weights
-    const int kpad = d->bwd_kpad[l];
-    if (conv_done) {
-      // (launched above)
-    } else if (k == 1 && ci_n <= 4) {
-      // transposed 1x1 layer: element-wise, like its forward (the MFMA form: 207 us per 256 latents, this: ~35)
-      const int voxn = np * np * np;
-      const dim3 g1((voxn + 255) / 256, N);
-      const float* wb = d->d_params + d->bwd_w_off[l];
-      const float* zb = d->d_params + d->zero_bias_off;
-      dispatch_int_else_last<1, 2, 3, 4>(ci_n, [&](auto ci) {
-        hipLaunchKernelGGL((conv1x1_kernel<decltype(ci)::value>), g1, dim3(256), 0, st, g, wb, zb, co_n, voxn, 0,
-                           buf[cur]);
-      });
-    } else if (!swap && launch_direct(d, d->bwd_direct_off[l], g, d->d_params + d->zero_bias_off, buf[cur], co_n, ci_n, np,
-                               pz, nconv, 0, N, st)) {
-      // (batched: direct VALU convolution)
-    } else if (pz != np) {
-      return fail(SDFR_E_INVALID, "sdfr_decoder_backward_latent: padded rows without the direct convolution (internal)");
-    } else {
-      const sdfr_decoder::ZPlan& zp = d->bwd_z[l];
-      const int split = use_split_k(false, (nconv * nconv * nconv + 15) / 16, (ci_n + 15) / 16, N, kpad);
-      const bool zgrp = !split && zp.zg > 1 && !swap &&
-                        (long long)nconv * nconv * (nconv / zp.zg) * N >= kZGroupMinRows;
-      const int kp = zgrp ? zp.kpad : kpad, rows = nconv * nconv * (nconv / (zgrp ? zp.zg : 1));
-      const int nt = (rows + 15) / 16;
-      launch_mfma(g, d->d_params + (zgrp ? zp.w_off : d->bwd_w_off[l]),
-                  reinterpret_cast<const int*>(d->d_params + (zgrp ? zp.tab_off : d->bwd_tab_off[l])),
-                  d->d_params + d->zero_bias_off, buf[cur], co_n, ci_n, np, nconv, kp, 0, nt,
-                  zgrp ? 1 : (ci_n + 15) / 16, zgrp ? zp.zg : 1, split, N, st);
-    }
-    if (!conv_done) {
-      g = buf[cur];
-      cur ^= 1;
-    }
-    n = nconv;
-    // 3. the resize in front of this layer, if any
-    if (!swap && prev != nin) {
-      // the layer below (l - 1) produced this tensor: if its transposed convolution is of the padded kind,
-      // the last resize pass writes its input directly
-      const bool fuse = l > 0 && !d->conv_swap[l - 1] && out_n[l - 1] == prev && d->conv_cout[l - 1] == ci_n;
-      if (fuse) pend.plan = below.ok ? below : vjp_stage_plan(d, l - 1, ci_n, prev, nin, 0, N, 1, g, g == grad_out);
-      if (fuse && pend.plan.ok) {
-        pend.on = true;
-        pend.g = g; pend.act = d->conv_relu[l - 1] ? tape + (size_t)N * d->tape_conv_off[l - 1] : nullptr;
-        pend.mix_w = nullptr;
-        pend.C = ci_n; pend.n_in = prev; pend.n_out = nin; pend.mix_cout = 0;
-      } else if (fuse) {
-        resize_backward(ci_n, prev, nin, d->conv_k[l - 1] - 1,
-                        d->conv_relu[l - 1] ? tape + (size_t)N * d->tape_conv_off[l - 1] : nullptr, nullptr, 0,
-                        pitch_of(l - 1));
-        padded = true;
-      } else {
-        resize_backward(ci_n, prev, nin);
-      }
-      n = prev;
-    }
-  }
-  // g is now the gradient w.r.t. the (ReLU'd) output of the Linear stack
-  FcDesc fd;
-  decoder_fc_desc(d, &fd, nullptr, nullptr);
-  // g == buf[cur ^ 1] here (every step above ends with g = buf[cur]; cur ^= 1): the transposed wide layer
-  // must write the FREE buffer -- other workgroups still read g while this one stores.
-  float* t_mid = buf[cur];
-  {
-    const int win = fd.width[d->n_fc - 1], wout = fd.width[d->n_fc];
-    const float* act_fc = tape + (size_t)N * d->tape_fc_off;
-    const float* wl = d->d_params + fd.w_off[d->n_fc - 1];
-    constexpr int kIb = 5, kSb = 4;
-    if (N >= 32 && (wout & 3) == 0 && (((uintptr_t)wl | (uintptr_t)g | (uintptr_t)act_fc) & 15) == 0)   // batches
-      hipLaunchKernelGGL((fc_last_backward_batch_kernel<kIb, kSb>), dim3((win + kIb - 1) / kIb, (N + kSb - 1) / kSb),
-                         dim3(kFcBlock), 0, st, d->d_params, fd, g, act_fc, N, t_mid);
-    else
-      hipLaunchKernelGGL(fc_last_backward_kernel, dim3(win, N), dim3(kFcBlock), 0, st, d->d_params, fd, g, act_fc,
-                         t_mid, sg ? const_cast<float*>(grad_out) : (float*)nullptr, sg ? sg->g2 : (float*)nullptr,
-                         (int)(vox_in / 4), sg ? sg->n : 0);
-  }
-  if (t_mid_out) *t_mid_out = t_mid;
-  else if (decoder_fc_one_wave(d, fd))
-    hipLaunchKernelGGL(fc_stack_backward_wave_kernel, dim3(N), dim3(64), 0, st, d->d_params, fd, z, t_mid, g_z);
-  else hipLaunchKernelGGL(fc_stack_backward_kernel, dim3(N), dim3(kFcBlock), 0, st, d->d_params, fd, z, t_mid, g_z);
+  Facts f;
+  f.deferred = t_mid_out != nullptr; f.views = sg ? sg->n : 0;
+  f.tape_mod = mod16(tape); f.grad_mod = mod16(grad_out);
+  const Plan plan = make_plan(d, N, f, true);
+  if (plan.error) return fail(SDFR_E_INVALID, "sdfr_decoder_backward_latent: %s", plan.error);
+  Tensors t{};
+  t.z = z; t.tape = const_cast<float*>(tape); t.grad = const_cast<float*>(grad_out); t.g_z = g_z; t.sg = sg;
+  t.buf[0] = aligned256(workspace); t.buf[1] = t.buf[0] + (size_t)N * d->max_bwd;
+  launch_plan(d, plan, true, t, N, (hipStream_t)stream);
+  if (t_mid_out) *t_mid_out = t.buf[plan.t_mid.i];
   SDFR_HIP_TRY(hipGetLastError());
-  (void)n;
   return 0;
 }
 }  // namespace
+
+extern "C" int sdfr_decoder_launch_plan(const sdfr_decoder* d, int pass, int N, int flags, int* steps, int capacity) {
+  if (!d) return fail(SDFR_E_NULL, "sdfr_decoder_launch_plan: decoder is NULL");
+  const bool vjp = pass == SDFR_DECODER_PASS_VJP;
+  if (!vjp && pass != SDFR_DECODER_PASS_FORWARD) return fail(SDFR_E_INVALID, "sdfr_decoder_launch_plan: unknown pass %d", pass);
+  const int both_stages = SDFR_DECODER_PLAN_STAGE_1 | SDFR_DECODER_PLAN_STAGE_2;
+  const int both_scaled = SDFR_DECODER_PLAN_SCALED_1 | SDFR_DECODER_PLAN_SCALED_N;
+  const int known = vjp ? SDFR_DECODER_PLAN_DEFERRED | both_scaled : SDFR_DECODER_PLAN_TAPE | SDFR_DECODER_PLAN_CLAMP | both_stages;
+  if ((flags & ~known) || (flags & both_stages) == both_stages || (flags & both_scaled) == both_scaled)
+    return fail(SDFR_E_INVALID, "sdfr_decoder_launch_plan: flags %d are not this pass's", flags);
+  if (N < 0 || N > 65535 || capacity < 0 || (capacity > 0 && !steps) || ((flags & both_scaled) && N > 1))
+    return fail(SDFR_E_INVALID, "sdfr_decoder_launch_plan: N=%d, capacity=%d", N, capacity);
+  if (N == 0) return 0;
+  SDFR_HIP_TRY(hipSetDevice(d->device));   // (the planners ask the runtime about kernels, once each)
+  Facts f;   // (every pointer of the caller's 256-byte aligned)
+  f.tape = (flags & (SDFR_DECODER_PLAN_TAPE | both_stages)) != 0;   // (the stages meet in the tape)
+  f.clamp = (flags & SDFR_DECODER_PLAN_CLAMP) && d->tsdf > 0.0f;
+  f.stages = (flags & SDFR_DECODER_PLAN_STAGE_1) ? 1 : (flags & SDFR_DECODER_PLAN_STAGE_2) ? 2 : 3;
+  f.deferred = (flags & (SDFR_DECODER_PLAN_DEFERRED | both_scaled)) != 0;
+  f.views = (flags & SDFR_DECODER_PLAN_SCALED_1) ? 1 : (flags & SDFR_DECODER_PLAN_SCALED_N) ? 2 : 0;
+  const Plan plan = make_plan(d, N, f, vjp);
+  if (plan.error) return fail(SDFR_E_INVALID, "sdfr_decoder_launch_plan: %s", plan.error);
+  for (int i = 0; i < std::min(plan.n, capacity); ++i) steps[i] = plan.s[i].form;
+  return plan.n;
+}
 
 extern "C" int sdfr_decoder_backward_latent(const sdfr_decoder* d, const float* z, const float* tape,
                                             const float* grad_out, int N, float* g_z,

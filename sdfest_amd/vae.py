@@ -125,6 +125,29 @@ class SDFDecoder:
             _lib.check(old, "sdfr_decoder_set_option")
         return old
 
+    STEPS = {code: name[len("SDFR_DECODER_STEP_"):].lower()                  # include/sdfr.h
+             for name, code in _lib.ABI.items() if name.startswith("SDFR_DECODER_STEP_")}
+
+    def launch_plan(self, N: int, vjp: bool = False, tape: bool = False, stages: int = 3, enforce_tsdf: bool = False,
+                    deferred: bool = False, scaled_views: int = 0) -> list:
+        """The launches a forward (or, ``vjp=True``, a VJP) over N latents would make on this decoder, in order, as step
+        names (``sdfr_decoder_launch_plan``: the planner the calls themselves launch from, asked for 256-byte aligned
+        buffers; nothing is launched).  ``tape``, ``stages``, ``enforce_tsdf`` describe a forward; ``deferred`` and
+        ``scaled_views`` (the scaled form's view count) a VJP."""
+        A = _lib.ABI
+        if vjp:
+            flags = (A["SDFR_DECODER_PLAN_DEFERRED"] if deferred else 0) | (
+                0 if not scaled_views else A["SDFR_DECODER_PLAN_SCALED_1"] if scaled_views == 1 else A["SDFR_DECODER_PLAN_SCALED_N"])
+        else:
+            flags = (A["SDFR_DECODER_PLAN_TAPE"] if tape else 0) | (A["SDFR_DECODER_PLAN_CLAMP"] if enforce_tsdf else 0) | {
+                1: A["SDFR_DECODER_PLAN_STAGE_1"], 2: A["SDFR_DECODER_PLAN_STAGE_2"], 3: 0}[stages]
+        steps = (ctypes.c_int * 128)()
+        n = self._L.sdfr_decoder_launch_plan(self._h, A["SDFR_DECODER_PASS_VJP" if vjp else "SDFR_DECODER_PASS_FORWARD"],
+                                             int(N), flags, steps, len(steps))
+        if n < 0:
+            _lib.check(n, "sdfr_decoder_launch_plan")
+        return [self.STEPS[c] for c in steps[:n]]
+
     def _scratch(self, need: int) -> torch.Tensor:
         """Scratch of the calls on the CURRENT stream, grown on demand -- one buffer per stream, like the renderer's
         (``differentiable_renderer._workspace``): two streams driving the same decoder (the view generator decodes

@@ -259,12 +259,19 @@ def test_decoder_latent_gradient_wide_hidden_layer_vs_torch():
 
 
 def test_batched_decoder_kernels_equal_single_decodes(mug):
-    """A batch large enough for every batched kernel (direct convolutions, tiled resizes, z-grouped
-    MFMA) against one-at-a-time decodes, which take the latency-oriented kernels: forward and VJP."""
+    """A batch large enough for the batched kernels (direct convolutions, tiled resizes, the MFMA convolution with its
+    input resident in LDS) against one-at-a-time decodes, which take the latency-oriented kernels: forward and VJP.
+    (The z-grouped MFMA is not among them: the mug decoder's first layer, the only one left to the matrix cores at
+    N = 130, takes the resident form.)"""
     from sdfest_amd import SDFDecoder
     d, wts = mug
     dec = SDFDecoder.from_config(mug_config(d), wts)
     N = 130
+    # the batch takes the batched forms the docstring names, a single decode none of them
+    batched = {"direct", "resize_tiled", "mfma_resident"}
+    plans = {n: set(dec.launch_plan(n, tape=True)) | set(dec.launch_plan(n, vjp=True)) for n in (N, 1)}
+    assert batched <= plans[N] and "mfma_z_grouped" not in plans[N], plans[N]
+    assert not (batched | {"mfma_z_grouped"}) & plans[1], plans[1]
     rng = np.random.default_rng(11)
     z_np = np.concatenate([d["z"], rng.normal(size=(N - len(d["z"]), 8)).astype(np.float32)])
     G = torch.tensor(decoder_probe_G(), device="cuda")
@@ -344,6 +351,11 @@ def test_tiled_transposed_resize_is_bitwise_the_three_launches(mug):
         for on in (1, 0):
             old = dec.set_option("tiled_vjp", on)
             try:
+                plan = dec.launch_plan(N, vjp=True)
+                if not on:
+                    assert "resize_t_tiled" not in plan, (name, N, plan)
+                elif name == "mug" and N in (70, 1):
+                    assert "resize_t_tiled" in plan, (name, N, plan)
                 z = torch.tensor(z_np, device="cuda", requires_grad=True)
                 dec.decode(z).backward(G)
                 torch.cuda.synchronize()
@@ -394,6 +406,11 @@ def test_resize_folded_into_the_patch_load_is_bitwise_the_two_launches(mug):
         for on in (2, 0):      # folded wherever the form exists / never (the default folds fine sizes up to 16)
             old = dec.set_option("fused_resize", on)
             try:
+                plan = dec.launch_plan(N, tape=True)
+                if not on:
+                    assert "direct_up" not in plan, (name, N, plan)
+                elif name == "mug" and N == 140:
+                    assert "direct_up" in plan, (name, N, plan)
                 z = torch.tensor(z_np, device="cuda", requires_grad=True)
                 o = dec.decode(z)
                 o.backward(G)
@@ -437,6 +454,12 @@ def test_one_wave_linear_backward_is_bitwise_the_workgroup_form(mug):
         for on in (1, 0):
             old = dec.set_option("fc_one_wave", on)
             try:
+                plan = dec.launch_plan(N, tape=True) + dec.launch_plan(N, vjp=True)
+                wave = {"fc_stack_t_wave", "fc_stack_narrow", "fc_stack_batch_narrow"} & set(plan)
+                if not on or name == "70 wide":
+                    assert not wave, (name, N, on, plan)
+                elif name == "mug":
+                    assert "fc_stack_t_wave" in wave, (name, N, plan)
                 z = torch.tensor(z_np, device="cuda", requires_grad=True)
                 o = dec.decode(z)
                 o.backward(G)
@@ -513,6 +536,13 @@ def test_single_latent_fused_pairs_are_bitwise_the_unfused_launches(mug):
         for bits in (0, 1, 2, 4, 12, 15):
             old = dec.set_option("fused_single", bits)
             try:
+                plan = set(dec.launch_plan(N) + dec.launch_plan(N, tape=True) + dec.launch_plan(N, vjp=True))
+                forms = {"mfma_up": 1, "fc_conv": 2, "vjp_stage": 4 | 8}
+                for form, bit in forms.items():
+                    if not bits & bit:
+                        assert form not in plan, (name, N, bits, form)
+                if name == "mug" and N == 1 and bits == 15:
+                    assert set(forms) <= plan, (name, bits, plan)
                 z = torch.tensor(z_np, device="cuda", requires_grad=True)
                 o = dec.decode(z)
                 o.backward(G)
@@ -530,3 +560,41 @@ def test_single_latent_fused_pairs_are_bitwise_the_unfused_launches(mug):
             assert torch.equal(o, ref[0]), (name, N, bits, "output", (o - ref[0]).abs().max().item())
             assert torch.equal(plain, ref[0]), (name, N, bits, "output without a tape", (plain - ref[0]).abs().max().item())
             assert torch.equal(g, ref[1]), (name, N, bits, "latent gradient", (g - ref[1]).abs().max().item())
+
+
+def test_launch_plan_query():
+    """sdfr_decoder_launch_plan on the smallest decoder of this file at N = 1 and 2: the same answer twice, a short
+    `steps` array, the error codes, N = 0, and the stages of a forward (stage 1 + stage 2 launch what the whole forward
+    launches, unless that one folds the Linear stack into the first convolution)."""
+    import ctypes
+    from sdfest_amd import SDFDecoder, _lib
+    rng = np.random.default_rng(3)
+    case = dict(volume=16, latent=3, fc=[{"out": 7}, {"out": 3 * 6 ** 3}],
+                conv=[dict(in_size=6, in_channels=3, out_channels=20, kernel_size=3, relu=True),
+                      dict(in_size=12, in_channels=20, out_channels=2, kernel_size=3, relu=False),
+                      dict(in_size=16, in_channels=2, out_channels=1, kernel_size=1, relu=True)])
+    cfg = {"latent_size": 3, "tsdf": False, "sdf_size": 16, "decoder": {"fc_layers": case["fc"], "conv_layers": case["conv"]}}
+    dec = SDFDecoder.from_config(cfg, _random_state(rng, case), sdf_size=16)
+    L, A = dec._L, _lib.ABI
+    fwd, vjp = A["SDFR_DECODER_PASS_FORWARD"], A["SDFR_DECODER_PASS_VJP"]
+    for N in (1, 2):
+        for kw in (dict(), dict(tape=True), dict(vjp=True), dict(vjp=True, deferred=True)):
+            plan = dec.launch_plan(N, **kw)
+            assert plan and plan == dec.launch_plan(N, **kw), (N, kw)
+        whole = dec.launch_plan(N, tape=True)
+        if "fc_conv" not in whole:
+            assert dec.launch_plan(N, tape=True, stages=1) + dec.launch_plan(N, tape=True, stages=2) == whole, N
+        assert dec.launch_plan(N, vjp=True)[:-1] == dec.launch_plan(N, vjp=True, deferred=True), N
+        # a short array: the full count, and only `capacity` entries written
+        n = len(whole)
+        steps = (ctypes.c_int * n)(*([-7] * n))
+        assert n >= 3 and L.sdfr_decoder_launch_plan(dec._h, fwd, N, A["SDFR_DECODER_PLAN_TAPE"], steps, 2) == n
+        assert [dec.STEPS[c] for c in steps[:2]] == whole[:2] and list(steps[2:]) == [-7] * (n - 2)
+        assert L.sdfr_decoder_launch_plan(dec._h, fwd, N, A["SDFR_DECODER_PLAN_TAPE"], None, 0) == n
+    steps = (ctypes.c_int * 64)()
+    assert L.sdfr_decoder_launch_plan(None, fwd, 1, 0, steps, 64) == A["SDFR_E_NULL"]
+    assert L.sdfr_decoder_launch_plan(dec._h, 2, 1, 0, steps, 64) == A["SDFR_E_INVALID"]
+    assert L.sdfr_decoder_launch_plan(dec._h, fwd, 1, 128, steps, 64) == A["SDFR_E_INVALID"]
+    assert L.sdfr_decoder_launch_plan(dec._h, fwd, 1, A["SDFR_DECODER_PLAN_DEFERRED"], steps, 64) == A["SDFR_E_INVALID"]
+    assert L.sdfr_decoder_launch_plan(dec._h, vjp, 1, A["SDFR_DECODER_PLAN_TAPE"], steps, 64) == A["SDFR_E_INVALID"]
+    assert L.sdfr_decoder_launch_plan(dec._h, fwd, 0, 0, steps, 64) == 0 and L.sdfr_decoder_launch_plan(dec._h, vjp, 0, 0, steps, 64) == 0
