@@ -89,11 +89,13 @@
  *  13. [unstable] FRAME ANNOTATION: the visibility mask of an annotated RGB-D frame (AnnotatedRedwoodDataset)
  *        sdfr_visible_mask
  *  14. [unstable] POSE INFORMATION: the Gauss-Newton normal matrix of the depth residual (SDFPipeline.pose_uncertainty)
- *        sdfr_render_information[_workspace_bytes]
+ *        sdfr_render_information[_workspace_bytes]; jointly with the latent: sdfr_render_information_shape[_workspace_bytes]
  *  15. [unstable] BOXES: the oriented box of an estimate without its mesh, and the exact 3D IoU of oriented boxes
  *        sdfr_sdf_bounds, sdfr_box_iou
  *  16. [unstable] AVERAGE PRECISION: pose errors of pairs, detection matching and the AP integral (the evaluation's mAP)
  *        sdfr_pose_pair_errors, sdfr_ap_match, sdfr_ap_integrate
+ *  17. [unstable] DECODER JVP: the Jacobian of the decoded volume w.r.t. the latent (SDFPipeline.shape_uncertainty)
+ *        sdfr_decoder_jvp[_workspace_bytes], sdfr_sdf_std
  * (Within the file the groups follow the order in which the reference's code runs; every declaration carries the
  * reference file:line it replaces.)
  */
@@ -1550,6 +1552,34 @@ SDFR_API int sdfr_render_information(const float* depth, const float* target, co
                                      float fy, float inlier_threshold, double* gram, void* workspace,
                                      size_t workspace_bytes, int device, void* stream);
 
+/* ---- the same jointly with the latent: per view the F x F Gram matrix, F = 10 + T, of f = (d0 .. d7, s0 .. s_{T-1}, r, 1)
+ * over the same included pixels -- d, r, the inclusion rule and the tile cull are sdfr_render_information's, instruction
+ * for instruction --, with
+ *     s_t = d depth / d (latent direction t) = f * trilerp(jac[.][t]) at the pixel's hit cell with the pixel's offsets,
+ *           f = scale |d.z|: the EXACT d depth / d SDF weights of sdfr_render_backward (SDFR_SDF_GRAD_EXACT) contracted
+ *           with the tangent volumes.  SDFR_SDF_GRAD_CUDA_COMPAT is a compatibility weighting (the reference's corner
+ *           permutation), not a derivative, and has no counterpart here.
+ *   jac     [R^3][Tp] floats, voxel-major as sdfr_decoder_jvp (group 17) writes it: the T tangent values of a grid corner
+ *           in one row of Tp floats (Tp a multiple of 4, Tp >= T; columns T .. Tp - 1 are not read into the result);
+ *           16-byte aligned.  jac_view_stride = 0: the views share it; otherwise >= R^3 Tp floats (a multiple of 4) from
+ *           view to view -- with several views per object, pass the views' own pointers through the stride of a
+ *           repeated buffer, as sdf_view_stride
+ *   gram    [B][F][F] doubles, overwritten: [:8][:8] the pose block (what sdfr_render_information gives, up to the
+ *           rounding of a different summation block), [8:8+T][8:8+T] the latent block, [:8+T][8+T] = J^T r,
+ *           [8+T][8+T] = sum r^2, [9+T][9+T] the exact count; exactly symmetric; all zeros for a view without an included
+ *           pixel
+ * 1 <= T <= 22: F <= 32 is one 32 x 32 block of the matrix cores.  Everything else -- the two launches, the fixed-order
+ * sums, "a view does not depend on its batch", "the workspace may hold anything on entry", the limits and the argument
+ * errors (all SDFR_E_INVALID before anything touches the GPU; T = 23, a Tp that is no multiple of 4 or below T, a
+ * misaligned jac) -- as sdfr_render_information. */
+SDFR_API size_t sdfr_render_information_shape_workspace_bytes(int B, int W, int H, int T);
+SDFR_API int sdfr_render_information_shape(const float* depth, const float* target, const float* sdf, int R,
+                                           long long sdf_view_stride, const float* jac, int Tp, int T,
+                                           long long jac_view_stride, const float* pos, const float* quat,
+                                           const float* inv_scale, int B, int W, int H, float cx, float cy, float fx,
+                                           float fy, float inlier_threshold, double* gram, void* workspace,
+                                           size_t workspace_bytes, int device, void* stream);
+
 /* ==== 15. BOXES =============================================================================== */
 /* ---- the bounds of a grid's iso-surface: what amin / amax of sdfr_mesh_emit's vertices give, without counting,
  * scanning or emitting a mesh.  Grids, `complete`, `level`, the inside rule (v < level), the axis order and the vertex
@@ -1671,6 +1701,42 @@ SDFR_API int sdfr_ap_match(const double* table, long long n_pairs, const int* pr
  * its terms in walk order and one xor butterfly adds the lanes.  0 <= T <= 2^20, T C <= 2^31 - 1. */
 SDFR_API int sdfr_ap_integrate(const unsigned char* matched, int T, int P, const int* order, const int* class_offset,
                                const int* n_gt, int C, double* ap, int device, void* stream);
+
+/* ==== 17. DECODER JVP ========================================================================= */
+/* ---- the forward-mode derivative of sdfr_decoder_forward w.r.t. the latent: d SDF / d z is volume^3 x latent, that is
+ * `latent` tangent volumes, which no number of VJP calls below volume^3 yields.  The decoder is Linear, ReLU, trilinear
+ * resize and Conv3d; its derivative along a direction is the same chain WITHOUT the biases and with every ReLU replaced
+ * by the mask [activation > 0] of the primal run (a ReLU on the last layer included).  The N T directions of a call are
+ * rows of a batch through that network, row (n, t) masked by latent n.
+ *   z        [N][latent]: the latents of the forward (the small leading Linear layers are not on the tape; they are
+ *            recomputed with the forward's own fmaf chains, as sdfr_decoder_backward_latent does)
+ *   tape     what a preceding sdfr_decoder_forward(decoder, z, N, ..., tape, ...) wrote; the forward is not touched
+ *   out      that forward's output [N][volume^3]; read only with enforce_tsdf on a decoder that truncates (NULL otherwise):
+ *            the result is zero where out sits on the clamp, !(|out| < tsdf)
+ *   tangents [N][T][latent]; NULL: the identity basis (T == latent), row t = d / d z_t
+ *   jac      [N][volume^3][Tp] floats, overwritten, VOXEL-major: jac[n][voxel][t] is the derivative of latent n's voxel
+ *            along tangents[n][t]; Tp = T rounded up to a multiple of 4, columns T .. Tp - 1 are written as zeros (the
+ *            tangents of a grid corner are Tp / 4 16-byte loads for sdfr_render_information_shape).  16-byte aligned.
+ *            The layout is written by the last step itself (the final resize, or the last convolution), no transpose.
+ * fp32 fmaf chains in a fixed order (channels, then taps ascending), no atomics: the same bits on every call, and
+ * row (n, .) does not depend on the other latents of the call.  The swapped 1x1x1 layer and the resizes are linear and
+ * pass unchanged.  Kernels only on `stream`, no allocation, no host synchronisation.  1 <= T <= 22 (group 14),
+ * N T <= 65535.  Errors before anything touches the GPU: SDFR_E_NULL (a pointer), SDFR_E_INVALID (N, T, a NULL
+ * `tangents` with T != latent, a misaligned jac), SDFR_E_WORKSPACE; _workspace_bytes answers 0 for what the call refuses. */
+SDFR_API size_t sdfr_decoder_jvp_workspace_bytes(const sdfr_decoder* decoder, int N, int T);
+SDFR_API int sdfr_decoder_jvp(const sdfr_decoder* decoder, const float* z, const float* tape,
+                              const float* out /* NULL unless enforce_tsdf */,
+                              const float* tangents /* nullable: the identity basis */, int N, int T, int enforce_tsdf,
+                              float* jac, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- the standard deviation of every voxel of K decoded volumes under a covariance of their latents (or of any T
+ * directions): out[k][voxel] = sqrt(max(0, j^T S_k j)), j = jac[k][voxel][:T].
+ *   jac        [K][voxels][Tp] as above; covariance [K][T][T] doubles; out [K][voxels] floats, overwritten
+ * One thread per voxel, the covariance in LDS, fp64 sums in a fixed order.  1 <= K <= 65535, 1 <= voxels <= 2^31,
+ * 1 <= T <= 22, Tp >= T a multiple of 4, jac 16-byte and covariance 8-byte aligned; every argument error is
+ * SDFR_E_INVALID before anything touches the GPU. */
+SDFR_API int sdfr_sdf_std(const float* jac, int K, long long voxels, int Tp, int T, const double* covariance,
+                          float* out, int device, void* stream);
 
 #ifdef __cplusplus
 }

@@ -37,6 +37,7 @@
 #include "common.hpp"
 #include "decoder_fc.hpp"
 #include "decoder_host.hpp"
+#include "decoder_jvp.hpp"
 
 struct sdfr_decoder {
   int device;
@@ -2115,6 +2116,22 @@ void decoder_fc_desc(const sdfr_decoder* d, FcDesc* out, const float** d_params,
   }
   if (d_params) *d_params = d->d_params;
   if (tape_fc_off) *tape_fc_off = d->tape_fc_off;
+}
+// the same for the forward-mode JVP (decoder_jvp.hip): the layers and where their weights and tape slots lie
+void decoder_jvp_desc(const sdfr_decoder* d, JvpDesc* out) {
+  out->device = d->device; out->latent = d->latent; out->n_conv = d->n_conv; out->volume = d->volume;
+  out->tsdf = d->tsdf;
+  for (int l = 0; l < d->n_conv; ++l) {
+    out->in_size[l] = d->conv_in_size[l]; out->cin[l] = d->conv_cin[l]; out->cout[l] = d->conv_cout[l];
+    out->k[l] = d->conv_k[l]; out->relu[l] = d->conv_relu[l]; out->swap[l] = d->conv_swap[l];
+    out->prev[l] = d->conv_prev[l]; out->kpad[l] = d->conv_kpad[l];
+    out->w_off[l] = (long long)d->conv_w_off[l];
+    out->tape_conv_off[l] = (long long)d->tape_conv_off[l];
+  }
+  out->tape_fc_off = (long long)d->tape_fc_off;
+  out->max_act = (long long)d->max_act;
+  out->params = d->d_params;
+  decoder_fc_desc(d, &out->fc, nullptr, nullptr);
 }
 }  // namespace sdfr
 

@@ -646,7 +646,53 @@ class SDFPipeline:
             depth = forward_raw(sdf, pos_c, quat_c, inv_scale, W, H, cx, cy, fx, fy, self.config["threshold"])
         return dict(K=K, V=V, depth=depth, target=loop.target.reshape(K * V, H, W), sdf=sdf, position=pos_c,
                     orientation=quat_c, inv_scale=inv_scale,
-                    camera_orientations=cam_quat[None].expand(K, V, 4).reshape(K * V, 4))
+                    camera_orientations=cam_quat[None].expand(K, V, 4).reshape(K * V, 4), latent=latent.contiguous())
+
+    def _shape_uncertainty_views(self) -> Dict:
+        """``_uncertainty_views`` plus the decoder's Jacobians at the K final latents: ``jac`` (K, D^3, Tp) as
+        ``SDFDecoder.jvp`` writes it (the identity basis: T = the latent size) and ``jacobian``, what the K V views
+        read -- the one buffer where a single object's views share it, else a copy per view, object-major like ``sdf``"""
+        v = self._uncertainty_views()
+        with torch.no_grad():
+            _, jac = self.vae.decode_jvp(v["latent"])
+        K, V = v["K"], v["V"]
+        v["jac"], v["T"] = jac, int(v["latent"].shape[1])
+        v["jacobian"] = jac[0] if K == 1 else jac.repeat_interleave(V, dim=0) if V > 1 else jac
+        return v
+
+    def shape_uncertainty(self, inlier_threshold=None, rcond: float = 1e-6, depth_sigma: Optional[float] = None,
+                          latent_prior: float = 1.0, sdf_std: bool = False):
+        """``pose_uncertainty`` without the assumption that the decoded shape is exact: the loop optimises the latent
+        together with the pose and the two trade against each other (a mug seen from one side fits nearly as well a
+        little larger and nearer), so the pose covariance conditioned on the shape is too small.  Valid after the same
+        calls, with the same ``RuntimeError`` / ``NotImplementedError`` cases.
+
+        The K final latents are decoded together with their Jacobian d SDF / d latent (``SDFVAE.decode_jvp``), ONE
+        ``sdfr_render_information_shape`` call over all K V views gives every view's joint Gram matrix over pose and
+        latent, and each object's views are added in the world tangent (the latent is frame-free).  Returns
+        ``uncertainty.ShapePoseUncertainty`` with leading dimension K: the joint information and covariance, the pose
+        covariance marginalised over the latent with position_std / rotation_std_deg / scale_rel_std from it,
+        ``conditional`` (what ``pose_uncertainty`` reports), latent_std, rank, sigma2, unobserved.
+        latent_prior: the weight of the VAE's N(0, I) prior on the latent (``uncertainty.shape_pose_covariance``; 0: none).
+        sdf_std=True: also ``sdf_std`` (K, D, D, D), the standard deviation of every voxel of the decoded volume under
+        the latent's covariance -- which part of the surface the observation pins down.
+        Reads the loop's buffers only: a following call returns what it would have returned."""
+        from . import uncertainty as U
+        thr = 0.0 if inlier_threshold is None else float(
+            self._relative_inlier_threshold if inlier_threshold is True else inlier_threshold)
+        with torch.no_grad():
+            v = self._shape_uncertainty_views()
+            K, V, T = v["K"], v["V"], v["T"]
+            gram = U.render_information(v["depth"], v["target"], v["sdf"], v["position"], v["orientation"],
+                                        v["inv_scale"], self.cam, thr, jacobian=v["jacobian"], tangents=T)
+            info = U.joint_tangent_information(gram, v["orientation"], v["inv_scale"], v["camera_orientations"])
+            per_object = lambda t: t.reshape((K, V) + tuple(t.shape[1:])).sum(dim=1)
+            rec = U.shape_pose_covariance(per_object(info), per_object(gram[:, 8 + T, 8 + T]),
+                                          per_object(gram[:, 9 + T, 9 + T]), latent_prior=latent_prior, rcond=rcond,
+                                          depth_sigma=depth_sigma)
+            if sdf_std:
+                rec.sdf_std = U.sdf_std(v["jac"], rec.covariance[:, 7:, 7:], tangents=T)   # (NaN where the row is)
+            return rec
 
     def best_estimates(self):
         """K entries (ratio, 1-based iteration, (position, orientation, scale, latent)), one per object: the parameters

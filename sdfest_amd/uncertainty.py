@@ -10,6 +10,13 @@ Local parameters (the *tangent*): position (3, metres), a world-frame rotation v
 ``q <- exp(w / 2) (x) q``, quaternions scalar-last) and log-scale (1).  A direction of that space the depth image does
 not constrain -- the spin of a bottle about its axis, any rotation of a sphere -- shows as a (numerically) zero
 eigenvalue: ``pose_covariance`` reports it through ``rank`` and ``unobserved`` instead of inverting it.
+
+Shape.  The loop optimises the latent together with the pose and the two trade against each other, so a pose
+covariance conditioned on the decoded shape is too small.  With the decoder's Jacobian (``SDFDecoder.jvp``) the same
+call forms the JOINT Gram matrix over pose and T latent directions (``sdfr_render_information_shape``);
+``joint_tangent_information`` and ``shape_pose_covariance`` give the (7 + T) x (7 + T) information and covariance, the
+pose covariance marginalised over the latent beside the conditional one, and ``sdf_std`` pushes the latent's covariance
+back through the Jacobian to a per-voxel standard deviation of the surface.
 """
 import math
 from dataclasses import dataclass
@@ -25,14 +32,21 @@ GRAM_SIZE = 10   # (d0 .. d7, r, 1)
 
 def render_information(depth: torch.Tensor, target: torch.Tensor, sdf: torch.Tensor, position: torch.Tensor,
                        orientation: torch.Tensor, inv_scale: torch.Tensor, camera: Camera,
-                       inlier_threshold: float = 0.0, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+                       inlier_threshold: float = 0.0, workspace: Optional[torch.Tensor] = None,
+                       jacobian: Optional[torch.Tensor] = None, tangents: Optional[int] = None) -> torch.Tensor:
     """(B,10,10) float64: per view the Gram matrix of f = (d depth / d (px,py,pz,qx,qy,qz,qw,inv_scale), depth - target, 1)
     over the pixels with depth > 0, target > 0 and -- for ``inlier_threshold`` > 0 -- |target - depth| / target below it.
 
     ``depth`` is the rendered estimate at the given pose ((H,W) or (B,H,W)), ``target`` the observation; the pose has
     the shapes ``render_depth_gpu`` / ``render_depth_batch`` take: position (3,) or (B,3), orientation (4,) or (B,4),
     inv_scale () or (B,); ``sdf`` (R,R,R) shared by the views or (B,R,R,R).  ``[:8,:8]`` is J^T J, ``[:8,8]`` J^T r,
-    ``[8,8]`` sum r^2, ``[9,9]`` the pixel count.  Exactly symmetric, the same bits on every call."""
+    ``[8,8]`` sum r^2, ``[9,9]`` the pixel count.  Exactly symmetric, the same bits on every call.
+
+    ``jacobian``: the decoder's Jacobian in ``SDFDecoder.jvp``'s voxel-major layout, (R^3, Tp) shared by the views or
+    (B, R^3, Tp), with ``tangents`` = T of its Tp columns in use (default: all).  The result is then (B, 10+T, 10+T), the
+    Gram matrix of f = (d0 .. d7, s0 .. s_{T-1}, r, 1) with s_t = d depth / d (latent direction t) over the same pixels
+    (``sdfr_render_information_shape``): ``[:8,:8]`` the pose block, ``[8:8+T,8:8+T]`` the latent block, ``[:8+T,8+T]``
+    J^T r, ``[8+T,8+T]`` sum r^2, ``[9+T,9+T]`` the count.  1 <= T <= 22."""
     _check_inputs((depth, "depth"), (target, "target"), (sdf, "sdf"), (position, "position"),
                   (orientation, "orientation"), (inv_scale, "inv_scale"))
     pos, quat, isc = position.reshape(-1, 3), orientation.reshape(-1, 4), inv_scale.reshape(-1)
@@ -54,6 +68,27 @@ def render_information(depth: torch.Tensor, target: torch.Tensor, sdf: torch.Ten
     fx, fy, cx, cy, _ = camera.get_pinhole_camera_parameters(0.5)
     dev = sdf.device
     L = _lib.lib()
+    if jacobian is not None:
+        _check_inputs((jacobian, "jacobian"))
+        Tp = jacobian.shape[-1]
+        T = Tp if tangents is None else int(tangents)
+        if jacobian.dim() == 2 and jacobian.shape[0] == R ** 3:
+            jstride = 0
+        elif jacobian.dim() == 3 and tuple(jacobian.shape[:2]) == (B, R ** 3):
+            jstride = R ** 3 * Tp
+        else:
+            raise RuntimeError("jacobian must be (R^3, Tp) or (B, R^3, Tp)")
+        nbytes = L.sdfr_render_information_shape_workspace_bytes(B, W, H, T)
+        if workspace is None and nbytes:
+            workspace = _workspace(dev, nbytes)
+        ws = _lib.workspace(nbytes, "sdfr_render_information_shape_workspace_bytes", dev, workspace)
+        gram = torch.empty((B, GRAM_SIZE + T, GRAM_SIZE + T), dtype=torch.float64, device=dev)
+        rc = L.sdfr_render_information_shape(_ptr(depth), _ptr(target), _ptr(sdf), R, stride, _ptr(jacobian), Tp, T,
+                                             jstride, _ptr(pos), _ptr(quat), _ptr(isc), B, W, H, cx, cy, fx, fy,
+                                             float(inlier_threshold), _ptr(gram), _ptr(ws), ws.numel(), dev.index,
+                                             _stream(dev))
+        _lib.check(rc, "sdfr_render_information_shape")
+        return gram
     nbytes = L.sdfr_render_information_workspace_bytes(B, W, H)
     if workspace is None and nbytes:
         workspace = _workspace(dev, nbytes)   # (the renderer's per-stream scratch buffer)
@@ -167,3 +202,132 @@ def pose_covariance(information: torch.Tensor, rss: torch.Tensor, count: torch.T
     return PoseUncertainty(information=H, covariance=cov, sigma2=sigma2, rank=rank, position_std=std[:, 0:3],
                            rotation_std_deg=std[:, 3:6] * (180.0 / math.pi), scale_rel_std=std[:, 6],
                            unobserved=unobserved)
+
+
+def joint_tangent_information(gram: torch.Tensor, orientation: torch.Tensor, inv_scale: torch.Tensor,
+                              camera_orientations: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(B,7+T,7+T) float64 from the joint Gram matrices (B,10+T,10+T) of ``render_information(jacobian=)``:
+    ``tangent_map``'s T on the pose block, the identity on the latent block (the latent is the same vector in every
+    frame).  In the world frame (``camera_orientations``) the views of one object add."""
+    F = gram.shape[-1]
+    L = F - GRAM_SIZE
+    if gram.shape[-2] != F or L < 1:
+        raise RuntimeError("gram must be (B, 10+T, 10+T) with T >= 1")
+    G = gram.to(torch.float64).reshape(-1, F, F)[:, :8 + L, :8 + L]
+    T8 = tangent_map(orientation, inv_scale, camera_orientations).to(G.device)
+    M = G.new_zeros((G.shape[0], 8 + L, 7 + L))
+    M[:, :8, :7] = T8
+    M[:, 8:, 7:] = torch.eye(L, dtype=torch.float64, device=G.device)
+    Hj = M.transpose(-1, -2) @ G @ M
+    return 0.5 * (Hj + Hj.transpose(-1, -2))
+
+
+@dataclass
+class ShapePoseUncertainty:
+    """What ``shape_pose_covariance`` returns, batched over K objects; n = 7 + T (float64 but ``rank``).
+
+    information (K,n,n): J^T J / sigma2 with the latent prior added; covariance (K,n,n) its pseudo-inverse over the
+    retained space -- [:7,:7] is the pose covariance MARGINALISED over the latent, [7:,7:] the latent's;
+    position_std (K,3), rotation_std_deg (K,3), scale_rel_std (K,) from that marginal block;
+    conditional: the ``PoseUncertainty`` of the pose block alone, the shape held fixed -- what
+    ``SDFPipeline.pose_uncertainty`` reports (its stds are never above the marginal ones in a full-rank problem);
+    latent_std (K,T); sigma2 (K,); rank (K,) int64 of ``information``; unobserved (K,n,n): row i is the direction of the
+    i-th smallest eigenvalue if it was discarded, zeros otherwise; sdf_std: (K,D,D,D) float32 where it was asked for
+    (``SDFPipeline.shape_uncertainty(sdf_std=True)``), else None."""
+    information: torch.Tensor
+    covariance: torch.Tensor
+    pose_covariance: torch.Tensor
+    position_std: torch.Tensor
+    rotation_std_deg: torch.Tensor
+    scale_rel_std: torch.Tensor
+    conditional: PoseUncertainty
+    latent_std: torch.Tensor
+    sigma2: torch.Tensor
+    rank: torch.Tensor
+    unobserved: torch.Tensor
+    sdf_std: Optional[torch.Tensor] = None
+
+
+def _retained(H: torch.Tensor, rcond: float):
+    """eigen-decomposition of the symmetric (K,n,n) H and the mask of the eigenvalues above rcond x the largest (a row
+    that is not finite keeps none): ``pose_covariance``'s rule"""
+    finite = torch.isfinite(H).all(-1).all(-1)
+    w, V = torch.linalg.eigh(torch.where(finite[:, None, None], H, torch.zeros_like(H)))
+    top = w.max(dim=-1).values.clamp(min=0.0)
+    keep = (w > rcond * top[:, None]) & (top[:, None] > 0.0) & finite[:, None]
+    return w, V, keep, finite
+
+
+def shape_pose_covariance(information: torch.Tensor, rss: torch.Tensor, count: torch.Tensor, latent_prior: float = 1.0,
+                          rcond: float = 1e-6, depth_sigma: Optional[float] = None) -> ShapePoseUncertainty:
+    """Joint covariance of (position, rotation vector, log-scale, latent) from ``joint_tangent_information``'s J^T J
+    (K,7+T,7+T), the residual sums of squares (K,) and the pixel counts (K,).
+
+    ``sigma2`` is formed as in ``pose_covariance`` -- ``rss / (count - rank of J^T J)``, NaN where the pixels do not
+    outnumber the rank, or ``depth_sigma ** 2`` -- BEFORE the prior is added.  ``latent_prior`` = lambda adds the VAE's
+    N(0, I / lambda) prior as ``lambda I`` on the latent block of ``J^T J / sigma2`` (0: no prior).
+    The latent's units are arbitrary beside metres and radians, so before the eigenvalues are compared with ``rcond``
+    every latent coordinate is scaled so that its diagonal entry equals the pose block's largest eigenvalue (the pose
+    block is not touched, a latent coordinate with a zero diagonal neither); the covariance is mapped back.  A degenerate row raises
+    nothing: it shows in ``rank`` and NaN."""
+    H = information.to(torch.float64)
+    n = H.shape[-1]
+    T = n - 7
+    if H.shape[-2] != n or T < 1:
+        raise RuntimeError("information must be (K, 7+T, 7+T) with T >= 1")
+    H = H.reshape(-1, n, n)
+    H = 0.5 * (H + H.transpose(-1, -2))
+    K = H.shape[0]
+    rss = rss.to(torch.float64).reshape(-1)
+    count = count.to(torch.float64).reshape(-1)
+    conditional = pose_covariance(H[:, :7, :7], rss, count, rcond=rcond, depth_sigma=depth_sigma)
+    _, _, keep0, _ = _retained(H, rcond)
+    if depth_sigma is None:
+        dof = count - keep0.sum(-1)
+        sigma2 = torch.where(dof > 0, rss / dof.clamp(min=1.0), torch.full_like(rss, float("nan")))
+    else:
+        sigma2 = torch.full_like(rss, float(depth_sigma) ** 2)
+    prior = H.new_zeros(n)
+    prior[7:] = float(latent_prior)
+    A = H / sigma2[:, None, None] + torch.diag(prior)
+    ok = torch.isfinite(A).all(-1).all(-1)
+    A0 = torch.where(ok[:, None, None], A, torch.zeros_like(A))
+    tp = torch.linalg.eigvalsh(A0[:, :7, :7])[:, -1].clamp(min=0.0)
+    dz = torch.diagonal(A0[:, 7:, 7:], dim1=-2, dim2=-1)
+    usable = (dz > 0) & (tp[:, None] > 0)
+    c = torch.where(usable, torch.sqrt(tp[:, None] / torch.where(usable, dz, torch.ones_like(dz))), torch.ones_like(dz))
+    S = torch.cat([H.new_ones((K, 7)), c], dim=1)
+    w, V, keep, _ = _retained(S[:, :, None] * A0 * S[:, None, :], rcond)
+    keep = keep & ok[:, None]
+    inv = torch.where(keep, 1.0 / torch.where(keep, w, torch.ones_like(w)), torch.zeros_like(w))
+    cov = S[:, :, None] * ((V * inv[:, None, :]) @ V.transpose(-1, -2)) * S[:, None, :]
+    cov = 0.5 * (cov + cov.transpose(-1, -2))
+    cov = torch.where(ok[:, None, None], cov, torch.full_like(cov, float("nan")))
+    std = torch.sqrt(torch.diagonal(cov, dim1=-2, dim2=-1).clamp(min=0.0))
+    # a discarded eigenvector v of S A S is the direction S v of A
+    U = V.transpose(-1, -2) * S[:, None, :]
+    U = U / torch.linalg.norm(U, dim=-1, keepdim=True).clamp(min=1e-300)
+    unobserved = torch.where(keep[:, :, None], torch.zeros_like(U), U)
+    return ShapePoseUncertainty(information=A, covariance=cov, pose_covariance=cov[:, :7, :7], position_std=std[:, 0:3],
+                                rotation_std_deg=std[:, 3:6] * (180.0 / math.pi), scale_rel_std=std[:, 6],
+                                conditional=conditional, latent_std=std[:, 7:], sigma2=sigma2, rank=keep.sum(-1),
+                                unobserved=unobserved)
+
+
+def sdf_std(jac: torch.Tensor, latent_covariance: torch.Tensor, tangents: Optional[int] = None) -> torch.Tensor:
+    """(K,D,D,D) float32: the standard deviation of every voxel of K decoded volumes under a covariance of their
+    latents, ``sqrt(max(0, j^T S j))`` with j the voxel's row of ``SDFDecoder.jvp``'s buffer ``jac`` (K, D^3, Tp) and S
+    ``latent_covariance`` (K,T,T) (``sdfr_sdf_std``; T = ``tangents``, default S's size)."""
+    _check_inputs((jac, "jac"))
+    if jac.dim() != 3:
+        raise RuntimeError("jac must be (K, D^3, Tp)")
+    K, voxels, Tp = jac.shape
+    T = latent_covariance.shape[-1] if tangents is None else int(tangents)
+    D = round(voxels ** (1.0 / 3.0))
+    cov = latent_covariance.to(device=jac.device, dtype=torch.float64).reshape(-1, T, T).contiguous()
+    if D ** 3 != voxels or cov.shape[0] != K:
+        raise RuntimeError("expected jac (K, D^3, Tp) and latent_covariance (K, T, T)")
+    out = torch.empty((K, D, D, D), dtype=torch.float32, device=jac.device)
+    rc = _lib.lib().sdfr_sdf_std(_ptr(jac), K, voxels, Tp, T, _ptr(cov), _ptr(out), jac.device.index, _stream(jac.device))
+    _lib.check(rc, "sdfr_sdf_std")
+    return out

@@ -204,6 +204,56 @@ class SDFDecoder:
         """Same as SDFVAE.decode (sdf_vae.py:79-87)."""
         return self.forward(z, enforce_tsdf)
 
+    def jvp(self, z: torch.Tensor, tangents: Optional[torch.Tensor] = None, enforce_tsdf: bool = False):
+        """The decoded volumes and their forward-mode derivative w.r.t. the latent (``sdfr_decoder_jvp``).
+
+        z (N, latent_size); tangents (N, T, latent_size) directions per latent, None = the identity basis (T =
+        latent_size: the full Jacobian d SDF / d z).  1 <= T <= 22.  Returns ``(sdf, jac)``: sdf (N, 1, D, D, D) is the
+        existing forward's output (run with a tape), jac the VOXEL-major buffer (N, D^3, Tp), Tp = T rounded up to a
+        multiple of 4 with zeros in the columns T .. Tp - 1 -- ``jac[n, voxel, t]`` is the derivative of voxel `voxel`
+        of latent n along ``tangents[n, t]``; this is the layout ``uncertainty.render_information(jacobian=)`` reads.
+        ``SDFDecoder.tangent_volumes(jac, T)`` is the same memory as (N, T, D, D, D).  With ``enforce_tsdf`` on a
+        truncating decoder the derivative is zero where the volume sits on the clamp.  No autograd: z is detached."""
+        if not z.is_cuda or z.dtype != torch.float32:
+            raise RuntimeError("z must be a float32 CUDA tensor")
+        if z.dim() != 2 or z.shape[1] != self.latent_size:
+            raise RuntimeError(f"z must have shape (N, {self.latent_size})")
+        zc = z.detach().contiguous()
+        N, D = zc.shape[0], self._volume_size
+        if tangents is None:
+            T, tc = self.latent_size, None
+        else:
+            if (not tangents.is_cuda or tangents.dtype != torch.float32 or tangents.dim() != 3
+                    or tangents.shape[0] != N or tangents.shape[2] != self.latent_size):
+                raise RuntimeError(f"tangents must be a float32 CUDA tensor of shape ({N}, T, {self.latent_size})")
+            T, tc = tangents.shape[1], tangents.detach().contiguous()
+        need = self._L.sdfr_decoder_jvp_workspace_bytes(self._h, N, T)
+        if need == 0:
+            raise RuntimeError(f"sdfr_decoder_jvp takes 1 <= T <= 22 tangents and N T <= 65535 (N={N}, T={T})")
+        tape = torch.empty(max(self._L.sdfr_decoder_tape_bytes(self._h, N) // 4, 1), dtype=torch.float32, device=self.device)
+        out = self._forward_raw(zc, enforce_tsdf, tape)
+        jac = torch.empty((N, D ** 3, (T + 3) & ~3), dtype=torch.float32, device=self.device)
+        ws = self._scratch(need)
+        clamp = bool(enforce_tsdf) and self._tsdf is not False
+        rc = self._L.sdfr_decoder_jvp(self._h, zc.data_ptr(), tape.data_ptr(), out.data_ptr() if clamp else None,
+                                      None if tc is None else tc.data_ptr(), N, T, int(clamp), jac.data_ptr(),
+                                      ws.data_ptr(), ws.numel(), _stream(self.device))
+        _lib.check(rc, "sdfr_decoder_jvp")
+        return out, jac
+
+    def decode_jvp(self, z: torch.Tensor, tangents: Optional[torch.Tensor] = None, enforce_tsdf: bool = False):
+        """``jvp`` under the name ``SDFVAE.decode_jvp`` has (a pipeline holds either as its ``vae``)."""
+        return self.jvp(z, tangents, enforce_tsdf)
+
+    @staticmethod
+    def tangent_volumes(jac: torch.Tensor, T: Optional[int] = None) -> torch.Tensor:
+        """The (N, T, D, D, D) strided view of a ``jvp`` buffer (N, D^3, Tp): tangent volume t of latent n, no copy."""
+        N, voxels, Tp = jac.shape
+        D = round(voxels ** (1.0 / 3.0))
+        if D ** 3 != voxels:
+            raise RuntimeError("jac must be (N, D^3, Tp)")
+        return jac.view(N, D, D, D, Tp)[..., :Tp if T is None else T].permute(0, 4, 1, 2, 3)
+
 
 # ---- encoder ------------------------------------------------------------------------------------------------------
 # reference: SDFEncoder (sdf_vae.py:103-169) builds `locate(type)(**args)` for every layer_infos entry; these are the
@@ -520,6 +570,10 @@ class SDFVAE:
 
     def decode(self, z: torch.Tensor, enforce_tsdf: bool = False) -> torch.Tensor:
         return self.decoder(z, enforce_tsdf)
+
+    def decode_jvp(self, z: torch.Tensor, tangents: Optional[torch.Tensor] = None, enforce_tsdf: bool = False):
+        """``SDFDecoder.jvp``: (sdf, jac) -- the decoded volumes and their derivative along latent directions."""
+        return self.decoder.jvp(z, tangents, enforce_tsdf)
 
     def prepare_input(self, sdfs: torch.Tensor) -> None:
         self.encoder.prepare_input(sdfs)
