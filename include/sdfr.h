@@ -96,6 +96,8 @@
  *        sdfr_pose_pair_errors, sdfr_ap_match, sdfr_ap_integrate
  *  17. [unstable] DECODER JVP: the Jacobian of the decoded volume w.r.t. the latent (SDFPipeline.shape_uncertainty)
  *        sdfr_decoder_jvp[_workspace_bytes], sdfr_sdf_std
+ *  18. [unstable] LM REFINEMENT: a damped Gauss-Newton step of pose and latent from those Gram matrices (SDFPipeline.refine)
+ *        sdfr_lm_step
  * (Within the file the groups follow the order in which the reference's code runs; every declaration carries the
  * reference file:line it replaces.)
  */
@@ -1737,6 +1739,82 @@ SDFR_API int sdfr_decoder_jvp(const sdfr_decoder* decoder, const float* z, const
  * SDFR_E_INVALID before anything touches the GPU. */
 SDFR_API int sdfr_sdf_std(const float* jac, int K, long long voxels, int Tp, int T, const double* covariance,
                           float* out, int device, void* stream);
+
+/* ==== 18. LM REFINEMENT ======================================================================= */
+/* ---- one Levenberg-Marquardt step of K estimates from the Gram matrices of groups 14 / 17.  The loop of group 3 is
+ * first order and returns the iterate it stopped at; the reference has nothing else (and no Gram matrix to build it
+ * from).  This is the bookkeeping-and-solve half of a damped Gauss-Newton iteration: the caller decodes and renders the
+ * TRIAL rows and hands in their Gram matrices, the call decides whether the trial replaces the CURRENT iterate, forms
+ * the normal equations at the current iterate in the world tangent, solves them and writes the next trial rows;
+ * sdfr_pose_to_views_objects (group 3) then gives that trial's camera-frame poses and packed latents for the next render.
+ *   gram_trial   [K V][F][F] doubles, F = 10 + T, object-major (view k V + v): what sdfr_render_information (T = 0) or
+ *                sdfr_render_information_shape (1 <= T <= 22) wrote for the rows of params_trial; read only
+ *   params_trial [K][n_params] floats: position 3 | orientation 4 (x, y, z, w) | scale 1 | latent ...; read as the rows
+ *                the Gram matrices were evaluated at, overwritten with the NEXT trial (entries 8 + T .. are the current
+ *                row's: with T = 0 the latent is never touched)
+ *   params_cur   [K][n_params], gram_cur [K V][F][F]: the current iterate and its Gram matrices; the call's own
+ *   state        [K][SDFR_LM_STATE_DOUBLES] doubles, indexed by the macros below
+ *   step         [K][7 + T] doubles or NULL: the solved tangent step delta behind the new trial (zeros for a row
+ *                that solved nothing in this call)
+ *   cam_quat     [V][4]: the cameras' orientations in the world, ONE list for every object (as sdfr_pose_to_views_objects)
+ * Per object, with rss = sum_v gram[v][8 + T][8 + T], cnt = sum_v gram[v][9 + T][9 + T] (views ascending), z the row's
+ * entries 8 .. 8 + T - 1 and mu = latent_weight:
+ *   cost     Phi = rss / cnt + mu |z|^2: the MEAN squared residual (the included pixels change from iterate to iterate; a
+ *            sum would reward losing overlap).  Not finite where a Gram entry of the trial is not, or cnt = 0.
+ *   accept   init != 0: always, and lambda = lambda0, the counters 0.  Otherwise iff Phi_trial is finite, cnt_trial >=
+ *            min_overlap cnt_cur and Phi_trial < Phi_cur.  Accepted: the trial row and its V matrices are copied into
+ *            the current ones, lambda <- max(lambda lambda_down, lambda_min).  Rejected: lambda <- lambda lambda_up.
+ *            These are IEEE double operations in this order without contraction: a float64 restatement decides alike.
+ *   system   at the current iterate, per view M = diag(T8, I_T) with T8 the 8 x 7 map d (px, py, pz, qx, qy, qz, qw,
+ *            inv_scale) / d (world position, world rotation vector, log-scale) -- identity; 1/2 (e_k, 0) (x) q_c; -inv_scale;
+ *            position and rotation columns through R_c^T -- at the view's camera-frame quaternion q_c = conj(cam_quat[v])
+ *            (x) q / |q| and inv_scale = 1 / scale, recomputed here in double from the current row:
+ *              H = sum_v M^T G_v[:8+T][:8+T] M / cnt + mu I_latent,   g = sum_v M^T G_v[:8+T][8+T] / cnt + mu z
+ *            (views ascending, then the division), the model Phi(delta) ~ Phi + 2 g^T delta + delta^T H delta.
+ *   solve    A = H + lambda diag(max(H_ii, 1e-12 max_j H_jj)) -- the floor keeps a direction nothing observes (a
+ *            symmetric body's spin, a latent column of zeros) from a zero pivot; its step is exactly 0 --, A delta = -g by
+ *            Cholesky in double.
+ *   retract  position += delta[0:3]; q <- exp(delta[3:6] / 2) (x) q / |q|, normalised; scale <- scale exp(delta[6]);
+ *            z += delta[7:]; rounded to float.
+ *   status   SDFR_LM_RUNNING; SDFR_LM_CONVERGED: the rounded trial equals the current row bit for bit (entries
+ *            0 .. 8 + T - 1), or the step behind a trial that has just been accepted had a scaled norm
+ *            sqrt(delta^T diag(A) delta) < step_tol; SDFR_LM_STALLED: lambda > lambda_max after a rejection;
+ *            SDFR_LM_NO_SYSTEM: cnt = 0, an input (a Gram entry, an entry 0 .. 8 + T - 1 of the row) or the retracted
+ *            row is not finite, or a pivot is not positive even with the floor.
+ *            A row whose status is not SDFR_LM_RUNNING is FROZEN: its trial row is set to its current row, and later calls
+ *            (init = 0) leave its current row, its current matrices and its state bit for bit as they are.  No NaN is
+ *            ever written to a parameter row.
+ * One launch on the caller's stream: workgroup k is object k and is one wave; all arithmetic is double, the matrices
+ * (n = 7 + T <= 29: 6.7 KB) live in LDS; no workspace, no allocation, no host synchronisation.  Every sum has one order:
+ * two calls on the same inputs give the same bits, and row k depends neither on K nor on the other rows.  On init the
+ * current buffers and the state may hold anything.
+ * 1 <= K <= 65535, 1 <= V <= 64, T = 0 or 1 <= T <= 22, 8 + T <= n_params <= 65535; the double buffers 8-byte aligned;
+ * every scalar finite and >= 0.  Errors before anything touches the GPU: SDFR_E_NULL (a pointer other than step),
+ * SDFR_E_INVALID (everything else), with a message. */
+#define SDFR_LM_STATE_DOUBLES 16
+#define SDFR_LM_LAMBDA 0        /* the damping the NEXT solve uses (the last one used, once frozen) */
+#define SDFR_LM_COST 1          /* Phi of the current iterate */
+#define SDFR_LM_COUNT 2         /* its pixel count, summed over the views */
+#define SDFR_LM_STATUS 3        /* SDFR_LM_RUNNING ... */
+#define SDFR_LM_ACCEPTED 4      /* trials accepted since init (init itself is not one) */
+#define SDFR_LM_REJECTED 5
+#define SDFR_LM_STEP_NORM 6     /* sqrt(delta^T diag(A) delta) of the last solve */
+#define SDFR_LM_PREDICTED 7     /* -(2 g^T delta + delta^T H delta) of the last solve */
+#define SDFR_LM_ACTUAL 8        /* Phi_cur - Phi_trial of the last trial judged (0 at init) */
+#define SDFR_LM_COST_INIT 9     /* Phi and count at init */
+#define SDFR_LM_COUNT_INIT 10
+#define SDFR_LM_LAST_ACCEPT 11  /* 1: the last call accepted its trial (init included), 0: it rejected it */
+#define SDFR_LM_COST_TRIAL 12   /* Phi and count of the last trial judged, accepted or not */
+#define SDFR_LM_COUNT_TRIAL 13  /* (14, 15: reserved, written as 0) */
+#define SDFR_LM_RUNNING 0
+#define SDFR_LM_CONVERGED 1
+#define SDFR_LM_STALLED 2
+#define SDFR_LM_NO_SYSTEM 3
+SDFR_API int sdfr_lm_step(const double* gram_trial, float* params_trial, float* params_cur, double* gram_cur,
+                          double* state, double* step /* nullable */, const float* cam_quat, int K, int V, int T,
+                          int n_params, int init, double latent_weight, double min_overlap, double lambda0,
+                          double lambda_up, double lambda_down, double lambda_min, double lambda_max, double step_tol,
+                          int device, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,286 @@
+"""Levenberg-Marquardt refinement of pose and latent from the Gram matrices of ``sdfest_amd.uncertainty``.
+
+The render-and-compare loop is first order: it returns the iterate Adam stopped at.  The information calls already give
+everything a second-order step needs -- per view ``J^T J``, ``J^T r``, ``sum r^2`` and the pixel count, jointly over
+the pose and up to 22 latent directions --, and ``sdfr_lm_step`` (include/sdfr.h group 18) turns them into one damped
+Gauss-Newton step per object on the device: the accept test, the normal equations in the world tangent, the Cholesky
+solve, the retraction and the status, one wave per object.  The reference has neither the matrices nor the step.
+
+``lm_step`` wraps the C entry; ``LMRefiner`` owns the buffers of K objects seen from V cameras and runs the iteration
+(decode, render, Jacobian, Gram matrices, step, poses of the next trial) as a launch sequence on one stream without an
+allocation or a host synchronisation; ``SDFPipeline.refine`` starts it from the last estimate.
+
+Objective: the MEAN squared depth residual over the included pixels plus ``latent_weight |z|^2``; a mean because the
+included pixels change from iterate to iterate and a sum would reward losing overlap.  The iteration is eager; its
+sequence has no host synchronisation and could be captured into a graph, which is not done here."""
+from dataclasses import dataclass
+from typing import Optional
+
+import torch
+
+from . import _lib
+from .differentiable_renderer import _ptr, _stream
+
+STATE_DOUBLES = _lib.ABI["SDFR_LM_STATE_DOUBLES"]
+STATE = {name[len("SDFR_LM_"):].lower(): index for name, index in _lib.ABI.items()
+         if name.startswith("SDFR_LM_") and name not in ("SDFR_LM_STATE_DOUBLES", "SDFR_LM_RUNNING", "SDFR_LM_CONVERGED",
+                                                        "SDFR_LM_STALLED", "SDFR_LM_NO_SYSTEM")}
+RUNNING, CONVERGED, STALLED, NO_SYSTEM = (_lib.ABI["SDFR_LM_" + s] for s in ("RUNNING", "CONVERGED", "STALLED", "NO_SYSTEM"))
+MAX_TANGENTS = 22
+
+# the damping schedule and the stopping rule, by the C entry's argument names: lambda starts at lambda0, an accepted
+# trial multiplies it by lambda_down (not below lambda_min), a rejected one by lambda_up; above lambda_max the row has
+# stalled; a scaled step norm below step_tol behind an accepted trial means converged
+LM_DEFAULTS = dict(lambda0=1e-3, lambda_up=10.0, lambda_down=0.1, lambda_min=1e-9, lambda_max=1e9, step_tol=1e-9)
+
+
+def _constants(lm: dict) -> dict:
+    unknown = set(lm) - set(LM_DEFAULTS)
+    if unknown:
+        raise TypeError(f"unknown LM constants {sorted(unknown)}: expected some of {sorted(LM_DEFAULTS)}")
+    return {k: float(v) for k, v in dict(LM_DEFAULTS, **lm).items()}
+
+
+def lm_step(gram_trial: torch.Tensor, params_trial: torch.Tensor, params_cur: torch.Tensor, gram_cur: torch.Tensor,
+            state: torch.Tensor, cam_quat: torch.Tensor, views: int, init: bool, latent_weight: float = 0.0,
+            min_overlap: float = 0.5, step: Optional[torch.Tensor] = None, **lm) -> None:
+    """One LM bookkeeping-and-solve step of K objects IN PLACE (``sdfr_lm_step``).
+
+    gram_trial (K V, F, F) float64, F = 10 + T: what ``uncertainty.render_information`` returned for the K V views of
+    the rows of ``params_trial`` (K, n_params) float32 [position 3 | orientation 4 xyzw | scale | latent], object-major;
+    T = 0 (pose only) or 1 <= T <= 22 latent directions.  params_cur, gram_cur (same shapes) and state (K, 16) float64
+    (``lm.STATE`` names its entries) are the call's own: ``init=True`` fills them from the trial, which it accepts
+    unconditionally.  cam_quat (V, 4): the cameras' orientations in the world.  Afterwards ``params_trial`` holds the
+    next rows to render and evaluate, or the current rows where the status is no longer ``RUNNING``.  step (K, 7 + T)
+    float64, optional: receives the solved tangent steps.  ``**lm``: ``LM_DEFAULTS``."""
+    c = _constants(lm)
+    V = int(views)
+    K, n_params = params_trial.shape
+    F = gram_trial.shape[-1]
+    T = F - 10
+    for t, name, dtype, shape in ((gram_trial, "gram_trial", torch.float64, (K * V, F, F)),
+                                  (gram_cur, "gram_cur", torch.float64, (K * V, F, F)),
+                                  (params_trial, "params_trial", torch.float32, (K, n_params)),
+                                  (params_cur, "params_cur", torch.float32, (K, n_params)),
+                                  (state, "state", torch.float64, (K, STATE_DOUBLES)),
+                                  (cam_quat, "cam_quat", torch.float32, (V, 4))) + (
+                                      ((step, "step", torch.float64, (K, 7 + T)),) if step is not None else ()):
+        if not (t.is_cuda and t.is_contiguous() and t.dtype is dtype and tuple(t.shape) == shape):
+            raise RuntimeError(f"{name} must be a contiguous {dtype} CUDA tensor of shape {shape}, got "
+                               f"{t.dtype} {tuple(t.shape)}")
+    dev = params_trial.device
+    rc = _lib.lib().sdfr_lm_step(_ptr(gram_trial), _ptr(params_trial), _ptr(params_cur), _ptr(gram_cur), _ptr(state),
+                                 _ptr(step), _ptr(cam_quat), K, V, T, n_params, int(bool(init)), float(latent_weight),
+                                 float(min_overlap), c["lambda0"], c["lambda_up"], c["lambda_down"], c["lambda_min"],
+                                 c["lambda_max"], c["step_tol"], dev.index, _stream(dev))
+    _lib.check(rc, "sdfr_lm_step")
+
+
+def view_volumes(per_object: torch.Tensor, K: int, V: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """What the K V object-major views of a render or information call read of a per-object buffer (K, ...) -- decoded
+    volumes, decoder Jacobians: ONE object's views share its row (a view stride of 0), one view per object reads the
+    buffer as it is, otherwise every view gets its own copy of its object's row.  ``out`` (K V, ...): the copy goes there
+    through ``sdfr_volumes_replicate`` (nothing is allocated); without it a new tensor is made."""
+    if K == 1:
+        return per_object[0]
+    if V == 1:
+        return per_object
+    if out is None:
+        return per_object.repeat_interleave(V, dim=0).contiguous()
+    dev = per_object.device
+    rc = _lib.lib().sdfr_volumes_replicate(_ptr(per_object), _ptr(out), K, V, per_object[0].numel(), dev.index, _stream(dev))
+    _lib.check(rc, "sdfr_volumes_replicate")
+    return out
+
+
+@dataclass
+class LMReport:
+    """What ``LMRefiner.report`` reads back, per object (leading dimension K, CPU tensors, float64 but ``status`` and the
+    counters): the cost Phi and the pixel count at the start and at the current iterate, the accepted and rejected
+    trials, the status (``lm.RUNNING`` / ``CONVERGED`` / ``STALLED`` / ``NO_SYSTEM``), the damping, the last step's scaled
+    norm and the last predicted and actual reduction of Phi."""
+    initial_cost: torch.Tensor
+    final_cost: torch.Tensor
+    initial_count: torch.Tensor
+    final_count: torch.Tensor
+    accepted: torch.Tensor
+    rejected: torch.Tensor
+    status: torch.Tensor
+    final_lambda: torch.Tensor
+    step_norm: torch.Tensor
+    predicted_reduction: torch.Tensor
+    actual_reduction: torch.Tensor
+
+
+class LMRefiner:
+    """K estimates seen from V cameras, refined side by side by Levenberg-Marquardt.
+
+    pipeline_or_parts: an ``SDFPipeline`` (its decoder, camera and ``threshold``) or the tuple ``(decoder, camera,
+    threshold)``.  shape: the latent is part of the step (T = the latent size, at most 22) or held fixed (T = 0).
+    inlier_threshold: ``render_information``'s; latent_weight: mu of the objective; min_overlap: a trial that keeps less
+    than this share of the current iterate's pixels is rejected; ``**lm``: ``LM_DEFAULTS``.
+
+    Everything an iteration touches is allocated here, once: the current and trial rows, the two sets of Gram matrices,
+    the state, the decoder's tape and Jacobian, the depth images and the workspaces.  ``start`` binds an observation and
+    a start; ``iterate(n)`` runs n iterations, each the launch sequence
+        batched decode of the K trial latents (with its tape), the forward render of the K V views,
+        ``sdfr_decoder_jvp`` (shape only), ``sdfr_render_information[_shape]`` into the trial's Gram matrices,
+        ``sdfr_lm_step``, ``sdfr_pose_to_views_objects`` for the new trial
+    on the current stream, without an allocation or a host synchronisation.  The first iteration after ``start`` is the
+    ``init`` call that evaluates the start; the Jacobian of a trial that ends up rejected is wasted work."""
+
+    def __init__(self, pipeline_or_parts, K: int, V: int, shape: bool, inlier_threshold: float = 0.0,
+                 latent_weight: float = 0.0, min_overlap: float = 0.5, device=None, **lm):
+        if isinstance(pipeline_or_parts, (tuple, list)):
+            vae, camera, threshold = pipeline_or_parts
+        else:
+            vae, camera = pipeline_or_parts.vae, pipeline_or_parts.cam
+            threshold = pipeline_or_parts.config["threshold"]
+        dec = self.dec = getattr(vae, "decoder", vae)
+        self.L = L = _lib.lib()
+        self.cam, self.threshold = camera, float(threshold)
+        self.dev = dev = torch.device(dec.device if device is None else device)
+        K, V = int(K), int(V)
+        if K < 1 or not 1 <= V <= 64 or K * V > 65535:
+            raise ValueError(f"K = {K} objects and V = {V} views: K >= 1, 1 <= V <= 64 and K V <= 65535 are expected")
+        self.K, self.V, self.B = K, V, K * V
+        self.Lz = int(dec.latent_size)
+        self.shape = bool(shape)
+        T = self.T = self.Lz if self.shape else 0
+        if T > MAX_TANGENTS:
+            raise ValueError(f"shape refinement takes latents of up to {MAX_TANGENTS} entries, this decoder has {T}")
+        self.n = 8 + self.Lz
+        self.inlier_threshold, self.latent_weight, self.min_overlap = (float(inlier_threshold), float(latent_weight),
+                                                                       float(min_overlap))
+        self.constants = _constants(lm)
+        B, H, W = self.B, int(camera.height), int(camera.width)
+        self.H, self.W = H, W
+        R = self.R = int(dec._volume_size)
+        F = self.F = 10 + T
+        f32, f64, u8 = (dict(dtype=t, device=dev) for t in (torch.float32, torch.float64, torch.uint8))
+        self.params_trial, self.params_cur = torch.zeros((K, self.n), **f32), torch.zeros((K, self.n), **f32)
+        self.gram_trial, self.gram_cur = torch.zeros((B, F, F), **f64), torch.zeros((B, F, F), **f64)
+        self.state = torch.zeros((K, STATE_DOUBLES), **f64)
+        self.step = torch.zeros((K, 7 + T), **f64)
+        self.cam_pos = torch.zeros((V, 3), **f32)
+        self.cam_quat = torch.tensor([[0.0, 0.0, 0.0, 1.0]], **f32).repeat(V, 1)
+        self.target = torch.zeros((B, H, W), **f32)
+        self.depth = torch.zeros((B, H, W), **f32)
+        self.pos_c, self.quat_c = torch.zeros((B, 3), **f32), torch.zeros((B, 4), **f32)
+        self.inv_scale, self.scale_v = torch.zeros(B, **f32), torch.zeros(B, **f32)
+        self.z = torch.zeros((K, self.Lz), **f32)              # the trial latents, packed for the decoder
+        self.sdf_objects = torch.empty((K, R, R, R), **f32)    # what the decoder writes
+        per_view = K > 1 and V > 1                             # (view_volumes: else the views read the objects' buffers)
+        self.sdf_views = torch.empty((B, R, R, R), **f32) if per_view else None
+        self.tape = torch.empty(max(L.sdfr_decoder_tape_bytes(dec._h, K), 256), **u8)
+        need = L.sdfr_decoder_workspace_bytes(dec._h, K)
+        self.Tp = (T + 3) & ~3
+        self.jac_objects = self.jac_views = None
+        if self.shape:
+            jvp = L.sdfr_decoder_jvp_workspace_bytes(dec._h, K, T)
+            if jvp == 0:
+                raise ValueError(f"sdfr_decoder_jvp refuses K = {K} latents with T = {T} tangents (K T <= 65535)")
+            need = max(need, jvp)
+            self.jac_objects = torch.empty((K, R ** 3, self.Tp), **f32)
+            self.jac_views = torch.empty((B, R ** 3, self.Tp), **f32) if per_view else None
+        self.ws_dec = torch.empty(max(need, 256), **u8)
+        self.ws_render = torch.empty(max(L.sdfr_render_forward_workspace_bytes(R, B, W, H), 256), **u8)
+        info = (L.sdfr_render_information_shape_workspace_bytes(B, W, H, T) if self.shape
+                else L.sdfr_render_information_workspace_bytes(B, W, H))
+        if info == 0:
+            raise ValueError(f"the information call refuses {B} views of {W} x {H} pixels")
+        self.ws_info = torch.empty(max(info, 256), **u8)
+        fx, fy, cx, cy, _ = camera.get_pinhole_camera_parameters(0.5)
+        self._intrinsics = (float(cx), float(cy), float(fx), float(fy))
+        self._init = True
+        self.iterations = 0
+
+    def start(self, params: torch.Tensor, target: torch.Tensor, cam_pos: Optional[torch.Tensor] = None,
+              cam_quat: Optional[torch.Tensor] = None) -> "LMRefiner":
+        """Bind the observation and the start: params (K, 8 + latent) rows, target (K V, H, W) object-major (or any shape
+        of as many pixels), the cameras (V, 3) / (V, 4) in the world (default: the origin, the identity).  Copies into
+        the refiner's own buffers; the next ``iterate`` begins with the ``init`` step."""
+        with torch.no_grad():
+            self.params_trial.copy_(params.reshape(self.K, self.n))
+            self.target.copy_(target.reshape(self.B, self.H, self.W))
+            if cam_pos is not None:
+                self.cam_pos.copy_(cam_pos.reshape(self.V, 3))
+            else:
+                self.cam_pos.zero_()
+            if cam_quat is not None:
+                self.cam_quat.copy_(cam_quat.reshape(self.V, 4))
+            else:
+                self.cam_quat.zero_()
+                self.cam_quat[:, 3] = 1.0
+            self._poses(_stream(self.dev))
+        self._init = True
+        self.iterations = 0
+        return self
+
+    def _poses(self, st) -> None:
+        """the trial rows as camera-frame poses and packed latents: the existing kernel, not a second copy of it"""
+        _lib.check(self.L.sdfr_pose_to_views_objects(
+            _ptr(self.params_trial), self.n, self.K, _ptr(self.cam_pos), _ptr(self.cam_quat), self.V, _ptr(self.pos_c),
+            _ptr(self.quat_c), _ptr(self.inv_scale), _ptr(self.scale_v), _ptr(self.z), self.dev.index, st),
+            "sdfr_pose_to_views_objects")
+
+    def evaluate(self, st=None) -> None:
+        """steps 1-4 of an iteration: decode, render, Jacobian and Gram matrices of the trial rows"""
+        L, dec, K, V, B, R, T = self.L, self.dec, self.K, self.V, self.B, self.R, self.T
+        st = _stream(self.dev) if st is None else st
+        d = self.dev.index
+        check = _lib.check
+        check(L.sdfr_decoder_forward(dec._h, _ptr(self.z), K, 0, _ptr(self.sdf_objects), _ptr(self.tape),
+                                     _ptr(self.ws_dec), self.ws_dec.numel(), st), "sdfr_decoder_forward")
+        sdf = view_volumes(self.sdf_objects, K, V, out=self.sdf_views)
+        stride = 0 if K == 1 else R ** 3
+        cx, cy, fx, fy = self._intrinsics
+        check(L.sdfr_render_forward(_ptr(sdf), R, stride, _ptr(self.pos_c), _ptr(self.quat_c), _ptr(self.inv_scale), B,
+                                    self.W, self.H, cx, cy, fx, fy, self.threshold, _ptr(self.depth),
+                                    _ptr(self.ws_render), self.ws_render.numel(), d, st), "sdfr_render_forward")
+        if self.shape:
+            check(L.sdfr_decoder_jvp(dec._h, _ptr(self.z), _ptr(self.tape), None, None, K, T, 0, _ptr(self.jac_objects),
+                                     _ptr(self.ws_dec), self.ws_dec.numel(), st), "sdfr_decoder_jvp")
+            jac = view_volumes(self.jac_objects, K, V, out=self.jac_views)
+            jstride = 0 if K == 1 else R ** 3 * self.Tp
+            check(L.sdfr_render_information_shape(
+                _ptr(self.depth), _ptr(self.target), _ptr(sdf), R, stride, _ptr(jac), self.Tp, T, jstride,
+                _ptr(self.pos_c), _ptr(self.quat_c), _ptr(self.inv_scale), B, self.W, self.H, cx, cy, fx, fy,
+                self.inlier_threshold, _ptr(self.gram_trial), _ptr(self.ws_info), self.ws_info.numel(), d, st),
+                "sdfr_render_information_shape")
+        else:
+            check(L.sdfr_render_information(
+                _ptr(self.depth), _ptr(self.target), _ptr(sdf), R, stride, _ptr(self.pos_c), _ptr(self.quat_c),
+                _ptr(self.inv_scale), B, self.W, self.H, cx, cy, fx, fy, self.inlier_threshold, _ptr(self.gram_trial),
+                _ptr(self.ws_info), self.ws_info.numel(), d, st), "sdfr_render_information")
+
+    def solve(self, st=None) -> None:
+        """steps 5-6: ``sdfr_lm_step`` on the trial's Gram matrices, then the new trial's camera-frame poses"""
+        st = _stream(self.dev) if st is None else st
+        c = self.constants
+        _lib.check(self.L.sdfr_lm_step(
+            _ptr(self.gram_trial), _ptr(self.params_trial), _ptr(self.params_cur), _ptr(self.gram_cur),
+            _ptr(self.state), _ptr(self.step), _ptr(self.cam_quat), self.K, self.V, self.T, self.n, int(self._init),
+            self.latent_weight, self.min_overlap, c["lambda0"], c["lambda_up"], c["lambda_down"], c["lambda_min"],
+            c["lambda_max"], c["step_tol"], self.dev.index, st), "sdfr_lm_step")
+        self._init = False
+        self._poses(st)
+
+    def iterate(self, n: int = 1) -> "LMRefiner":
+        """n iterations.  After ``start`` the first one is the ``init`` step: n iterations judge n - 1 trials, and the
+        last solve's trial stays unjudged -- the estimate is ``params_cur``."""
+        st = _stream(self.dev)
+        for _ in range(int(n)):
+            self.evaluate(st)
+            self.solve(st)
+            self.iterations += 1
+        return self
+
+    def report(self) -> LMReport:
+        """the per-object state, read back (ONE device-to-host copy: the only synchronisation of a refinement)"""
+        s = self.state.cpu()
+        col = lambda name: s[:, STATE[name]].clone()
+        return LMReport(initial_cost=col("cost_init"), final_cost=col("cost"), initial_count=col("count_init"),
+                        final_count=col("count"), accepted=col("accepted").long(), rejected=col("rejected").long(),
+                        status=col("status").long(), final_lambda=col("lambda"), step_norm=col("step_norm"),
+                        predicted_reduction=col("predicted"), actual_reduction=col("actual"))

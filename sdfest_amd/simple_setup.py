@@ -62,7 +62,9 @@ class SDFPipeline:
     ``init`` {backbone_type, backbone, head_type, head, normalize_pose, model}, ``vae`` {latent_size, decoder, tsdf,
     model} (or ``init["vae"]``), optionally ``far_field``, ``result_selection_strategy``,
     ``relative_inlier_threshold``, ``orientation_hypotheses`` (N > 1: ``__call__`` refines the N most probable
-    orientation cells side by side and returns the best supported one, ``estimate_hypotheses``; not in the reference).
+    orientation cells side by side and returns the best supported one, ``estimate_hypotheses``; not in the reference),
+    ``gauss_newton_iterations`` (n > 0: ``__call__``, ``estimate_objects``, ``estimate_frames`` and
+    ``estimate_hypotheses`` end with ``refine(n)`` and return the refined estimate; default 0; not in the reference).
     vae_state_dict / init_state_dict: the state dicts of the reference's ``SDFVAE`` (keys ``decoder.*``; encoder
     keys are ignored) and ``SDFPoseNet``; default: ``torch.load`` of ``config[...]["model"]`` if that file exists.
     init_network: an object called like ``nn_init``'s network, or a callable
@@ -115,6 +117,7 @@ class SDFPipeline:
         self._multi_loops, self._resident_objects = BoundedCache(limit), BoundedCache(limit)
         # estimate_hypotheses: per N / the last call's record
         self._resident_hypotheses, self._last_hypotheses = BoundedCache(limit), None
+        self._refiners = BoundedCache(limit)      # refine: per (K, V, shape_optimization)
         self._ignored_warned = False
 
     def _parse_config(self, config: Dict) -> None:
@@ -314,7 +317,7 @@ class SDFPipeline:
         # :583-596 -- "best_inlier_ratio" returns the tensors the reference stored, which its optimiser went on
         # updating in place: the last iterate as well (pipeline._BestEstimate); the snapshot at the best ratio is
         # self.best_estimate()
-        return position, orientation, scale, latent_shape
+        return self._gauss_newton((position, orientation, scale, latent_shape))
 
     def estimate_objects(self, depth_images: torch.Tensor, masks: torch.Tensor,
                          camera_positions: Optional[torch.Tensor] = None,
@@ -400,7 +403,7 @@ class SDFPipeline:
             raise NoDepthError
         if V > 1 and bool((loop.counts == 0).any()):     # (the initialisation saw the first views only)
             raise NoDepthError
-        return out
+        return self._gauss_newton(out)
 
     def estimate_frames(self, depth_images: torch.Tensor, masks: torch.Tensor, shape_optimization: bool = True,
                         prior_orientation_distribution: Optional[torch.Tensor] = None,
@@ -568,6 +571,11 @@ class SDFPipeline:
                 raise NoDepthError
             if V > 1 and bool((loop.counts == 0).any()):
                 raise NoDepthError
+            if int(self.config.get("gauss_newton_iterations", 0)) > 0:
+                # all N rows are refined; the winner stays the one the loop's inlier ratios selected
+                self._gauss_newton(out)
+                row = loop.params.index_select(0, loop.selection["index"].long())[0]
+                out = row[0:3][None].clone(), row[3:7][None].clone(), row[7:8].clone(), row[8:][None].clone()
         return out
 
     def last_hypotheses(self):
@@ -615,21 +623,26 @@ class SDFPipeline:
             return pose_covariance(per_object(info), per_object(gram[:, 8, 8]), per_object(gram[:, 9, 9]), rcond=rcond,
                                    depth_sigma=depth_sigma)
 
-    def _uncertainty_views(self) -> Dict:
-        """the K V views ``pose_uncertainty`` looks at, object-major (view k V + v is object k from camera v, as in the
-        loops): the last loop's targets and cameras, its final parameters as camera-frame poses
-        (pipeline.RenderAndCompare.losses), the decoded volumes and the rendered estimate"""
-        from .differentiable_renderer import forward_raw
+    def _last_rows(self):
+        """(loop, K, params (K, 8 + L)) of the last estimate: the loop that made it and its final parameter rows, a VIEW
+        of the loop's own buffer -- what ``pose_uncertainty``, ``shape_uncertainty`` and ``refine`` start from"""
         loop = getattr(self, "_last_estimate", None)
         if loop is None:
             raise RuntimeError("pose_uncertainty() needs an estimate: call the pipeline (or estimate_objects, "
                                "estimate_frames, estimate_hypotheses) first")
         if isinstance(loop, MultiObjectRenderAndCompare):
-            K, params = loop.K, loop.params
-        else:
-            if loop.group is not None:
-                raise NotImplementedError("pose_uncertainty() after a loop sharded over ranks")
-            K, params = 1, loop.params[None]
+            return loop, loop.K, loop.params
+        if loop.group is not None:
+            raise NotImplementedError("pose_uncertainty() after a loop sharded over ranks")
+        return loop, 1, loop.params[None]
+
+    def _uncertainty_views(self) -> Dict:
+        """the K V views ``pose_uncertainty`` looks at, object-major (view k V + v is object k from camera v, as in the
+        loops): the last loop's targets and cameras, its final parameters as camera-frame poses
+        (pipeline.RenderAndCompare.losses), the decoded volumes and the rendered estimate"""
+        from .differentiable_renderer import forward_raw
+        from .lm import view_volumes
+        loop, K, params = self._last_rows()
         V, cam_pos, cam_quat = loop.V, loop.cam_pos, loop.cam_quat
         H, W = int(self.cam.height), int(self.cam.width)
         with torch.no_grad():
@@ -641,7 +654,7 @@ class SDFPipeline:
             inv_scale = (1.0 / scale)[:, None].expand(K, V).reshape(K * V).contiguous()
             sdf = self.vae.decode(latent.contiguous())[:, 0]
             # one object: its views share the grid; else every view its own copy
-            sdf = (sdf[0] if K == 1 else sdf.repeat_interleave(V, dim=0) if V > 1 else sdf).contiguous()
+            sdf = view_volumes(sdf, K, V).contiguous()
             fx, fy, cx, cy, _ = self.cam.get_pinhole_camera_parameters(0.5)
             depth = forward_raw(sdf, pos_c, quat_c, inv_scale, W, H, cx, cy, fx, fy, self.config["threshold"])
         return dict(K=K, V=V, depth=depth, target=loop.target.reshape(K * V, H, W), sdf=sdf, position=pos_c,
@@ -652,12 +665,13 @@ class SDFPipeline:
         """``_uncertainty_views`` plus the decoder's Jacobians at the K final latents: ``jac`` (K, D^3, Tp) as
         ``SDFDecoder.jvp`` writes it (the identity basis: T = the latent size) and ``jacobian``, what the K V views
         read -- the one buffer where a single object's views share it, else a copy per view, object-major like ``sdf``"""
+        from .lm import view_volumes
         v = self._uncertainty_views()
         with torch.no_grad():
             _, jac = self.vae.decode_jvp(v["latent"])
         K, V = v["K"], v["V"]
         v["jac"], v["T"] = jac, int(v["latent"].shape[1])
-        v["jacobian"] = jac[0] if K == 1 else jac.repeat_interleave(V, dim=0) if V > 1 else jac
+        v["jacobian"] = view_volumes(jac, K, V)
         return v
 
     def shape_uncertainty(self, inlier_threshold=None, rcond: float = 1e-6, depth_sigma: Optional[float] = None,
@@ -693,6 +707,46 @@ class SDFPipeline:
             if sdf_std:
                 rec.sdf_std = U.sdf_std(v["jac"], rec.covariance[:, 7:, 7:], tangents=T)   # (NaN where the row is)
             return rec
+
+    def refine(self, iterations: int = 10, shape_optimization: Optional[bool] = None, inlier_threshold=None,
+               latent_weight: float = 0.0, min_overlap: float = 0.5, **lm):
+        """Finish the last estimate by Levenberg-Marquardt on the squared depth residual (``sdfest_amd.lm``): valid after
+        the same calls as ``pose_uncertainty``, with the same ``RuntimeError`` / ``NotImplementedError`` cases.  The loop is
+        first order and returns the iterate Adam stopped at; the covariance ``pose_uncertainty`` / ``shape_uncertainty``
+        report is that of the MINIMISER of the residual, and this takes the estimate there.  The reference has none.
+
+        From the last loop's final parameters, bound targets and cameras: the start is evaluated, then `iterations` trials
+        are judged, each one launch sequence on the current stream without an allocation or a host synchronisation
+        (``LMRefiner``).  The refined rows are written back into that loop's parameters, so a following
+        ``pose_uncertainty()`` / ``shape_uncertainty()`` is evaluated at them.
+        shape_optimization: None = as the last call; False: the latent is not touched.  inlier_threshold: as
+        ``pose_uncertainty``.  latent_weight: mu of the objective mean r^2 + mu |z|^2.  min_overlap: a trial keeping less
+        than this share of the current pixels is rejected.  ``**lm``: ``lm.LM_DEFAULTS``.
+        Returns ``((position (K,3), orientation (K,4) normalised, scale (K,), latent (K,L)), LMReport)``; the report is
+        read back once, after the last iteration.  ``best_estimates()`` keeps reporting the Adam loop's bookkeeping."""
+        from .lm import LMRefiner, _constants
+        loop, K, params = self._last_rows()
+        shape = bool(loop.shape_opt if shape_optimization is None else shape_optimization)
+        thr = 0.0 if inlier_threshold is None else float(
+            self._relative_inlier_threshold if inlier_threshold is True else inlier_threshold)
+        refiner = self._refiners.get_or_build((K, int(loop.V), shape), lambda: LMRefiner(
+            self, K, int(loop.V), shape, device=self._dev))
+        refiner.inlier_threshold, refiner.latent_weight, refiner.min_overlap = thr, float(latent_weight), float(min_overlap)
+        refiner.constants = _constants(lm)
+        with torch.no_grad():
+            refiner.start(params, loop.target, loop.cam_pos, loop.cam_quat)
+            refiner.iterate(int(iterations) + 1)     # (the first one evaluates the start)
+            params.copy_(refiner.params_cur)
+            rows = refiner.params_cur.clone()
+            orientation = rows[:, 3:7] / torch.linalg.norm(rows[:, 3:7], dim=-1, keepdim=True)
+        self._last_refiner = refiner
+        return (rows[:, 0:3], orientation, rows[:, 7], rows[:, 8:]), refiner.report()
+
+    def _gauss_newton(self, estimate: tuple) -> tuple:
+        """config key ``gauss_newton_iterations`` (default 0: `estimate` as it is): the estimation calls end with
+        ``refine`` of that many iterations and return its rows"""
+        n = int(self.config.get("gauss_newton_iterations", 0))
+        return self.refine(n)[0] if n > 0 else estimate
 
     def best_estimates(self):
         """K entries (ratio, 1-based iteration, (position, orientation, scale, latent)), one per object: the parameters
