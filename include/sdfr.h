@@ -98,6 +98,9 @@
  *        sdfr_decoder_jvp[_workspace_bytes], sdfr_sdf_std
  *  18. [unstable] LM REFINEMENT: a damped Gauss-Newton step of pose and latent from those Gram matrices (SDFPipeline.refine)
  *        sdfr_lm_step
+ *  19. [unstable] POINT-CLOUD INFORMATION: the Gauss-Newton normal matrix of the point-cloud residual, and its sum with
+ *      the depth term's for group 18 (LMRefiner(pc_weight=), SDFPipeline.refine(pc_weight=))
+ *        sdfr_pc_information[_workspace_bytes], sdfr_information_combine
  * (Within the file the groups follow the order in which the reference's code runs; every declaration carries the
  * reference file:line it replaces.)
  */
@@ -1815,6 +1818,64 @@ SDFR_API int sdfr_lm_step(const double* gram_trial, float* params_trial, float* 
                           int n_params, int init, double latent_weight, double min_overlap, double lambda0,
                           double lambda_up, double lambda_down, double lambda_min, double lambda_max, double step_tol,
                           int device, void* stream);
+
+/* ==== 19. POINT-CLOUD INFORMATION ============================================================= */
+/* ---- the Gauss-Newton information of the point-cloud residual.  The loop of group 3 minimises the depth L1 PLUS the
+ * point-cloud loss (simple_setup.py:133-144: the observed points must lie on the zero set of the posed SDF); the Gram
+ * matrices of groups 14 / 17, and so sdfr_lm_step, see the depth residual alone, which is summed over a pixel set that
+ * changes with the iterate.  This is the matrix of the other half, summed over the FIXED set of observed points, in the
+ * same 8 + T coordinates and the same layout.  The reference has neither.
+ *   points, offsets, max_view_points, pos, quat, scale, sdf, R, sdf_view_stride: exactly sdfr_pc_loss_forward's (group 1;
+ *       `scale`, not inv_scale, as the sampler takes it; offsets may be NULL for a single view of max_view_points points)
+ *   jac, Tp, T, jac_view_stride: exactly sdfr_render_information_shape's (group 14).  T = 0: pose only, jac may be NULL
+ *       and Tp is ignored; otherwise 1 <= T <= 22, Tp a multiple of 4 and >= T.  F = 10 + T.
+ *   gram    [B][F][F] doubles, overwritten: per view the Gram matrix over ALL M_v points of the view of
+ *       f = (e0 .. e7, s0 .. s_{T-1}, r, 1):
+ *         r        the point's value as sdfr_pc_loss_forward writes it (0 outside the volume)
+ *         e0..e2   d r / d p;   e3..e6  d r / d q of the RAW quaternion, through the normalisation: with a = d r / d q^,
+ *                  (a - q^ (q^ . a)) / |q|;   e7  d r / d inv_scale = -scale^2 d r / d scale -- group 14's coordinate, so
+ *                  that the tangent map of sdfr_lm_step applies unchanged
+ *         s_t      scale * trilerp(jac[.][t]) at the point's cell with the point's offsets
+ *       A point outside the volume has f = (0, .., 0, 0, 1): it is a member of the reference's mean with residual 0
+ *       (losses.py:134, simple_setup.py:144) and gets no gradient.
+ *       [:8+T][:8+T] = J^T J, [:8+T][8+T] = J^T r, [8+T][8+T] = sum r^2, [9+T][9+T] = M_v exactly; symmetric bit for bit;
+ *       all zeros for a view without points.
+ *   inside  [B] ints or NULL: the number of the view's points inside the volume (exact)
+ *   workspace: sdfr_pc_information_workspace_bytes(B, max_view_points, T) bytes = B min(nblk, G) F F floats with
+ *       nblk = ceil(max_view_points / 256) and G = 64 (pc_information.hip), 128-byte aligned; it may hold anything on entry.
+ * Two launches on `stream` (three with `inside`: its zero fill): workgroup g of a view takes the view's 256-point blocks
+ * g, g + G, ... -- 32 v_mfma_f32_32x32x2_f32 per 64 points into accumulators that stay live across them (the longest
+ * fp32 chain is 64 ceil(nb_v / G) points) --, the four waves are summed as (0 + 1) + (2 + 3) into one float record, and
+ * the second launch sums a view's min(nb_v, G) records in record order in double.  Every sum has one order: the same
+ * inputs give the same bits, and a view's matrix depends neither on B, nor on the other views, nor on max_view_points.
+ * The per-point derivative expressions are those of the sampler's backward (sdfr_pc_loss_backward) with upstream
+ * gradient 1.  B <= 65535, max_view_points <= 2^30, 2 <= R <= 1024; gram 8-byte, jac (and its stride) 16-byte aligned.
+ * Every error is SDFR_E_INVALID with a message, before anything touches the GPU: a NULL pointer other than `inside`
+ * (or jac at T = 0), a short or misaligned workspace.  Not an error, returns 0: B = 0 (nothing is written), and
+ * max_view_points = 0 (gram and inside are zeroed).  _workspace_bytes returns 0 for sizes the call refuses. */
+SDFR_API size_t sdfr_pc_information_workspace_bytes(int B, int max_view_points, int T);
+SDFR_API int sdfr_pc_information(const float* points, const int* offsets /* nullable */, int B, int max_view_points,
+                                 const float* pos, const float* quat, const float* scale, const float* sdf, int R,
+                                 long long sdf_view_stride, const float* jac /* nullable with T = 0 */, int Tp, int T,
+                                 long long jac_view_stride, double* gram, int* inside /* nullable */, void* workspace,
+                                 size_t workspace_bytes, int device, void* stream);
+
+/* ---- depth and point-cloud Gram matrices of K objects with V views each, added for sdfr_lm_step (which stays as it is:
+ * its cost is rss / cnt).  The combined objective is
+ *     Phi = sum_v rss_d / sum_v cnt_d + pc_weight sum_v rss_p / sum_v M_v + mu |z|^2
+ * -- the squared counterpart of what the loop minimises.  Per object k, views ascending, IEEE double without contraction,
+ * in this order (F = 10 + T; Gd, Gp the [K V][F][F] inputs, object-major):
+ *     cd = sum_v Gd[k V + v][F-1][F-1];  cp = sum_v Gp[k V + v][F-1][F-1]
+ *     alpha = (cd > 0 && cp > 0) ? (pc_weight cd) / cp : 0
+ *     out[i][j] = Gd[i][j] + alpha Gp[i][j]  for i, j < F - 1 (the product is rounded, then the sum);
+ *     row and column F - 1 are copied from Gd
+ * Then out[8+T][8+T] / cd is Phi's data part and H, g of sdfr_lm_step are those of Phi; the count stays the depth term's,
+ * so min_overlap means what it meant.  gram_out may be gram_depth (in place).  Entries that are not finite propagate (the
+ * step then reports SDFR_LM_NO_SYSTEM).  One launch, no workspace; object k depends neither on K nor on the other
+ * objects.  1 <= K <= 65535, 1 <= V <= 64, 0 <= T <= 22, pc_weight finite and >= 0, the matrices 8-byte aligned; every
+ * error is SDFR_E_INVALID with a message before anything touches the GPU. */
+SDFR_API int sdfr_information_combine(const double* gram_depth, const double* gram_pc, int K, int V, int T,
+                                      double pc_weight, double* gram_out, int device, void* stream);
 
 #ifdef __cplusplus
 }

@@ -11,8 +11,11 @@ solve, the retraction and the status, one wave per object.  The reference has ne
 allocation or a host synchronisation; ``SDFPipeline.refine`` starts it from the last estimate.
 
 Objective: the MEAN squared depth residual over the included pixels plus ``latent_weight |z|^2``; a mean because the
-included pixels change from iterate to iterate and a sum would reward losing overlap.  The iteration is eager; its
-sequence has no host synchronisation and could be captured into a graph, which is not done here."""
+included pixels change from iterate to iterate and a sum would reward losing overlap.  With ``pc_weight`` = w > 0 the
+point-cloud term joins it, Phi = mean r_depth^2 + w mean r_pc^2 + mu |z|^2 with r_pc the posed SDF at the observed
+points (all of them: a point outside the volume counts with residual 0) -- the squared counterpart of what the Adam loop
+minimises; ``sdfr_pc_information`` and ``sdfr_information_combine`` (group 19) hand ``sdfr_lm_step`` the sum.  The
+iteration is eager; its sequence has no host synchronisation and could be captured into a graph, which is not done here."""
 from dataclasses import dataclass
 from typing import Optional
 
@@ -96,7 +99,8 @@ def view_volumes(per_object: torch.Tensor, K: int, V: int, out: Optional[torch.T
 @dataclass
 class LMReport:
     """What ``LMRefiner.report`` reads back, per object (leading dimension K, CPU tensors, float64 but ``status`` and the
-    counters): the cost Phi and the pixel count at the start and at the current iterate, the accepted and rejected
+    counters): the cost Phi (of the refiner's mode: with ``pc_weight`` > 0 the combined one) and the depth term's pixel
+    count at the start and at the current iterate, the accepted and rejected
     trials, the status (``lm.RUNNING`` / ``CONVERGED`` / ``STALLED`` / ``NO_SYSTEM``), the damping, the last step's scaled
     norm and the last predicted and actual reduction of Phi."""
     initial_cost: torch.Tensor
@@ -119,18 +123,24 @@ class LMRefiner:
     threshold)``.  shape: the latent is part of the step (T = the latent size, at most 22) or held fixed (T = 0).
     inlier_threshold: ``render_information``'s; latent_weight: mu of the objective; min_overlap: a trial that keeps less
     than this share of the current iterate's pixels is rejected; ``**lm``: ``LM_DEFAULTS``.
+    pc_weight: w of Phi = mean r_depth^2 + w mean r_pc^2 + mu |z|^2.  0 (the default): Phi is the depth term's, no
+    further buffer is allocated and no further launch issued -- every result keeps its bits.  w > 0: the observed points
+    are the back-projected pixels of the bound target (``start`` makes them once, on the device), and every evaluation
+    adds ``sdfr_pc_information`` at the trial poses and ``sdfr_information_combine``; ``gram_depth_trial`` and
+    ``gram_pc_trial`` keep the two terms, ``gram_trial`` their combination, whose costs ``report`` returns.
 
     Everything an iteration touches is allocated here, once: the current and trial rows, the two sets of Gram matrices,
     the state, the decoder's tape and Jacobian, the depth images and the workspaces.  ``start`` binds an observation and
     a start; ``iterate(n)`` runs n iterations, each the launch sequence
         batched decode of the K trial latents (with its tape), the forward render of the K V views,
         ``sdfr_decoder_jvp`` (shape only), ``sdfr_render_information[_shape]`` into the trial's Gram matrices,
+        (pc_weight > 0: ``sdfr_pc_information``, ``sdfr_information_combine``,)
         ``sdfr_lm_step``, ``sdfr_pose_to_views_objects`` for the new trial
     on the current stream, without an allocation or a host synchronisation.  The first iteration after ``start`` is the
     ``init`` call that evaluates the start; the Jacobian of a trial that ends up rejected is wasted work."""
 
     def __init__(self, pipeline_or_parts, K: int, V: int, shape: bool, inlier_threshold: float = 0.0,
-                 latent_weight: float = 0.0, min_overlap: float = 0.5, device=None, **lm):
+                 latent_weight: float = 0.0, min_overlap: float = 0.5, device=None, pc_weight: float = 0.0, **lm):
         if isinstance(pipeline_or_parts, (tuple, list)):
             vae, camera, threshold = pipeline_or_parts
         else:
@@ -152,6 +162,9 @@ class LMRefiner:
         self.n = 8 + self.Lz
         self.inlier_threshold, self.latent_weight, self.min_overlap = (float(inlier_threshold), float(latent_weight),
                                                                        float(min_overlap))
+        self.pc_weight = float(pc_weight)
+        if not 0.0 <= self.pc_weight < float("inf"):
+            raise ValueError(f"pc_weight = {pc_weight} must be finite and >= 0")
         self.constants = _constants(lm)
         B, H, W = self.B, int(camera.height), int(camera.width)
         self.H, self.W = H, W
@@ -192,6 +205,21 @@ class LMRefiner:
         self.ws_info = torch.empty(max(info, 256), **u8)
         fx, fy, cx, cy, _ = camera.get_pinhole_camera_parameters(0.5)
         self._intrinsics = (float(cx), float(cy), float(fx), float(fy))
+        self.gram_depth_trial = self.gram_pc_trial = None
+        if self.pc_weight > 0.0:
+            # the observed points at capacity, counts and offsets on the device (as the loop's, pipeline.py)
+            i32 = dict(dtype=torch.int32, device=dev)
+            self.max_pts = W * H
+            self.points = torch.zeros((B * W * H, 3), **f32)
+            self.counts, self.offsets = torch.zeros(B, **i32), torch.zeros(B + 1, **i32)
+            self.ws_points = torch.empty(max(L.sdfr_depth_points_workspace_bytes(B, W, H), 256), **u8)
+            self.gram_depth_trial, self.gram_pc_trial = torch.zeros((B, F, F), **f64), torch.zeros((B, F, F), **f64)
+            pc = L.sdfr_pc_information_workspace_bytes(B, self.max_pts, T)
+            if pc == 0:
+                raise ValueError(f"the point-cloud information call refuses {B} views of {self.max_pts} points")
+            self.ws_pc = torch.empty(max(pc, 256), **u8)
+            fx0, fy0, cx0, cy0, _ = camera.get_pinhole_camera_parameters(0.0)
+            self._point_intrinsics = (1.0 / float(fx0), 1.0 / float(fy0), float(cx0), float(cy0))
         self._init = True
         self.iterations = 0
 
@@ -213,6 +241,13 @@ class LMRefiner:
                 self.cam_quat.zero_()
                 self.cam_quat[:, 3] = 1.0
             self._poses(_stream(self.dev))
+            if self.pc_weight > 0.0:
+                # the bound target's point clouds, once: the order and the intrinsics of the loop's (pipeline.py)
+                rfx, rfy, cx0, cy0 = self._point_intrinsics
+                _lib.check(self.L.sdfr_depth_to_points_resident(
+                    _ptr(self.target), self.B, self.W, self.H, _lib.ABI["SDFR_POINT_ORDER_TILED"], rfx, rfy, cx0, cy0,
+                    _ptr(self.counts), _ptr(self.offsets), _ptr(self.ws_points), self.ws_points.numel(),
+                    _ptr(self.points), self.dev.index, _stream(self.dev)), "sdfr_depth_to_points_resident")
         self._init = True
         self.iterations = 0
         return self
@@ -225,7 +260,9 @@ class LMRefiner:
             "sdfr_pose_to_views_objects")
 
     def evaluate(self, st=None) -> None:
-        """steps 1-4 of an iteration: decode, render, Jacobian and Gram matrices of the trial rows"""
+        """steps 1-4 of an iteration: decode, render, Jacobian and Gram matrices of the trial rows (pc_weight > 0: the
+        depth term's into ``gram_depth_trial``, the point-cloud term's into ``gram_pc_trial``, their combination into
+        ``gram_trial``)"""
         L, dec, K, V, B, R, T = self.L, self.dec, self.K, self.V, self.B, self.R, self.T
         st = _stream(self.dev) if st is None else st
         d = self.dev.index
@@ -235,6 +272,9 @@ class LMRefiner:
         sdf = view_volumes(self.sdf_objects, K, V, out=self.sdf_views)
         stride = 0 if K == 1 else R ** 3
         cx, cy, fx, fy = self._intrinsics
+        pc = self.pc_weight > 0.0
+        gram = self.gram_depth_trial if pc else self.gram_trial
+        jac, jstride = None, 0
         check(L.sdfr_render_forward(_ptr(sdf), R, stride, _ptr(self.pos_c), _ptr(self.quat_c), _ptr(self.inv_scale), B,
                                     self.W, self.H, cx, cy, fx, fy, self.threshold, _ptr(self.depth),
                                     _ptr(self.ws_render), self.ws_render.numel(), d, st), "sdfr_render_forward")
@@ -246,13 +286,20 @@ class LMRefiner:
             check(L.sdfr_render_information_shape(
                 _ptr(self.depth), _ptr(self.target), _ptr(sdf), R, stride, _ptr(jac), self.Tp, T, jstride,
                 _ptr(self.pos_c), _ptr(self.quat_c), _ptr(self.inv_scale), B, self.W, self.H, cx, cy, fx, fy,
-                self.inlier_threshold, _ptr(self.gram_trial), _ptr(self.ws_info), self.ws_info.numel(), d, st),
+                self.inlier_threshold, _ptr(gram), _ptr(self.ws_info), self.ws_info.numel(), d, st),
                 "sdfr_render_information_shape")
         else:
             check(L.sdfr_render_information(
                 _ptr(self.depth), _ptr(self.target), _ptr(sdf), R, stride, _ptr(self.pos_c), _ptr(self.quat_c),
-                _ptr(self.inv_scale), B, self.W, self.H, cx, cy, fx, fy, self.inlier_threshold, _ptr(self.gram_trial),
+                _ptr(self.inv_scale), B, self.W, self.H, cx, cy, fx, fy, self.inlier_threshold, _ptr(gram),
                 _ptr(self.ws_info), self.ws_info.numel(), d, st), "sdfr_render_information")
+        if pc:
+            check(L.sdfr_pc_information(
+                _ptr(self.points), _ptr(self.offsets), B, self.max_pts, _ptr(self.pos_c), _ptr(self.quat_c),
+                _ptr(self.scale_v), _ptr(sdf), R, stride, _ptr(jac), self.Tp, T, jstride, _ptr(self.gram_pc_trial), None,
+                _ptr(self.ws_pc), self.ws_pc.numel(), d, st), "sdfr_pc_information")
+            check(L.sdfr_information_combine(_ptr(gram), _ptr(self.gram_pc_trial), K, V, T, self.pc_weight,
+                                             _ptr(self.gram_trial), d, st), "sdfr_information_combine")
 
     def solve(self, st=None) -> None:
         """steps 5-6: ``sdfr_lm_step`` on the trial's Gram matrices, then the new trial's camera-frame poses"""

@@ -64,7 +64,8 @@ class SDFPipeline:
     ``relative_inlier_threshold``, ``orientation_hypotheses`` (N > 1: ``__call__`` refines the N most probable
     orientation cells side by side and returns the best supported one, ``estimate_hypotheses``; not in the reference),
     ``gauss_newton_iterations`` (n > 0: ``__call__``, ``estimate_objects``, ``estimate_frames`` and
-    ``estimate_hypotheses`` end with ``refine(n)`` and return the refined estimate; default 0; not in the reference).
+    ``estimate_hypotheses`` end with ``refine(n)`` and return the refined estimate; default 0; not in the reference),
+    ``gauss_newton_pc_weight`` (the weight of the point-cloud term in ``refine``'s objective; default 0.0: none).
     vae_state_dict / init_state_dict: the state dicts of the reference's ``SDFVAE`` (keys ``decoder.*``; encoder
     keys are ignored) and ``SDFPoseNet``; default: ``torch.load`` of ``config[...]["model"]`` if that file exists.
     init_network: an object called like ``nn_init``'s network, or a callable
@@ -117,7 +118,7 @@ class SDFPipeline:
         self._multi_loops, self._resident_objects = BoundedCache(limit), BoundedCache(limit)
         # estimate_hypotheses: per N / the last call's record
         self._resident_hypotheses, self._last_hypotheses = BoundedCache(limit), None
-        self._refiners = BoundedCache(limit)      # refine: per (K, V, shape_optimization)
+        self._refiners = BoundedCache(limit)      # refine: per (K, V, shape_optimization, point-cloud term on / off)
         self._ignored_warned = False
 
     def _parse_config(self, config: Dict) -> None:
@@ -709,7 +710,7 @@ class SDFPipeline:
             return rec
 
     def refine(self, iterations: int = 10, shape_optimization: Optional[bool] = None, inlier_threshold=None,
-               latent_weight: float = 0.0, min_overlap: float = 0.5, **lm):
+               latent_weight: float = 0.0, min_overlap: float = 0.5, pc_weight: Optional[float] = None, **lm):
         """Finish the last estimate by Levenberg-Marquardt on the squared depth residual (``sdfest_amd.lm``): valid after
         the same calls as ``pose_uncertainty``, with the same ``RuntimeError`` / ``NotImplementedError`` cases.  The loop is
         first order and returns the iterate Adam stopped at; the covariance ``pose_uncertainty`` / ``shape_uncertainty``
@@ -721,7 +722,9 @@ class SDFPipeline:
         ``pose_uncertainty()`` / ``shape_uncertainty()`` is evaluated at them.
         shape_optimization: None = as the last call; False: the latent is not touched.  inlier_threshold: as
         ``pose_uncertainty``.  latent_weight: mu of the objective mean r^2 + mu |z|^2.  min_overlap: a trial keeping less
-        than this share of the current pixels is rejected.  ``**lm``: ``lm.LM_DEFAULTS``.
+        than this share of the current pixels is rejected.  pc_weight: w > 0 adds the point-cloud term of the loop's
+        objective, w mean r_pc^2 over the bound targets' back-projected points (``LMRefiner``); None reads the config key
+        ``gauss_newton_pc_weight`` (default 0.0: the depth term alone, as before).  ``**lm``: ``lm.LM_DEFAULTS``.
         Returns ``((position (K,3), orientation (K,4) normalised, scale (K,), latent (K,L)), LMReport)``; the report is
         read back once, after the last iteration.  ``best_estimates()`` keeps reporting the Adam loop's bookkeeping."""
         from .lm import LMRefiner, _constants
@@ -729,8 +732,13 @@ class SDFPipeline:
         shape = bool(loop.shape_opt if shape_optimization is None else shape_optimization)
         thr = 0.0 if inlier_threshold is None else float(
             self._relative_inlier_threshold if inlier_threshold is True else inlier_threshold)
-        refiner = self._refiners.get_or_build((K, int(loop.V), shape), lambda: LMRefiner(
-            self, K, int(loop.V), shape, device=self._dev))
+        w = float(self.config.get("gauss_newton_pc_weight", 0.0) if pc_weight is None else pc_weight)
+        if not 0.0 <= w < float("inf"):
+            raise ValueError(f"pc_weight = {w} must be finite and >= 0")
+        # (a refiner with the point-cloud term owns more buffers: "pc on / off" is part of the key, the weight is not)
+        refiner = self._refiners.get_or_build((K, int(loop.V), shape, w > 0.0), lambda: LMRefiner(
+            self, K, int(loop.V), shape, device=self._dev, pc_weight=w))
+        refiner.pc_weight = w
         refiner.inlier_threshold, refiner.latent_weight, refiner.min_overlap = thr, float(latent_weight), float(min_overlap)
         refiner.constants = _constants(lm)
         with torch.no_grad():
@@ -744,7 +752,8 @@ class SDFPipeline:
 
     def _gauss_newton(self, estimate: tuple) -> tuple:
         """config key ``gauss_newton_iterations`` (default 0: `estimate` as it is): the estimation calls end with
-        ``refine`` of that many iterations and return its rows"""
+        ``refine`` of that many iterations and return its rows; ``gauss_newton_pc_weight`` (default 0.0) is the weight of
+        the point-cloud term in that refinement's objective"""
         n = int(self.config.get("gauss_newton_iterations", 0))
         return self.refine(n)[0] if n > 0 else estimate
 

@@ -101,6 +101,103 @@ def render_information(depth: torch.Tensor, target: torch.Tensor, sdf: torch.Ten
     return gram
 
 
+def pc_information(points: torch.Tensor, offsets: Optional[torch.Tensor], sdf: torch.Tensor, position: torch.Tensor,
+                   orientation: torch.Tensor, scale: torch.Tensor, jacobian: Optional[torch.Tensor] = None,
+                   tangents: Optional[int] = None, max_view_points: Optional[int] = None,
+                   workspace: Optional[torch.Tensor] = None, return_inside: bool = False):
+    """(B,F,F) float64, F = 10 + T: per view the Gram matrix of f = (d r / d (px,py,pz,qx,qy,qz,qw,inv_scale),
+    s0 .. s_{T-1}, r, 1) over ALL points of the view, r the point-cloud residual -- the posed SDF at the observed point,
+    what ``pc_loss`` returns; 0 and no gradient outside the volume -- (``sdfr_pc_information``).
+
+    ``points`` (N,3) float32 packed view after view, ``offsets`` (B+1,) int32 (view v owns [offsets[v], offsets[v+1]));
+    None: one view of all N points); the pose has ``render_information``'s shapes, with ``scale`` () or (B,) where that
+    takes inv_scale -- the derivative's coordinate is inv_scale all the same, so ``tangent_information`` /
+    ``joint_tangent_information`` apply to the result as they are; ``sdf`` (R,R,R) shared or (B,R,R,R); ``jacobian`` /
+    ``tangents`` as ``render_information`` (T = 0 without).  ``max_view_points``: an upper bound of every view's count
+    that the caller knows without reading ``offsets`` back (default: N).  ``[:8+T,:8+T]`` is J^T J, ``[:8+T,8+T]`` J^T r,
+    ``[8+T,8+T]`` sum r^2, ``[9+T,9+T]`` the view's point count.  Exactly symmetric, the same bits on every call, a view
+    does not depend on its batch.  ``return_inside``: also the (B,) int32 counts of the points inside the volume."""
+    _check_inputs((points, "points"), (sdf, "sdf"), (position, "position"), (orientation, "orientation"),
+                  (scale, "scale"))
+    pos, quat, sc = position.reshape(-1, 3), orientation.reshape(-1, 4), scale.reshape(-1)
+    B = pos.shape[0]
+    if quat.shape[0] != B or sc.shape[0] != B:
+        raise RuntimeError("expected position (B,3), orientation (B,4), scale (B,)")
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise RuntimeError("points must be (N,3)")
+    N = points.shape[0]
+    if offsets is None:
+        if B != 1:
+            raise RuntimeError("offsets may be None only for a single view")
+    elif not (offsets.is_cuda and offsets.is_contiguous() and offsets.dtype is torch.int32 and tuple(offsets.shape) == (B + 1,)):
+        raise RuntimeError(f"offsets must be a contiguous int32 CUDA tensor of shape ({B + 1},)")
+    M = N if max_view_points is None else int(max_view_points)
+    if offsets is None and M != N:
+        raise RuntimeError("without offsets max_view_points is the number of points")
+    R = sdf.shape[-1]
+    if sdf.dim() == 3:
+        stride = 0
+    elif sdf.dim() == 4 and sdf.shape[0] == B:
+        stride = R * R * R
+    else:
+        raise RuntimeError("sdf must be (R,R,R) or (B,R,R,R)")
+    if tuple(sdf.shape[-3:]) != (R, R, R):
+        raise RuntimeError("sdf must be cubic")
+    Tp = T = jstride = 0
+    if jacobian is not None:
+        _check_inputs((jacobian, "jacobian"))
+        Tp = jacobian.shape[-1]
+        T = Tp if tangents is None else int(tangents)
+        if jacobian.dim() == 2 and jacobian.shape[0] == R ** 3:
+            jstride = 0
+        elif jacobian.dim() == 3 and tuple(jacobian.shape[:2]) == (B, R ** 3):
+            jstride = R ** 3 * Tp
+        else:
+            raise RuntimeError("jacobian must be (R^3, Tp) or (B, R^3, Tp)")
+        if T < 1:
+            raise RuntimeError("tangents must be >= 1 with a jacobian")
+    dev = sdf.device
+    L = _lib.lib()
+    ws = None
+    if B > 0 and M > 0:
+        nbytes = L.sdfr_pc_information_workspace_bytes(B, M, T)
+        if workspace is None and nbytes:
+            workspace = _workspace(dev, nbytes)
+        ws = _lib.workspace(nbytes, "sdfr_pc_information_workspace_bytes", dev, workspace)
+    gram = torch.empty((B, GRAM_SIZE + T, GRAM_SIZE + T), dtype=torch.float64, device=dev)
+    inside = torch.empty(B, dtype=torch.int32, device=dev) if return_inside else None
+    rc = L.sdfr_pc_information(_ptr(points), _ptr(offsets), B, M, _ptr(pos), _ptr(quat), _ptr(sc), _ptr(sdf), R, stride,
+                               _ptr(jacobian), Tp, T, jstride, _ptr(gram), _ptr(inside), _ptr(ws),
+                               0 if ws is None else ws.numel(), dev.index, _stream(dev))
+    _lib.check(rc, "sdfr_pc_information")
+    return (gram, inside) if return_inside else gram
+
+
+def combine_information(gram_depth: torch.Tensor, gram_pc: torch.Tensor, views: int, pc_weight: float,
+                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(K V, F, F) float64: the Gram matrices of the combined objective
+    ``sum rss_d / sum cnt_d + pc_weight sum rss_p / sum M`` of K objects with ``views`` views each, object-major, in the
+    form ``lm_step`` takes (``sdfr_information_combine``): per object ``gram_depth + alpha gram_pc`` with
+    ``alpha = pc_weight cnt_d / M`` (0 where either count is 0) on all but the last row and column, which stay
+    ``gram_depth``'s -- the count is the depth term's.  ``out`` may be ``gram_depth`` (in place); default: a new tensor."""
+    V = int(views)
+    F = gram_depth.shape[-1]
+    if out is None:
+        out = torch.empty_like(gram_depth)
+    for t, name in ((gram_depth, "gram_depth"), (gram_pc, "gram_pc"), (out, "out")):
+        if not (t.is_cuda and t.is_contiguous() and t.dtype is torch.float64 and t.dim() == 3
+                and tuple(t.shape) == tuple(gram_depth.shape) and t.shape[-2] == F):
+            raise RuntimeError(f"{name} must be a contiguous float64 CUDA tensor of shape (K V, F, F), got "
+                               f"{t.dtype} {tuple(t.shape)}")
+    if V < 1 or gram_depth.shape[0] % V:
+        raise RuntimeError(f"{gram_depth.shape[0]} matrices are not K objects of {V} views")
+    dev = gram_depth.device
+    rc = _lib.lib().sdfr_information_combine(_ptr(gram_depth), _ptr(gram_pc), gram_depth.shape[0] // V, V,
+                                             F - GRAM_SIZE, float(pc_weight), _ptr(out), dev.index, _stream(dev))
+    _lib.check(rc, "sdfr_information_combine")
+    return out
+
+
 def _quaternion_multiply(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     ax, ay, az, aw = torch.unbind(a, -1)
     bx, by, bz, bw = torch.unbind(b, -1)
