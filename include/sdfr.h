@@ -1573,10 +1573,11 @@ SDFR_API int sdfr_render_information(const float* depth, const float* target, co
  *           rounding of a different summation block), [8:8+T][8:8+T] the latent block, [:8+T][8+T] = J^T r,
  *           [8+T][8+T] = sum r^2, [9+T][9+T] the exact count; exactly symmetric; all zeros for a view without an included
  *           pixel
- * 1 <= T <= 22: F <= 32 is one 32 x 32 block of the matrix cores.  Everything else -- the two launches, the fixed-order
+ * 1 <= T <= SDFR_INFO_MAX_TANGENTS: F <= 32 is one 32 x 32 block of the matrix cores.  Everything else -- the two launches, the fixed-order
  * sums, "a view does not depend on its batch", "the workspace may hold anything on entry", the limits and the argument
  * errors (all SDFR_E_INVALID before anything touches the GPU; T = 23, a Tp that is no multiple of 4 or below T, a
  * misaligned jac) -- as sdfr_render_information. */
+#define SDFR_INFO_MAX_TANGENTS 22 /* 10 + T <= 32; the T of groups 17, 18 and 19 has the same limit */
 SDFR_API size_t sdfr_render_information_shape_workspace_bytes(int B, int W, int H, int T);
 SDFR_API int sdfr_render_information_shape(const float* depth, const float* target, const float* sdf, int R,
                                            long long sdf_view_stride, const float* jac, int Tp, int T,
@@ -1725,7 +1726,7 @@ SDFR_API int sdfr_ap_integrate(const unsigned char* matched, int T, int P, const
  *            The layout is written by the last step itself (the final resize, or the last convolution), no transpose.
  * fp32 fmaf chains in a fixed order (channels, then taps ascending), no atomics: the same bits on every call, and
  * row (n, .) does not depend on the other latents of the call.  The swapped 1x1x1 layer and the resizes are linear and
- * pass unchanged.  Kernels only on `stream`, no allocation, no host synchronisation.  1 <= T <= 22 (group 14),
+ * pass unchanged.  Kernels only on `stream`, no allocation, no host synchronisation.  1 <= T <= SDFR_INFO_MAX_TANGENTS (group 14),
  * N T <= 65535.  Errors before anything touches the GPU: SDFR_E_NULL (a pointer), SDFR_E_INVALID (N, T, a NULL
  * `tangents` with T != latent, a misaligned jac), SDFR_E_WORKSPACE; _workspace_bytes answers 0 for what the call refuses. */
 SDFR_API size_t sdfr_decoder_jvp_workspace_bytes(const sdfr_decoder* decoder, int N, int T);
@@ -1738,7 +1739,7 @@ SDFR_API int sdfr_decoder_jvp(const sdfr_decoder* decoder, const float* z, const
  * directions): out[k][voxel] = sqrt(max(0, j^T S_k j)), j = jac[k][voxel][:T].
  *   jac        [K][voxels][Tp] as above; covariance [K][T][T] doubles; out [K][voxels] floats, overwritten
  * One thread per voxel, the covariance in LDS, fp64 sums in a fixed order.  1 <= K <= 65535, 1 <= voxels <= 2^31,
- * 1 <= T <= 22, Tp >= T a multiple of 4, jac 16-byte and covariance 8-byte aligned; every argument error is
+ * 1 <= T <= SDFR_INFO_MAX_TANGENTS, Tp >= T a multiple of 4, jac 16-byte and covariance 8-byte aligned; every argument error is
  * SDFR_E_INVALID before anything touches the GPU. */
 SDFR_API int sdfr_sdf_std(const float* jac, int K, long long voxels, int Tp, int T, const double* covariance,
                           float* out, int device, void* stream);
@@ -1751,7 +1752,7 @@ SDFR_API int sdfr_sdf_std(const float* jac, int K, long long voxels, int Tp, int
  * the normal equations at the current iterate in the world tangent, solves them and writes the next trial rows;
  * sdfr_pose_to_views_objects (group 3) then gives that trial's camera-frame poses and packed latents for the next render.
  *   gram_trial   [K V][F][F] doubles, F = 10 + T, object-major (view k V + v): what sdfr_render_information (T = 0) or
- *                sdfr_render_information_shape (1 <= T <= 22) wrote for the rows of params_trial; read only
+ *                sdfr_render_information_shape (T >= 1) wrote for the rows of params_trial; read only
  *   params_trial [K][n_params] floats: position 3 | orientation 4 (x, y, z, w) | scale 1 | latent ...; read as the rows
  *                the Gram matrices were evaluated at, overwritten with the NEXT trial (entries 8 + T .. are the current
  *                row's: with T = 0 the latent is never touched)
@@ -1791,9 +1792,11 @@ SDFR_API int sdfr_sdf_std(const float* jac, int K, long long voxels, int Tp, int
  * (n = 7 + T <= 29: 6.7 KB) live in LDS; no workspace, no allocation, no host synchronisation.  Every sum has one order:
  * two calls on the same inputs give the same bits, and row k depends neither on K nor on the other rows.  On init the
  * current buffers and the state may hold anything.
- * 1 <= K <= 65535, 1 <= V <= 64, T = 0 or 1 <= T <= 22, 8 + T <= n_params <= 65535; the double buffers 8-byte aligned;
+ * 1 <= K <= 65535, 1 <= V <= SDFR_LM_MAX_VIEWS, 0 <= T <= SDFR_INFO_MAX_TANGENTS (group 14), 8 + T <= n_params <= 65535; the
+ * double buffers 8-byte aligned;
  * every scalar finite and >= 0.  Errors before anything touches the GPU: SDFR_E_NULL (a pointer other than step),
  * SDFR_E_INVALID (everything else), with a message. */
+#define SDFR_LM_MAX_VIEWS 64 /* views per object, here and in sdfr_information_combine (group 19) */
 #define SDFR_LM_STATE_DOUBLES 16
 #define SDFR_LM_LAMBDA 0        /* the damping the NEXT solve uses (the last one used, once frozen) */
 #define SDFR_LM_COST 1          /* Phi of the current iterate */
@@ -1828,7 +1831,7 @@ SDFR_API int sdfr_lm_step(const double* gram_trial, float* params_trial, float* 
  *   points, offsets, max_view_points, pos, quat, scale, sdf, R, sdf_view_stride: exactly sdfr_pc_loss_forward's (group 1;
  *       `scale`, not inv_scale, as the sampler takes it; offsets may be NULL for a single view of max_view_points points)
  *   jac, Tp, T, jac_view_stride: exactly sdfr_render_information_shape's (group 14).  T = 0: pose only, jac may be NULL
- *       and Tp is ignored; otherwise 1 <= T <= 22, Tp a multiple of 4 and >= T.  F = 10 + T.
+ *       and Tp is ignored; otherwise 1 <= T <= SDFR_INFO_MAX_TANGENTS, Tp a multiple of 4 and >= T.  F = 10 + T.
  *   gram    [B][F][F] doubles, overwritten: per view the Gram matrix over ALL M_v points of the view of
  *       f = (e0 .. e7, s0 .. s_{T-1}, r, 1):
  *         r        the point's value as sdfr_pc_loss_forward writes it (0 outside the volume)
@@ -1872,8 +1875,8 @@ SDFR_API int sdfr_pc_information(const float* points, const int* offsets /* null
  * Then out[8+T][8+T] / cd is Phi's data part and H, g of sdfr_lm_step are those of Phi; the count stays the depth term's,
  * so min_overlap means what it meant.  gram_out may be gram_depth (in place).  Entries that are not finite propagate (the
  * step then reports SDFR_LM_NO_SYSTEM).  One launch, no workspace; object k depends neither on K nor on the other
- * objects.  1 <= K <= 65535, 1 <= V <= 64, 0 <= T <= 22, pc_weight finite and >= 0, the matrices 8-byte aligned; every
- * error is SDFR_E_INVALID with a message before anything touches the GPU. */
+ * objects.  1 <= K <= 65535, 1 <= V <= SDFR_LM_MAX_VIEWS, 0 <= T <= SDFR_INFO_MAX_TANGENTS, pc_weight finite and >= 0, the
+ * matrices 8-byte aligned; every error is SDFR_E_INVALID with a message before anything touches the GPU. */
 SDFR_API int sdfr_information_combine(const double* gram_depth, const double* gram_pc, int K, int V, int T,
                                       double pc_weight, double* gram_out, int device, void* stream);
 

@@ -24,8 +24,6 @@
 namespace sdfr {
 namespace {
 
-constexpr int kJvpMaxT = 22;   // 10 + T features fit one 32 x 32 MFMA block (information_shape.hip)
-
 // resize_axis / blend of decoder.hip's resize3_kernel (ATen upsample_trilinear3d, align_corners=False), term for term
 __device__ __forceinline__ void jvp_resize_axis(int d, float ratio, int n_in, int& i0, int& i1, float& l1) {
   float src = fmaf(ratio, (float)d + 0.5f, -0.5f);
@@ -186,7 +184,7 @@ __global__ __launch_bounds__(256) void jvp_resize_kernel(const float* __restrict
 // order (rows, then columns, ascending).  grid (ceil(voxels / 256), K)
 __global__ __launch_bounds__(256) void sdf_std_kernel(const float* __restrict__ jac, long long voxels, int Tp, int T,
                                                       const double* __restrict__ cov, float* __restrict__ out) {
-  __shared__ double S[kJvpMaxT * kJvpMaxT];
+  __shared__ double S[SDFR_INFO_MAX_TANGENTS * SDFR_INFO_MAX_TANGENTS];
   const int n = blockIdx.y;
   for (int e = threadIdx.x; e < T * T; e += 256) S[e] = cov[(size_t)n * T * T + e];
   __syncthreads();
@@ -211,7 +209,7 @@ inline float* aligned256(void* p) { return (float*)(((uintptr_t)p + 255) & ~(uin
 using namespace sdfr;
 
 extern "C" size_t sdfr_decoder_jvp_workspace_bytes(const sdfr_decoder* d, int N, int T) {
-  if (!d || N < 1 || T < 1 || T > kJvpMaxT || (long long)N * T > 65535) return 0;
+  if (!d || N < 1 || T < 1 || T > SDFR_INFO_MAX_TANGENTS || (long long)N * T > 65535) return 0;
   JvpDesc j;
   decoder_jvp_desc(d, &j);
   return 2 * (size_t)N * T * (size_t)j.max_act * sizeof(float) + 512;
@@ -222,8 +220,9 @@ extern "C" int sdfr_decoder_jvp(const sdfr_decoder* d, const float* z, const flo
                                 size_t workspace_bytes, void* stream) {
   const char* fn = "sdfr_decoder_jvp";
   if (!d) return fail(SDFR_E_NULL, "%s: NULL decoder", fn);
-  if (N < 1 || T < 1 || T > kJvpMaxT || (long long)N * T > 65535)
-    return fail(SDFR_E_INVALID, "%s: N=%d, T=%d: need N >= 1, 1 <= T <= %d and N T <= 65535", fn, N, T, kJvpMaxT);
+  if (N < 1 || T < 1 || T > SDFR_INFO_MAX_TANGENTS || (long long)N * T > 65535)
+    return fail(SDFR_E_INVALID, "%s: N=%d, T=%d: need N >= 1, 1 <= T <= %d and N T <= 65535", fn, N, T,
+                SDFR_INFO_MAX_TANGENTS);
   JvpDesc j;
   decoder_jvp_desc(d, &j);
   if (!tangents && T != j.latent)
@@ -296,9 +295,10 @@ extern "C" int sdfr_decoder_jvp(const sdfr_decoder* d, const float* z, const flo
 extern "C" int sdfr_sdf_std(const float* jac, int K, long long voxels, int Tp, int T, const double* covariance,
                             float* out, int device, void* stream) {
   const char* fn = "sdfr_sdf_std";
-  if (K < 1 || K > 65535 || voxels < 1 || voxels > (1ll << 31) || T < 1 || T > kJvpMaxT || Tp < T || (Tp & 3))
+  if (K < 1 || K > 65535 || voxels < 1 || voxels > (1ll << 31) || T < 1 || T > SDFR_INFO_MAX_TANGENTS || Tp < T ||
+      (Tp & 3))
     return fail(SDFR_E_INVALID, "%s: K=%d, voxels=%lld, T=%d, Tp=%d: need 1 <= K <= 65535, 1 <= voxels <= 2^31, "
-                "1 <= T <= %d, Tp >= T a multiple of 4", fn, K, voxels, T, Tp, kJvpMaxT);
+                "1 <= T <= %d, Tp >= T a multiple of 4", fn, K, voxels, T, Tp, SDFR_INFO_MAX_TANGENTS);
   if (!jac || !covariance || !out) return fail(SDFR_E_INVALID, "%s: NULL pointer argument", fn);
   if (((uintptr_t)jac & 15u) || ((uintptr_t)covariance & 7u))
     return fail(SDFR_E_INVALID, "%s: jac must be 16-byte and covariance 8-byte aligned", fn);

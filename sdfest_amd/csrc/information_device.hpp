@@ -1,7 +1,8 @@
-// information_device.hpp -- the device and host pieces that sdfr_render_information (information.hip) and
-// sdfr_render_information_shape (information_shape.hip) share: the tile shape, the view set-up, the tile cull, the
-// per-pixel pose derivatives and the sizes of the flag block.  One statement of each: both kernels include a pixel by the
-// same rule and form its d with the same instructions.
+// information_device.hpp -- the device and host pieces that the two depth kernels of information.hip
+// (sdfr_render_information, sdfr_render_information_shape) share: the tile shape, the view set-up, the tile cull, the
+// tile's pixels with the inclusion rule, the per-pixel pose derivatives, the cell of a pixel's latent features and the
+// sizes of the flag block.  One statement of each: both kernels include a pixel by the same rule and form its d with
+// the same instructions.
 #pragma once
 #include <climits>
 
@@ -51,6 +52,52 @@ __device__ __forceinline__ bool info_tile_culled(const ViewSetup& s, int px0, in
          (float)(py0 + kInfoTileH) < fminf(va, vb) - my || (float)py0 > fmaxf(va, vb) + my;
 }
 
+// The prologue of a tile kernel (grid: tiles in x, tiles in y, B) over the kernel's own locals: the view's pose and, per
+// lane and sub-tile, the estimate, the target and whether the pixel is included.  false: the tile has no included pixel,
+// its 0 flag is written and the workgroup leaves (workgroup-uniform).  The view's pose first (scalar loads): three tiles
+// out of four lie outside the object and leave without a pixel read.  Then the estimate, and the target of the hit
+// pixels only.
+__device__ __forceinline__ bool info_tile_begin(const float* __restrict__ depth, const float* __restrict__ target,
+                                                const float* __restrict__ pos, const float* __restrict__ quat,
+                                                const float* __restrict__ inv_scale, int W, int H, float cx, float cy,
+                                                float fx, float fy, float inlier_threshold, unsigned* __restrict__ flag,
+                                                ViewSetup& s, int& row, float (&zs)[kInfoSubs], float (&ts)[kInfoSubs],
+                                                bool (&inc)[kInfoSubs]) {
+  using PB = Patch<kPatchWBwd>;
+  const int b = blockIdx.z;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int px0 = blockIdx.x * kInfoTileW, py0 = blockIdx.y * kInfoTileH;
+  info_pose(b, pos, quat, inv_scale, s);
+  if (info_tile_culled(s, px0, py0, cx, cy, fx, fy)) {   // workgroup-uniform
+    if (tid == 0) *flag = 0u;
+    return false;
+  }
+  const float* zimg = depth + (size_t)b * H * W;
+  const float* timg = target + (size_t)b * H * W;
+  bool any = false;
+  row = py0 + PB::oy(wave) + PB::y(lane);
+#pragma unroll
+  for (int sub = 0; sub < kInfoSubs; ++sub) {
+    const int col = px0 + sub * kSubW + PB::ox(wave) + PB::x(lane);
+    zs[sub] = (col < W && row < H) ? zimg[(size_t)row * W + col] : 0.0f;
+  }
+#pragma unroll
+  for (int sub = 0; sub < kInfoSubs; ++sub) {
+    const int col = px0 + sub * kSubW + PB::ox(wave) + PB::x(lane);
+    const float z = zs[sub];
+    const float t = z > 0.0f ? timg[(size_t)row * W + col] : 0.0f;
+    ts[sub] = t;
+    // overlap, and the relative inlier rule with an IEEE subtraction and DIVISION: numpy float32 gives the same set
+    inc[sub] = z > 0.0f && t > 0.0f && (inlier_threshold == 0.0f || __fdiv_rn(fabsf(t - z), t) < inlier_threshold);
+    any = any || inc[sub];
+  }
+  if (!__syncthreads_or(any)) {   // workgroup-uniform
+    if (tid == 0) *flag = 0u;
+    return false;
+  }
+  return true;
+}
+
 // d depth / d (p, q, inv_scale) of one hit pixel: backward_tile's acc[0 .. 7] terms with upstream gradient 1
 template <int RT>
 __device__ __forceinline__ void pixel_derivatives(const ViewSetup& s, const float* __restrict__ vol, int R, int row,
@@ -96,6 +143,26 @@ __device__ __forceinline__ void pixel_derivatives(const ViewSetup& s, const floa
   dd[6] = kf * 2.0f * (w * Gv - dot(G, uxv) - w * Go);
   // inverse scale: dc/ds^-1 = o / g, plus the product rule on scale
   dd[7] = f * h * Go - tri * scale * scale * adz;
+}
+
+// Where latent_features blends for a hit pixel and with what weight: the cell is gather_cell's (the same clamped floor of
+// the same hit point, no corner read), weight = scale |d.z| -- times a corner's trilinear weight it is d depth / d (that
+// corner).  A restatement of what pixel_derivatives has just formed, on purpose: with that function handing its Cell
+// and weight back, the compiler contracted its products differently in the kernel for a run-time R, and the matrices
+// lost their bits (measured); as it stands the second hit_point folds into the first.
+template <int RT>
+__device__ __forceinline__ void info_latent_cell(const ViewSetup& s, int R, int row, int col, float z, float cx, float cy,
+                                                 float rfx, float rfy, Cell& c, float& weight) {
+  const int Rr = RT > 0 ? RT : R;
+  const float h = 0.5f * (float)(Rr - 1);
+  const HitPoint hp = hit_point(s, row, col, z, cx, cy, rfx, rfy, s.isc, h);
+  const float top = (float)(Rr - 2);
+  const float bx = fminf(fmaxf(floorf(hp.gx), 0.0f), top);
+  const float by = fminf(fmaxf(floorf(hp.gy), 0.0f), top);
+  const float bz = fminf(fmaxf(floorf(hp.gz), 0.0f), top);
+  c.ox = hp.gx - bx; c.oy = hp.gy - by; c.oz = hp.gz - bz;
+  c.lin = (Rr <= 256) ? (int)fmaf(fmaf(bx, (float)Rr, by), (float)Rr, bz) : ((int)bx * Rr + (int)by) * Rr + (int)bz;
+  weight = s.scale * fabsf(hp.d.z);
 }
 
 inline int info_tiles_x(int W) { return (W + kInfoTileW - 1) / kInfoTileW; }

@@ -19,10 +19,8 @@
 namespace sdfr {
 namespace {
 
-constexpr int kLmMaxT = 22;             // group 14's limit: 10 + T features are one 32 x 32 block there
-constexpr int kLmMaxN = 7 + kLmMaxT;    // tangent dimensions
-constexpr int kLmMaxM = 8 + kLmMaxT;    // parameters the Gram matrix differentiates by = entries of a row the step moves
-constexpr int kLmMaxV = 64;
+constexpr int kLmMaxN = 7 + SDFR_INFO_MAX_TANGENTS;   // tangent dimensions
+constexpr int kLmMaxM = 8 + SDFR_INFO_MAX_TANGENTS;   // parameters the Gram matrix differentiates by = entries of a moved row
 constexpr double kLmFloor = 1e-12;      // damping floor relative to the largest diagonal entry (a condition, sdfr.h)
 
 struct LmConstants {
@@ -359,9 +357,10 @@ extern "C" int sdfr_lm_step(const double* gram_trial, float* params_trial, float
                             double lambda_down, double lambda_min, double lambda_max, double step_tol, int device,
                             void* stream) {
   const char* fn = "sdfr_lm_step";
-  if (K < 1 || K > 65535 || V < 1 || V > kLmMaxV || T < 0 || T > kLmMaxT || n_params < 8 + T || n_params > 65535)
+  if (K < 1 || K > 65535 || V < 1 || V > SDFR_LM_MAX_VIEWS || T < 0 || T > SDFR_INFO_MAX_TANGENTS || n_params < 8 + T ||
+      n_params > 65535)
     return fail(SDFR_E_INVALID, "%s: K=%d, V=%d, T=%d, n_params=%d: need 1 <= K <= 65535, 1 <= V <= %d, 0 <= T <= %d, "
-                "8 + T <= n_params <= 65535", fn, K, V, T, n_params, kLmMaxV, kLmMaxT);
+                "8 + T <= n_params <= 65535", fn, K, V, T, n_params, SDFR_LM_MAX_VIEWS, SDFR_INFO_MAX_TANGENTS);
   if (!gram_trial || !params_trial || !params_cur || !gram_cur || !state || !cam_quat)
     return fail(SDFR_E_NULL, "%s: NULL pointer argument", fn);
   if (((uintptr_t)gram_trial & 7u) || ((uintptr_t)gram_cur & 7u) || ((uintptr_t)state & 7u) || ((uintptr_t)step & 7u))

@@ -10,9 +10,8 @@
 // s_t = scale * trilerp(jac[.][t]) at the point's cell with the point's offsets.  A point outside the volume is a member
 // of the reference's mean with residual 0 and no gradient: f = (0, .., 0, 0, 1).
 //
-// The Gram product is render_information_shape_kernel's (information_shape.hip): a wave writes its 64 points' rows
-// [point][32] to LDS and reads them back as the one operand of 32 v_mfma_f32_32x32x2_f32 into 16 accumulator registers
-// -- a k-ordered fma chain: one order, symmetric bit for bit, entry (F - 1, F - 1) the exact count.
+// The Gram product and the latent features are information_gram.hpp's, shared with render_information_shape_kernel: a
+// wave's 64 points are the rows.
 //
 // The grid.  (min(nblk, G), B) workgroups of 256 points, G = kPcInfoGroups: workgroup g of a view takes the view's blocks
 // g, g + G, g + 2 G, ... (as PcBackwardArgs::groups) and keeps its accumulators across them, so a view writes
@@ -24,6 +23,7 @@
 
 #include "common.hpp"
 #include "device.hpp"
+#include "information_gram.hpp"
 #include "sampler_device.hpp"
 
 namespace sdfr {
@@ -36,20 +36,9 @@ namespace {
 // benchmark ties its counter profile to its bytes); G decides which points share an accumulator and so the result's
 // bits -- a build with another G would not compute what this one computes.
 constexpr int kPcInfoGroups = 64;
-constexpr int kPcInfoMaxT = 22;      // 10 + T <= 32
-constexpr int kPcInfoF = 32;         // feature slots of a point's row
 // a workgroup's count, 256 ceil(nblk / G), must stay an exact float
 constexpr long long kPcInfoMaxPoints = (long long)kPcInfoGroups << 24;
-constexpr int kCombineMaxV = 64;     // sdfr_lm_step's
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-struct PcInfoLds {
-  // per wave: [point][feature], features F .. 31 zero; the wave's 32 x 32 block (row-major) overlays it at the end
-  float feat[kPts / 64][64 * kPcInfoF];
-  int inside[kPts / 64];
-};
+static_assert(kPts == 64 * kGramWaves, "one Gram block per wave");
 
 // d value / d (p, q^, scale) of one inside point: pc_backward_block's acc[0 .. 7] with go = 1
 template <int RT>
@@ -85,34 +74,6 @@ __device__ __forceinline__ void point_derivatives(const PointFrame& f, const Cel
   a[6] = -2.0f * dot(dvo, cross(u, vrel));
 }
 
-// the T latent features of one inside point into f[8 ..]: scale * trilerp (x, then y, then z) of the cell's eight
-// corners of jac, Tp / 4 16-byte loads a corner
-__device__ __forceinline__ void point_latent_features(const Cell& c, const float* __restrict__ jac, int Tp, int T, int Rr,
-                                                      float scale, float (&f)[kPcInfoF]) {
-  const float ox = c.ox, oy = c.oy, oz = c.oz;
-  const float ax = 1.0f - ox, ay = 1.0f - oy, az = 1.0f - oz;
-  const float* base = jac + (size_t)c.lin * Tp;
-  const size_t sy = (size_t)Rr * Tp, sx = (size_t)Rr * Rr * Tp;
-#pragma unroll
-  for (int g = 0; g < (kPcInfoMaxT + 3) / 4; ++g) {
-    if (4 * g >= Tp) continue;   // wave-uniform
-    const float* p = base + 4 * g;
-    // corner 4 ix + 2 iy + iz, as Cell::v
-    const f32x4 v0 = *reinterpret_cast<const f32x4*>(p), v1 = *reinterpret_cast<const f32x4*>(p + Tp);
-    const f32x4 v2 = *reinterpret_cast<const f32x4*>(p + sy), v3 = *reinterpret_cast<const f32x4*>(p + sy + Tp);
-    const f32x4 v4 = *reinterpret_cast<const f32x4*>(p + sx), v5 = *reinterpret_cast<const f32x4*>(p + sx + Tp);
-    const f32x4 v6 = *reinterpret_cast<const f32x4*>(p + sx + sy), v7 = *reinterpret_cast<const f32x4*>(p + sx + sy + Tp);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float c00 = fmaf(v4[j], ox, v0[j] * ax), c01 = fmaf(v5[j], ox, v1[j] * ax);
-      const float c10 = fmaf(v6[j], ox, v2[j] * ax), c11 = fmaf(v7[j], ox, v3[j] * ax);
-      const float c0 = fmaf(c10, oy, c00 * ay), c1 = fmaf(c11, oy, c01 * ay);
-      const float tri = fmaf(c1, oz, c0 * az);
-      if (8 + 4 * g + j < kPcInfoF) f[8 + 4 * g + j] = 4 * g + j < T ? scale * tri : 0.0f;
-    }
-  }
-}
-
 // grid: (min(nblk, G), B).  records [B][gridDim.x][F F], F = 10 + T; Tp = 0 with T = 0 (jac is not read).
 template <int RT>
 __global__ __launch_bounds__(kPts) void pc_information_kernel(
@@ -120,7 +81,8 @@ __global__ __launch_bounds__(kPts) void pc_information_kernel(
     const float* __restrict__ quat, const float* __restrict__ scale, const float* __restrict__ sdf, int R,
     long long sdf_view_stride, const float* __restrict__ jac, int Tp, int T, long long jac_view_stride,
     float* __restrict__ records, int* __restrict__ inside) {
-  __shared__ PcInfoLds lds;
+  __shared__ GramBlock lds[kGramWaves];
+  __shared__ int lds_inside[kGramWaves];
   const int v = blockIdx.y, g = blockIdx.x;
   const int begin = offsets ? offsets[v] : 0;
   const int end = offsets ? offsets[v + 1] : n_single;
@@ -132,7 +94,6 @@ __global__ __launch_bounds__(kPts) void pc_information_kernel(
   const PointFrame fr = load_frame(pos, quat, scale, v);
   const float* vol = sdf + (size_t)v * sdf_view_stride;
   const float* jv = jac + (size_t)v * jac_view_stride;
-  float* blk = lds.feat[wave];
   f32x16 acc;
 #pragma unroll
   for (int k = 0; k < 16; ++k) acc[k] = 0.0f;
@@ -143,9 +104,9 @@ __global__ __launch_bounds__(kPts) void pc_information_kernel(
     const long long first = b * kPts + 64 * wave;   // the wave's first point of this block, relative to the view
     if (first >= len) continue;                     // wave-uniform: no rows, no products (all-zero rows add nothing)
     const long long rel = first + lane;
-    float f[kPcInfoF];
+    float f[kGramF];
 #pragma unroll
-    for (int k = 0; k < kPcInfoF; ++k) f[k] = 0.0f;
+    for (int k = 0; k < kGramF; ++k) f[k] = 0.0f;
     bool live = false;
     if (rel < len) {
       const size_t i = (size_t)begin + (size_t)rel;
@@ -164,41 +125,21 @@ __global__ __launch_bounds__(kPts) void pc_information_kernel(
 #pragma unroll
         for (int k = 0; k < 4; ++k) f[3 + k] = (a[3 + k] - fr.qn[k] * d) * fr.inv_norm;
         f[7] = -(fr.scale * fr.scale) * a[7];   // d / d inv_scale
-        if (T > 0) point_latent_features(c, jv, Tp, T, Rr, fr.scale, f);
+        if (T > 0) latent_features(c, jv, Tp, T, Rr, fr.scale, f);
         r = tri * fr.scale;
       }
 #pragma unroll
-      for (int k = 8; k < kPcInfoF; ++k) f[k] = k == 8 + T ? r : k == 9 + T ? 1.0f : f[k];
+      for (int k = 8; k < kGramF; ++k) f[k] = k == 8 + T ? r : k == 9 + T ? 1.0f : f[k];
     }
     n_inside += __popcll(__ballot(live));
-    f32x4* mine = reinterpret_cast<f32x4*>(blk + lane * kPcInfoF);
-#pragma unroll
-    for (int k = 0; k < kPcInfoF / 4; ++k) mine[k] = f32x4{f[4 * k], f[4 * k + 1], f[4 * k + 2], f[4 * k + 3]};
-    // the wave's own rows, read back across lanes (as information_shape.hip: the LDS serves a wave's accesses in order)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-#pragma unroll 8
-    for (int s = 0; s < 32; ++s) {
-      const float x = blk[64 * s + lane];
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(x, x, acc, 0, 0, 0);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    gram32_accumulate(f, lds[wave], lane, acc);
   }
-  // C/D layout: column = lane & 31, row = (register & 3) + 8 (register >> 2) + 4 (lane >> 5); into the wave's own block
-#pragma unroll
-  for (int k = 0; k < 16; ++k) blk[((k & 3) + 8 * (k >> 2) + 4 * (lane >> 5)) * 32 + (lane & 31)] = acc[k];
-  if (lane == 0) lds.inside[wave] = n_inside;
+  gram32_store(acc, lds[wave], lane);
+  if (lane == 0) lds_inside[wave] = n_inside;
   __syncthreads();
-  float* rec = records + ((size_t)v * gridDim.x + g) * (size_t)(F * F);
-  for (int e = tid; e < F * F; e += kPts) {
-    const int w = (e / F) * 32 + e % F;
-    rec[e] = (lds.feat[0][w] + lds.feat[1][w]) + (lds.feat[2][w] + lds.feat[3][w]);
-  }
+  gram32_record(lds, F, tid, records + ((size_t)v * gridDim.x + g) * (size_t)(F * F));
   // (integers: whatever order the view's workgroups arrive in, the sum is the same)
-  if (inside && tid == 0) atomicAdd(inside + v, (lds.inside[0] + lds.inside[1]) + (lds.inside[2] + lds.inside[3]));
+  if (inside && tid == 0) atomicAdd(inside + v, (lds_inside[0] + lds_inside[1]) + (lds_inside[2] + lds_inside[3]));
 }
 
 // A view's min(nb_v, G) records summed in record order in double, one thread per entry.  grid: B; 256 threads.
@@ -252,7 +193,7 @@ inline int pc_info_slots(int max_view_points) {
 }
 inline bool pc_info_sizes_ok(int B, int max_view_points, int T) {
   return B >= 0 && B <= 65535 && max_view_points >= 0 && (long long)max_view_points <= kPcInfoMaxPoints && T >= 0 &&
-         T <= kPcInfoMaxT;
+         T <= SDFR_INFO_MAX_TANGENTS;
 }
 
 }  // namespace
@@ -275,7 +216,8 @@ extern "C" int sdfr_pc_information(const float* points, const int* offsets, int 
   if (max_view_points < 0 || (long long)max_view_points > kPcInfoMaxPoints)
     return fail(SDFR_E_INVALID, "%s: max_view_points=%d out of range [0,%lld]", fn, max_view_points, kPcInfoMaxPoints);
   if (R < 2 || R > 1024) return fail(SDFR_E_INVALID, "%s: R=%d out of range [2,1024]", fn, R);
-  if (T < 0 || T > kPcInfoMaxT) return fail(SDFR_E_INVALID, "%s: T=%d out of range [0,%d]", fn, T, kPcInfoMaxT);
+  if (T < 0 || T > SDFR_INFO_MAX_TANGENTS)
+    return fail(SDFR_E_INVALID, "%s: T=%d out of range [0,%d]", fn, T, SDFR_INFO_MAX_TANGENTS);
   if (T > 0 && (Tp < T || (Tp & 3)))
     return fail(SDFR_E_INVALID, "%s: Tp=%d must be a multiple of 4 and at least T=%d", fn, Tp, T);
   if (sdf_view_stride != 0 && sdf_view_stride < (long long)R * R * R)
@@ -326,9 +268,9 @@ extern "C" int sdfr_pc_information(const float* points, const int* offsets, int 
 extern "C" int sdfr_information_combine(const double* gram_depth, const double* gram_pc, int K, int V, int T,
                                         double pc_weight, double* gram_out, int device, void* stream) {
   const char* fn = "sdfr_information_combine";
-  if (K < 1 || K > 65535 || V < 1 || V > kCombineMaxV || T < 0 || T > kPcInfoMaxT)
+  if (K < 1 || K > 65535 || V < 1 || V > SDFR_LM_MAX_VIEWS || T < 0 || T > SDFR_INFO_MAX_TANGENTS)
     return fail(SDFR_E_INVALID, "%s: K=%d, V=%d, T=%d: need 1 <= K <= 65535, 1 <= V <= %d, 0 <= T <= %d", fn, K, V, T,
-                kCombineMaxV, kPcInfoMaxT);
+                SDFR_LM_MAX_VIEWS, SDFR_INFO_MAX_TANGENTS);
   if (!(pc_weight >= 0.0) || !std::isfinite(pc_weight))
     return fail(SDFR_E_INVALID, "%s: pc_weight=%g must be finite and >= 0", fn, pc_weight);
   if (!gram_depth || !gram_pc || !gram_out) return fail(SDFR_E_INVALID, "%s: NULL pointer argument", fn);

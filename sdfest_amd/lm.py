@@ -2,7 +2,7 @@
 
 The render-and-compare loop is first order: it returns the iterate Adam stopped at.  The information calls already give
 everything a second-order step needs -- per view ``J^T J``, ``J^T r``, ``sum r^2`` and the pixel count, jointly over
-the pose and up to 22 latent directions --, and ``sdfr_lm_step`` (include/sdfr.h group 18) turns them into one damped
+the pose and up to ``MAX_TANGENTS`` latent directions --, and ``sdfr_lm_step`` (include/sdfr.h group 18) turns them into one damped
 Gauss-Newton step per object on the device: the accept test, the normal equations in the world tangent, the Cholesky
 solve, the retraction and the status, one wave per object.  The reference has neither the matrices nor the step.
 
@@ -26,10 +26,10 @@ from .differentiable_renderer import _ptr, _stream
 
 STATE_DOUBLES = _lib.ABI["SDFR_LM_STATE_DOUBLES"]
 STATE = {name[len("SDFR_LM_"):].lower(): index for name, index in _lib.ABI.items()
-         if name.startswith("SDFR_LM_") and name not in ("SDFR_LM_STATE_DOUBLES", "SDFR_LM_RUNNING", "SDFR_LM_CONVERGED",
-                                                        "SDFR_LM_STALLED", "SDFR_LM_NO_SYSTEM")}
+         if name.startswith("SDFR_LM_") and name not in ("SDFR_LM_STATE_DOUBLES", "SDFR_LM_MAX_VIEWS", "SDFR_LM_RUNNING",
+                                                        "SDFR_LM_CONVERGED", "SDFR_LM_STALLED", "SDFR_LM_NO_SYSTEM")}
 RUNNING, CONVERGED, STALLED, NO_SYSTEM = (_lib.ABI["SDFR_LM_" + s] for s in ("RUNNING", "CONVERGED", "STALLED", "NO_SYSTEM"))
-MAX_TANGENTS = 22
+MAX_TANGENTS, MAX_VIEWS = _lib.ABI["SDFR_INFO_MAX_TANGENTS"], _lib.ABI["SDFR_LM_MAX_VIEWS"]
 
 # the damping schedule and the stopping rule, by the C entry's argument names: lambda starts at lambda0, an accepted
 # trial multiplies it by lambda_down (not below lambda_min), a rejected one by lambda_up; above lambda_max the row has
@@ -51,7 +51,7 @@ def lm_step(gram_trial: torch.Tensor, params_trial: torch.Tensor, params_cur: to
 
     gram_trial (K V, F, F) float64, F = 10 + T: what ``uncertainty.render_information`` returned for the K V views of
     the rows of ``params_trial`` (K, n_params) float32 [position 3 | orientation 4 xyzw | scale | latent], object-major;
-    T = 0 (pose only) or 1 <= T <= 22 latent directions.  params_cur, gram_cur (same shapes) and state (K, 16) float64
+    T = 0 (pose only) or 1 <= T <= ``MAX_TANGENTS`` latent directions.  params_cur, gram_cur (same shapes) and state (K, 16) float64
     (``lm.STATE`` names its entries) are the call's own: ``init=True`` fills them from the trial, which it accepts
     unconditionally.  cam_quat (V, 4): the cameras' orientations in the world.  Afterwards ``params_trial`` holds the
     next rows to render and evaluate, or the current rows where the status is no longer ``RUNNING``.  step (K, 7 + T)
@@ -120,7 +120,7 @@ class LMRefiner:
     """K estimates seen from V cameras, refined side by side by Levenberg-Marquardt.
 
     pipeline_or_parts: an ``SDFPipeline`` (its decoder, camera and ``threshold``) or the tuple ``(decoder, camera,
-    threshold)``.  shape: the latent is part of the step (T = the latent size, at most 22) or held fixed (T = 0).
+    threshold)``.  shape: the latent is part of the step (T = the latent size, at most ``MAX_TANGENTS``) or held fixed (T = 0).
     inlier_threshold: ``render_information``'s; latent_weight: mu of the objective; min_overlap: a trial that keeps less
     than this share of the current iterate's pixels is rejected; ``**lm``: ``LM_DEFAULTS``.
     pc_weight: w of Phi = mean r_depth^2 + w mean r_pc^2 + mu |z|^2.  0 (the default): Phi is the depth term's, no
@@ -151,8 +151,8 @@ class LMRefiner:
         self.cam, self.threshold = camera, float(threshold)
         self.dev = dev = torch.device(dec.device if device is None else device)
         K, V = int(K), int(V)
-        if K < 1 or not 1 <= V <= 64 or K * V > 65535:
-            raise ValueError(f"K = {K} objects and V = {V} views: K >= 1, 1 <= V <= 64 and K V <= 65535 are expected")
+        if K < 1 or not 1 <= V <= MAX_VIEWS or K * V > 65535:
+            raise ValueError(f"K = {K} objects and V = {V} views: K >= 1, 1 <= V <= {MAX_VIEWS} and K V <= 65535 are expected")
         self.K, self.V, self.B = K, V, K * V
         self.Lz = int(dec.latent_size)
         self.shape = bool(shape)

@@ -30,6 +30,34 @@ from .differentiable_renderer import Camera, _check_inputs, _ptr, _stream, _work
 GRAM_SIZE = 10   # (d0 .. d7, r, 1)
 
 
+def _sdf_layout(sdf: torch.Tensor, B: int):
+    """(R, sdf_view_stride) of an ``sdf`` (R,R,R) shared by B views or (B,R,R,R)"""
+    R = sdf.shape[-1]
+    if sdf.dim() == 3:
+        stride = 0
+    elif sdf.dim() == 4 and sdf.shape[0] == B:
+        stride = R * R * R
+    else:
+        raise RuntimeError("sdf must be (R,R,R) or (B,R,R,R)")
+    if tuple(sdf.shape[-3:]) != (R, R, R):
+        raise RuntimeError("sdf must be cubic")
+    return R, stride
+
+
+def _jacobian_layout(jacobian: torch.Tensor, tangents: Optional[int], B: int, R: int):
+    """(Tp, T, jac_view_stride) of a ``jacobian`` (R^3, Tp) shared by B views or (B, R^3, Tp), T = ``tangents`` or Tp"""
+    _check_inputs((jacobian, "jacobian"))
+    Tp = jacobian.shape[-1]
+    T = Tp if tangents is None else int(tangents)
+    if jacobian.dim() == 2 and jacobian.shape[0] == R ** 3:
+        jstride = 0
+    elif jacobian.dim() == 3 and tuple(jacobian.shape[:2]) == (B, R ** 3):
+        jstride = R ** 3 * Tp
+    else:
+        raise RuntimeError("jacobian must be (R^3, Tp) or (B, R^3, Tp)")
+    return Tp, T, jstride
+
+
 def render_information(depth: torch.Tensor, target: torch.Tensor, sdf: torch.Tensor, position: torch.Tensor,
                        orientation: torch.Tensor, inv_scale: torch.Tensor, camera: Camera,
                        inlier_threshold: float = 0.0, workspace: Optional[torch.Tensor] = None,
@@ -46,7 +74,7 @@ def render_information(depth: torch.Tensor, target: torch.Tensor, sdf: torch.Ten
     (B, R^3, Tp), with ``tangents`` = T of its Tp columns in use (default: all).  The result is then (B, 10+T, 10+T), the
     Gram matrix of f = (d0 .. d7, s0 .. s_{T-1}, r, 1) with s_t = d depth / d (latent direction t) over the same pixels
     (``sdfr_render_information_shape``): ``[:8,:8]`` the pose block, ``[8:8+T,8:8+T]`` the latent block, ``[:8+T,8+T]``
-    J^T r, ``[8+T,8+T]`` sum r^2, ``[9+T,9+T]`` the count.  1 <= T <= 22."""
+    J^T r, ``[8+T,8+T]`` sum r^2, ``[9+T,9+T]`` the count.  1 <= T <= SDFR_INFO_MAX_TANGENTS."""
     _check_inputs((depth, "depth"), (target, "target"), (sdf, "sdf"), (position, "position"),
                   (orientation, "orientation"), (inv_scale, "inv_scale"))
     pos, quat, isc = position.reshape(-1, 3), orientation.reshape(-1, 4), inv_scale.reshape(-1)
@@ -56,28 +84,12 @@ def render_information(depth: torch.Tensor, target: torch.Tensor, sdf: torch.Ten
     H, W = camera.height, camera.width
     if depth.numel() != B * H * W or target.numel() != B * H * W or tuple(depth.shape[-2:]) != (H, W):
         raise RuntimeError(f"expected depth and target of {B} x {H} x {W} pixels")
-    R = sdf.shape[-1]
-    if sdf.dim() == 3:
-        stride = 0
-    elif sdf.dim() == 4 and sdf.shape[0] == B:
-        stride = R * R * R
-    else:
-        raise RuntimeError("sdf must be (R,R,R) or (B,R,R,R)")
-    if tuple(sdf.shape[-3:]) != (R, R, R):
-        raise RuntimeError("sdf must be cubic")
+    R, stride = _sdf_layout(sdf, B)
     fx, fy, cx, cy, _ = camera.get_pinhole_camera_parameters(0.5)
     dev = sdf.device
     L = _lib.lib()
     if jacobian is not None:
-        _check_inputs((jacobian, "jacobian"))
-        Tp = jacobian.shape[-1]
-        T = Tp if tangents is None else int(tangents)
-        if jacobian.dim() == 2 and jacobian.shape[0] == R ** 3:
-            jstride = 0
-        elif jacobian.dim() == 3 and tuple(jacobian.shape[:2]) == (B, R ** 3):
-            jstride = R ** 3 * Tp
-        else:
-            raise RuntimeError("jacobian must be (R^3, Tp) or (B, R^3, Tp)")
+        Tp, T, jstride = _jacobian_layout(jacobian, tangents, B, R)
         nbytes = L.sdfr_render_information_shape_workspace_bytes(B, W, H, T)
         if workspace is None and nbytes:
             workspace = _workspace(dev, nbytes)
@@ -134,26 +146,10 @@ def pc_information(points: torch.Tensor, offsets: Optional[torch.Tensor], sdf: t
     M = N if max_view_points is None else int(max_view_points)
     if offsets is None and M != N:
         raise RuntimeError("without offsets max_view_points is the number of points")
-    R = sdf.shape[-1]
-    if sdf.dim() == 3:
-        stride = 0
-    elif sdf.dim() == 4 and sdf.shape[0] == B:
-        stride = R * R * R
-    else:
-        raise RuntimeError("sdf must be (R,R,R) or (B,R,R,R)")
-    if tuple(sdf.shape[-3:]) != (R, R, R):
-        raise RuntimeError("sdf must be cubic")
+    R, stride = _sdf_layout(sdf, B)
     Tp = T = jstride = 0
     if jacobian is not None:
-        _check_inputs((jacobian, "jacobian"))
-        Tp = jacobian.shape[-1]
-        T = Tp if tangents is None else int(tangents)
-        if jacobian.dim() == 2 and jacobian.shape[0] == R ** 3:
-            jstride = 0
-        elif jacobian.dim() == 3 and tuple(jacobian.shape[:2]) == (B, R ** 3):
-            jstride = R ** 3 * Tp
-        else:
-            raise RuntimeError("jacobian must be (R^3, Tp) or (B, R^3, Tp)")
+        Tp, T, jstride = _jacobian_layout(jacobian, tangents, B, R)
         if T < 1:
             raise RuntimeError("tangents must be >= 1 with a jacobian")
     dev = sdf.device

@@ -208,7 +208,7 @@ class SDFDecoder:
         """The decoded volumes and their forward-mode derivative w.r.t. the latent (``sdfr_decoder_jvp``).
 
         z (N, latent_size); tangents (N, T, latent_size) directions per latent, None = the identity basis (T =
-        latent_size: the full Jacobian d SDF / d z).  1 <= T <= 22.  Returns ``(sdf, jac)``: sdf (N, 1, D, D, D) is the
+        latent_size: the full Jacobian d SDF / d z).  1 <= T <= SDFR_INFO_MAX_TANGENTS.  Returns ``(sdf, jac)``: sdf (N, 1, D, D, D) is the
         existing forward's output (run with a tape), jac the VOXEL-major buffer (N, D^3, Tp), Tp = T rounded up to a
         multiple of 4 with zeros in the columns T .. Tp - 1 -- ``jac[n, voxel, t]`` is the derivative of voxel `voxel`
         of latent n along ``tangents[n, t]``; this is the layout ``uncertainty.render_information(jacobian=)`` reads.
@@ -229,7 +229,8 @@ class SDFDecoder:
             T, tc = tangents.shape[1], tangents.detach().contiguous()
         need = self._L.sdfr_decoder_jvp_workspace_bytes(self._h, N, T)
         if need == 0:
-            raise RuntimeError(f"sdfr_decoder_jvp takes 1 <= T <= 22 tangents and N T <= 65535 (N={N}, T={T})")
+            raise RuntimeError(f"sdfr_decoder_jvp takes 1 <= T <= {_lib.ABI['SDFR_INFO_MAX_TANGENTS']} tangents and N T <= 65535 "
+                               f"(N={N}, T={T})")
         tape = torch.empty(max(self._L.sdfr_decoder_tape_bytes(self._h, N) // 4, 1), dtype=torch.float32, device=self.device)
         out = self._forward_raw(zc, enforce_tsdf, tape)
         jac = torch.empty((N, D ** 3, (T + 3) & ~3), dtype=torch.float32, device=self.device)

@@ -89,6 +89,32 @@ def test_abi_constants_from_header():
     assert (_lib.ABI["SDFR_E_INVALID"], _lib.ABI["SDFR_SYNC_POLLS_MAGIC"]) == (-1, 0x504F4C4C)
 
 
+def test_information_limits_have_one_statement(libpath):
+    """the tangent and view limits of groups 14, 17, 18 and 19 are two macros of the header: the Python side reads them,
+    and every entry refuses the first size beyond them before anything touches the GPU"""
+    from sdfest_amd import _lib, lm
+    assert (_lib.ABI["SDFR_INFO_MAX_TANGENTS"], _lib.ABI["SDFR_LM_MAX_VIEWS"]) == (22, 64)
+    assert (lm.MAX_TANGENTS, lm.MAX_VIEWS) == (22, 64)
+    assert "max_views" not in lm.STATE and len(lm.STATE) == 14
+    L = _lib.lib()
+    assert L.sdfr_render_information_shape_workspace_bytes(1, 64, 48, 22) > 0
+    assert L.sdfr_render_information_shape_workspace_bytes(1, 64, 48, 23) == 0
+    assert L.sdfr_pc_information_workspace_bytes(1, 1000, 22) > 0
+    assert L.sdfr_pc_information_workspace_bytes(1, 1000, 23) == 0
+    buf = (ctypes.c_double * 64)()
+    q = ctypes.cast(buf, ctypes.c_void_p)   # a non-NULL, 8-byte aligned pointer that is never dereferenced
+    invalid = _lib.ABI["SDFR_E_INVALID"]
+    # sdfr_lm_step(gram_trial, params_trial, params_cur, gram_cur, state, step, cam_quat, K, V, T, n_params, init, ...)
+    step = lambda V, T: L.sdfr_lm_step(q, q, q, q, q, None, q, 1, V, T, 8 + T, 1, 0.0, 0.5, 1e-3, 10.0, 0.1, 1e-9, 1e9,
+                                       1e-9, 0, None)
+    assert step(64, 23) == invalid and b"T=23" in L.sdfr_last_error() and b"0 <= T <= 22" in L.sdfr_last_error()
+    assert step(65, 22) == invalid and b"V=65" in L.sdfr_last_error() and b"1 <= V <= 64" in L.sdfr_last_error()
+    # sdfr_information_combine(gram_depth, gram_pc, K, V, T, pc_weight, gram_out, device, stream)
+    combine = lambda V, T: L.sdfr_information_combine(q, q, 1, V, T, 1.0, q, 0, None)
+    assert combine(64, 23) == invalid and b"T=23" in L.sdfr_last_error() and b"0 <= T <= 22" in L.sdfr_last_error()
+    assert combine(65, 22) == invalid and b"V=65" in L.sdfr_last_error() and b"1 <= V <= 64" in L.sdfr_last_error()
+
+
 def test_parse_header_comments_void_and_expressions():
     from sdfest_amd import _lib
     text = """
