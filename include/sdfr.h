@@ -1880,6 +1880,51 @@ SDFR_API int sdfr_pc_information(const float* points, const int* offsets /* null
 SDFR_API int sdfr_information_combine(const double* gram_depth, const double* gram_pc, int K, int V, int T,
                                       double pc_weight, double* gram_out, int device, void* stream);
 
+/* ---- looking at a render: surface normals, the range of a depth image, packed RGB8 frames (shade.hip).  Nothing here
+ * is differentiated and nothing takes a workspace.
+ *
+ * sdfr_render_normals: `depth` [B][H][W] is sdfr_render_forward's output for the same grid(s), poses and intrinsics;
+ * sdf, R, sdf_view_stride (0: one grid for all B views, otherwise >= R^3: one per view), pos, quat, inv_scale as the
+ * forward takes them.  normals [B][H][W][3], every element written: for a pixel with depth != 0 the gradient of the
+ * trilinear interpolant at the pixel's hit point -- the cell, the clamped base and the un-clamped offsets of
+ * sdfr_render_backward, cells that extrapolate past the grid included -- normalised and rotated into the camera frame
+ * (it points away from the object: the SDF is positive outside); three zeros where depth == 0, where the gradient
+ * vanishes and where it is not finite.  One launch, no atomics; a view's result does not depend on its batch.
+ *
+ * sdfr_depth_range: range [B][2] (shared == 0) or [1][2] (shared != 0: one workgroup reads all B images -- meant for a
+ * few images; for many, reduce the [B][2] rows with a second call that takes them as one 2B x 1 image) = the minimum
+ * and the maximum over the pixels that are finite and non-zero, (0, 0) where there are none.  Exact; one launch.
+ *
+ * sdfr_shade_frames: one pass over B frames ordered (state, view) with V = views_per_state; frame f reads grid f / V
+ * when sdf_view_stride != 0, pose f and target image f % V.  Outputs [B][H][W][3] bytes R, G, B; a NULL output is
+ * skipped (not all three).  A pixel with depth == 0 gets `background` (0xRRGGBB) in every image.  Otherwise
+ *   depth_rgb   (needs range: device memory, {vmin, vmax} at range + f * range_stride, range_stride 0 or 2)
+ *               viridis[clamp(floor((z - vmin) / (vmax - vmin) * 256), 0, 255)], entry 0 when vmax == vmin
+ *   error_rgb   (needs target [V][H][W]) background where the target is 0, else
+ *               viridis[clamp(floor(|z - target| / error_max * 256), 0, 255)]
+ *   shaded_rgb  (needs sdf, pos, quat, inv_scale) with n the normal of sdfr_render_normals and l = light / |light| (camera
+ *               frame, towards the light): s = ambient + (1 - ambient) max(0, n . l), channel c =
+ *               round(255 clamp(base_c s, 0, 1))
+ * The table is matplotlib's viridis at 256 entries (colormap_table.hpp).  A frame's bytes depend on that frame's inputs
+ * alone, and the same inputs give the same bytes.
+ *
+ * All three: 1 <= B <= 65535, W, H >= 1, W H <= 2^30, 2 <= R <= 1024, float buffers 4-byte aligned.  Every error is
+ * SDFR_E_INVALID with a message, before anything touches the GPU: a NULL required pointer, B, W or H <= 0, R < 2, V < 1 or
+ * B not a multiple of V, error_max <= 0, range_stride not 0 or 2, a zero focal length or light, background beyond 0xffffff. */
+SDFR_API int sdfr_render_normals(const float* depth, const float* sdf, int R, long long sdf_view_stride,
+                                 const float* pos, const float* quat, const float* inv_scale, int B, int W, int H,
+                                 float cx, float cy, float fx, float fy, float* normals, int device, void* stream);
+SDFR_API int sdfr_depth_range(const float* depth, int B, int W, int H, int shared, float* range, int device,
+                              void* stream);
+SDFR_API int sdfr_shade_frames(const float* depth, const float* sdf, int R, long long sdf_view_stride,
+                               const float* pos, const float* quat, const float* inv_scale, int B, int W, int H,
+                               float cx, float cy, float fx, float fy, int views_per_state,
+                               const float* target /* nullable */, const float* range /* nullable */, int range_stride,
+                               float error_max, float light_x, float light_y, float light_z, float ambient,
+                               float base_r, float base_g, float base_b, int background,
+                               unsigned char* depth_rgb /* nullable */, unsigned char* error_rgb /* nullable */,
+                               unsigned char* shaded_rgb /* nullable */, int device, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -143,3 +143,11 @@
 #ifndef SDFR_BT_THREADS
 #define SDFR_BT_THREADS 0
 #endif
+// shade.hip.  Plain constants, not override points of a variant build (tests/test_build_variants_cpu.py lists those):
+// the packed store form is written for exactly four pixels.
+// Adjacent pixels per lane of sdfr_shade_frames: four RGB8 pixels are 12 bytes = three whole dwords, so a lane's store
+// is one 12-byte instruction and a wave's 768 contiguous bytes (three single bytes per lane is the form to avoid); the
+// depth and target reads are one 16-byte load each.
+#define SDFR_SHADE_PIXELS_PER_LANE 4
+// threads per workgroup of sdfr_depth_range's reduction (one workgroup per image)
+#define SDFR_RANGE_THREADS 1024

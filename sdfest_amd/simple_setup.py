@@ -17,12 +17,16 @@ After the estimate, ``generate_mesh`` turns a latent and a scale into a mesh as 
 marching cubes on the GPU (``mesh.extract_mesh``) instead of skimage + open3d; ``generate_meshes`` does the same for
 the K rows of ``estimate_objects`` in one batched decode and one launch sequence.
 
-What is NOT here (out of scope): plots (``visualize``), step logs (``log_path``), animations
-(``animation_path``) and weight downloads -- the first three arguments are accepted and ignored with a warning,
-weights come as state dicts or from a local file.  ``generate_mesh`` returns ``mesh.Mesh`` (device tensors, OBJ / PLY
+What is NOT here (out of scope): plots (``visualize``) and weight downloads -- weights come as state
+dicts or from a local file.  Step logs (``log_path``) and animations (``animation_path``) are OPT-IN, with the config key
+``step_log: true``: the loop then records its per-iteration states on the device, and what the reference draws
+iteration by iteration with a host synchronisation each is made AFTER the loop from those states (``visualization.py``:
+the reference's log pickle, raw ``W x H`` frames instead of matplotlib figures, GIFs instead of mp4).  Without the key
+the three arguments are accepted and ignored with a warning, as before, and no launch is added.  ``generate_mesh`` returns ``mesh.Mesh`` (device tensors, OBJ / PLY
 writers), not an open3d ``TriangleMesh``.
 """
 import os
+import pickle
 import warnings
 from typing import Dict, List, Mapping, Optional, Tuple
 
@@ -52,6 +56,65 @@ def _load_state(source, what: str) -> Mapping:
             return torch.load(path, map_location="cpu")
     raise FileNotFoundError(f"{what}: no state dict given and {source!r} is not a local file "
                             "(weights are not downloaded; pass vae_state_dict= / init_state_dict=)")
+
+
+def _event(device) -> "torch.cuda.Event":
+    """a timing event recorded on `device`'s current stream -- the stream the loop launches on"""
+    event = torch.cuda.Event(enable_timing=True)
+    event.record(torch.cuda.current_stream(device))
+    return event
+
+
+class _TimedHistory(list):
+    """a loop's ``history`` that also records an event on the loop's stream behind every entry: the time of every
+    iteration without a synchronisation per iteration (read after the loop, ``_StepRecord.timestamps``)"""
+
+    def __init__(self, device):
+        super().__init__()
+        self.device = device
+        self.events = []
+
+    def append(self, entry) -> None:
+        super().append(entry)
+        self.events.append(_event(self.device))
+
+
+class _StepRecord:
+    """what one ``__call__`` under ``step_log`` keeps: the inputs of the first view as they came, the preprocessed
+    observation and the cameras the loop was bound to, the initial estimate, the loop's history and the events that
+    time them.  Device tensors; nothing is read back here."""
+
+    def __init__(self, device, start, depth_images, masks, color_images, animation_path):
+        self.device = device
+        self.start = start           # recorded at the top of the call
+        # (the depth is preprocessed in place further on: the animation's depth_input.png needs the first view as given)
+        self.raw_depth = None
+        if animation_path is not None:
+            self.raw_depth = depth_images[0].detach().to(device, torch.float32).clone()
+        self.masks = masks.detach()
+        self.color = color_images.detach() if isinstance(color_images, torch.Tensor) else color_images
+        self.history = _TimedHistory(device)
+        self.inputs_done = self.init_done = None     # events behind the preprocessing / behind the initialisation
+
+    def begin(self, loop, position, orientation, scale, latent) -> None:
+        """in front of the loop: the observation as the loop holds it, and the estimate it starts from"""
+        self.target = loop.target.detach().clone()
+        self.cam_pos, self.cam_quat = loop.cam_pos_all.detach().clone(), loop.cam_quat_all.detach().clone()
+        self.initial = (position.detach().reshape(1, 3).clone(), orientation.detach().reshape(1, 4).clone(),
+                        scale.detach().reshape(1).clone(), latent.detach().reshape(1, -1).clone())
+        self.init_done = _event(self.device)
+
+    def states(self) -> tuple:
+        keys = ("position", "orientation", "scale", "latent")
+        shapes = ((1, 3), (1, 4), (1,), (1, -1))
+        return tuple(torch.cat([first] + [h[k].reshape(shape) for h in self.history])
+                     for first, k, shape in zip(self.initial, keys, shapes))
+
+    def timestamps(self) -> list:
+        """seconds since the call began: [the inputs, the initial estimate, every iteration]; waits for the last event"""
+        events = [self.inputs_done, self.init_done] + self.history.events
+        events[-1].synchronize()
+        return [self.start.elapsed_time(e) * 1e-3 for e in events]
 
 
 class SDFPipeline:
@@ -120,6 +183,7 @@ class SDFPipeline:
         self._resident_hypotheses, self._last_hypotheses = BoundedCache(limit), None
         self._refiners = BoundedCache(limit)      # refine: per (K, V, shape_optimization, point-cloud term on / off)
         self._ignored_warned = False
+        self._trajectory = None                   # step_log: the last call's states and what they were fitted to
 
     def _parse_config(self, config: Dict) -> None:
         """simple_setup.py:91-109"""
@@ -133,6 +197,7 @@ class SDFPipeline:
         # without the key its _preprocess_depth raises AttributeError; None here = no far-field clipping)
         self._far_field = config.get("far_field")
         self.sdf_grad_mode = parse_sdf_grad_mode(config.get("sdf_grad_mode"))
+        self.step_log = bool(config.get("step_log", False))
         self.config = config
 
     # ---- the reference's helpers, same names ------------------------------------------------------------------
@@ -251,12 +316,36 @@ class SDFPipeline:
 
         depth_images (N,H,W) or (H,W): masked and far-field-clipped IN PLACE (pass a copy if the full depth is used
         afterwards); masks: same shape, bool; color_images: unused (visualisation only in the reference).
-        Returns (position (1,3), orientation (1,4) normalised scalar-last, scale (1,), latent (1,L))."""
-        if (visualize or log_path is not None or animation_path is not None) and not self._ignored_warned:
+        Returns (position (1,3), orientation (1,4) normalised scalar-last, scale (1,), latent (1,L)).
+
+        With ``step_log: true`` in the config the loop records its states (the estimate is bit for bit the one without
+        the key): ``last_trajectory()`` returns the initial estimate and the ``max_iterations`` iterates,
+        ``render_trajectory()`` their frames; log_path: the reference's pickle ``{"config", "log"}`` -- the inputs
+        (:339-349), the initial estimate (:363-373), one entry per iteration (:482-490), CPU tensors of the reference's
+        shapes, which ``play_log.py`` reads; ``timestamp`` is seconds since the call began, from events recorded on the
+        loop's stream between iterations and read after the loop (no synchronisation per iteration).  animation_path:
+        the reference's folder (:870-912) -- ``depth/``, ``depth_error/``, ``sdf/`` with ``{iteration:06}.png`` from 1,
+        ``color_input.png``, ``depth_input.png``, ``mask.png``, ``preprocessed_depth_input.png`` (the first view; the
+        depth ones through the colour map) and ``depth.gif``, ``depth_error.gif``, ``sdf.gif`` (the reference: mp4
+        through ffmpeg).  Frames are raw ``W x H`` images, not matplotlib figures.  ``visualize`` stays ignored, and
+        the forms without a single trajectory (``orientation_hypotheses > 1``, a loop sharded over ranks) raise
+        ``NotImplementedError`` when a path is given."""
+        recording = self.step_log
+        if recording:
+            # seconds since HERE are the log's timestamps; and whatever this call does -- a form that records nothing,
+            # an exception -- no earlier call's trajectory is left to be taken for this one's
+            start = _event(self._dev)
+            self._trajectory = None
+        ignored = visualize or (not recording and (log_path is not None or animation_path is not None))
+        if ignored and not self._ignored_warned:
             warnings.warn("sdfest_amd.SDFPipeline: visualize / log_path / animation_path are accepted and ignored "
                           "(plots, step logs and animations are outside the hot path)")
             self._ignored_warned = True
+        wants_files = recording and (log_path is not None or animation_path is not None)
         n_hypotheses = int(self.config.get("orientation_hypotheses", 1))
+        if n_hypotheses != 1 and wants_files:
+            raise NotImplementedError("step_log: orientation_hypotheses > 1 refines several estimates side by side and has "
+                                      "no single trajectory to log or animate")
         if n_hypotheses != 1:     # (the default path below is untouched by the key's absence or 1)
             if point_constraint is not None:
                 raise ValueError("point_constraint cannot be combined with orientation_hypotheses > 1: the K-row loop "
@@ -282,6 +371,10 @@ class SDFPipeline:
         # into the loop's own buffers; only the host-driven initialisation below needs them as tensors)
 
         loop = self._loop(n_imgs, shape_optimization)
+        if wants_files and loop.group is not None:
+            raise NotImplementedError("step_log: a loop sharded over ranks holds a part of the views on every rank and "
+                                      "has no single trajectory to log or animate")
+        record = _StepRecord(dev, start, depth_images, masks, color_images, animation_path) if recording else None
         with torch.no_grad():
             # :333-334, and the observation into the loop's buffers in the same pass
             if (depth_images.is_cuda and depth_images.dtype is torch.float32 and depth_images.is_contiguous()
@@ -296,6 +389,8 @@ class SDFPipeline:
                     depth_images[depth_images > self._far_field] = 0
                 loop.rebind(depth_images, camera_positions, camera_orientations, point_constraint)
                 depth_images = loop.target if loop.group is None else depth_images.to(dev, torch.float32)
+            if record is not None:
+                record.inputs_done = _event(dev)
             # :352-359
             resident = self._resident_init(n_imgs)
             if resident is not None:
@@ -309,22 +404,99 @@ class SDFPipeline:
                     loop.cam_quat_all if camera_orientations is None else camera_orientations,
                     prior_orientation_distribution, training_orientation_distribution)
             # :381-470
-            position, orientation, scale, latent_shape = loop(position, orientation, scale, latent_shape)
+            if record is None:
+                position, orientation, scale, latent_shape = loop(position, orientation, scale, latent_shape)
+            else:
+                record.begin(loop, position, orientation, scale, latent_shape)
+                position, orientation, scale, latent_shape = loop(position, orientation, scale, latent_shape,
+                                                                  history=record.history)
             if resident is not None and resident.empty_views():
                 # (:780-781 -- known only now: the counts were never waited for in front of the launches)
                 raise NoDepthError
         self._last_loop = loop
         self._last_estimate = loop
+        if record is not None:
+            self._trajectory = record
+            if log_path is not None:
+                self._write_log(record, log_path)
+            if animation_path is not None:
+                self._write_animation(record, animation_path)
         # :583-596 -- "best_inlier_ratio" returns the tensors the reference stored, which its optimiser went on
         # updating in place: the last iterate as well (pipeline._BestEstimate); the snapshot at the best ratio is
         # self.best_estimate()
         return self._gauss_newton((position, orientation, scale, latent_shape))
 
+    # ---- step_log: the last call's trajectory --------------------------------------------------------------------
+    def _recorded(self) -> "_StepRecord":
+        if self._trajectory is None:
+            raise RuntimeError("no trajectory: set step_log: true in the config and call the pipeline first")
+        return self._trajectory
+
+    def last_trajectory(self) -> tuple:
+        """(positions (T,3), orientations (T,4), scales (T,), latents (T,L)) of the last ``__call__`` under
+        ``step_log: true``, T = max_iterations + 1: the initial estimate, then the loop's iterate after every iteration
+        (the last row is the loop's result -- what the call returned, before any ``gauss_newton_iterations``).  World
+        frame, device tensors."""
+        return self._recorded().states()
+
+    def render_trajectory(self, view: int = 0) -> Dict[str, torch.Tensor]:
+        """The frames of the last trajectory in camera `view`: ``visualization.trajectory_frames`` -- {"depth",
+        "depth_error", "sdf"}, each (T,H,W,3) uint8 on the device, from one batched decode, two batched renders and two
+        shading passes."""
+        from .visualization import trajectory_frames
+        r = self._recorded()
+        return trajectory_frames(self, r.states(), r.target, r.cam_pos, r.cam_quat, view=view)
+
+    def _write_log(self, record: "_StepRecord", log_path: str) -> None:
+        """the reference's pickle (:339-349, :363-373, :482-490; written as simple_setup.py's ``_write_log_data``)"""
+        positions, orientations, scales, latents = (t.cpu() for t in record.states())
+        stamps = record.timestamps()
+        cams = {"camera_positions": record.cam_pos.cpu(), "camera_orientations": record.cam_quat.cpu()}
+        log = [dict({"timestamp": stamps[0], "depth_images": record.target.cpu(),
+                     "color_images": record.color.cpu() if isinstance(record.color, torch.Tensor) else record.color,
+                     "masks": record.masks.cpu()}, **cams)]
+        for t in range(positions.shape[0]):
+            entry = {"timestamp": stamps[1 + t]}
+            if t == 0:
+                entry.update(cams)
+            entry.update({"latent_shape": latents[t:t + 1].clone(), "position": positions[t:t + 1].clone(),
+                          "scale_inv": 1 / scales[t:t + 1], "orientation": orientations[t:t + 1].clone()})
+            log.append(entry)
+        with open(log_path, "wb") as f:
+            pickle.dump({"config": self.config, "log": log}, f)
+
+    def _write_animation(self, record: "_StepRecord", animation_path: str) -> None:
+        from .visualization import depth_range, shade_frames, write_animation, write_frames
+        from PIL import Image
+        os.makedirs(animation_path, exist_ok=True)
+        frames = self.render_trajectory(view=0)
+        for name in ("depth", "depth_error", "sdf"):
+            host = frames[name][1:].cpu()           # the reference draws after every iteration: 1 .. max_iterations
+            write_frames(os.path.join(animation_path, name), host, first=1)
+            if host.shape[0]:
+                write_animation(os.path.join(animation_path, f"{name}.gif"), host)
+        inputs = torch.stack([record.raw_depth, record.target[0]])
+        # each image over its own range, as the reference's imshow scales each by itself (a far wall in the raw depth
+        # must not squeeze the preprocessed image into a few bins)
+        mapped = shade_frames(inputs, None, None, None, None, self.cam, value_range=depth_range(inputs),
+                              outputs=("depth",))["depth"]
+        Image.fromarray(mapped[0].cpu().numpy()).save(os.path.join(animation_path, "depth_input.png"))
+        Image.fromarray(mapped[1].cpu().numpy()).save(os.path.join(animation_path,
+                                                                         "preprocessed_depth_input.png"))
+        Image.fromarray((record.masks[0].cpu().numpy() != 0).astype("uint8") * 255).save(
+            os.path.join(animation_path, "mask.png"))
+        color = record.color[0] if isinstance(record.color, torch.Tensor) and record.color.dim() == 4 else record.color
+        color = torch.as_tensor(color).detach().cpu()
+        if color.is_floating_point():
+            color = (color.clamp(0, 1) * 255).round()
+        Image.fromarray(color.to(torch.uint8).numpy()).save(os.path.join(animation_path, "color_input.png"))
+
     def estimate_objects(self, depth_images: torch.Tensor, masks: torch.Tensor,
                          camera_positions: Optional[torch.Tensor] = None,
                          camera_orientations: Optional[torch.Tensor] = None, shape_optimization: bool = True,
                          prior_orientation_distribution: Optional[torch.Tensor] = None,
-                         training_orientation_distribution: Optional[torch.Tensor] = None) -> tuple:
+                         training_orientation_distribution: Optional[torch.Tensor] = None,
+                         log_path: Optional[str] = None, animation_path: Optional[str] = None) -> tuple:
         """The K detected objects of ONE frame at once: what a caller of the reference does with a loop of K
         ``pipeline(depth, mask_k, color)`` calls (one per instance mask), as one call whose K estimates are optimised side
         by side (``pipeline.MultiObjectRenderAndCompare``: one launch sequence per iteration for all of them).
@@ -347,7 +519,10 @@ class SDFPipeline:
         "best_inlier_ratio" every object's inlier bookkeeping (:177-211, on its last view) runs beside the loop and
         ``best_estimates()`` returns it.
         ``NoDepthError`` for an (object, view) without a valid depth pixel is raised AFTER the call's work was
-        enqueued (the counts are read behind the launches), where the reference raises before optimising (:780-781)."""
+        enqueued (the counts are read behind the launches), where the reference raises before optimising (:780-781).
+        log_path / animation_path: K estimates have no single trajectory -- ``NotImplementedError`` under ``step_log``,
+        ignored with ``__call__``'s warning without it."""
+        self._no_step_files("estimate_objects", log_path, animation_path)
         if depth_images.dim() == 2 and masks.dim() == 3 and tuple(masks.shape[1:]) == tuple(depth_images.shape):
             V = 1
         elif (depth_images.dim() == 3 and masks.dim() == 4 and masks.shape[1] == depth_images.shape[0]
@@ -366,6 +541,17 @@ class SDFPipeline:
             loop.rebind(depth_images.reshape(V, H, W), camera_positions, camera_orientations,
                         masks=masks.reshape(K, V, H, W), far_field=self._far_field)
             return self._run_objects(loop, prior_orientation_distribution, training_orientation_distribution)
+
+    def _no_step_files(self, what: str, log_path, animation_path) -> None:
+        if log_path is None and animation_path is None:
+            return
+        if self.step_log:
+            raise NotImplementedError(f"step_log: {what} refines K estimates side by side and has no single trajectory "
+                                      "to log or animate; call the pipeline per object for a log")
+        if not self._ignored_warned:
+            warnings.warn("sdfest_amd.SDFPipeline: visualize / log_path / animation_path are accepted and ignored "
+                          "(plots, step logs and animations are outside the hot path)")
+            self._ignored_warned = True
 
     def _objects_loop(self, K: int, V: int, shape_optimization: bool) -> MultiObjectRenderAndCompare:
         """the K-row loop of ``estimate_objects`` and ``estimate_frames``, built on first use and kept"""
@@ -408,7 +594,8 @@ class SDFPipeline:
 
     def estimate_frames(self, depth_images: torch.Tensor, masks: torch.Tensor, shape_optimization: bool = True,
                         prior_orientation_distribution: Optional[torch.Tensor] = None,
-                        training_orientation_distribution: Optional[torch.Tensor] = None) -> tuple:
+                        training_orientation_distribution: Optional[torch.Tensor] = None,
+                        log_path: Optional[str] = None, animation_path: Optional[str] = None) -> tuple:
         """K DIFFERENT frames with one object each -- what a caller of the reference does with K
         ``pipeline(depth_k, mask_k, color_k)`` calls over a sequence or a dataset --, refined side by side as the K rows
         of ``estimate_objects``' loop (the same cached ``MultiObjectRenderAndCompare`` and initialisation: a loop built
@@ -420,7 +607,9 @@ class SDFPipeline:
         (K,), latent (K,L): row k follows ``estimate_objects(depth_images[k], masks[k][None])`` as that follows
         ``__call__`` (its docstring); K copies of one frame under K masks are ``estimate_objects(frame, masks)`` bit for
         bit.  ``best_estimates()`` works as after ``estimate_objects``.  ``ValueError`` for other shapes;
-        ``NoDepthError`` for a frame without a valid pixel, raised AFTER the call's work was enqueued."""
+        ``NoDepthError`` for a frame without a valid pixel, raised AFTER the call's work was enqueued.
+        log_path / animation_path: as in ``estimate_objects``."""
+        self._no_step_files("estimate_frames", log_path, animation_path)
         if depth_images.dim() != 3 or tuple(masks.shape) != tuple(depth_images.shape):
             raise ValueError("depth_images (K,H,W) and masks (K,H,W) are expected, got "
                              f"{tuple(depth_images.shape)} and {tuple(masks.shape)}")
