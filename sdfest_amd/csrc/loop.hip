@@ -1250,39 +1250,62 @@ extern "C" int sdfr_views_to_pose_grad_deferred(const float* orientation, const 
 }
 
 namespace {
-int loop_tail_impl(const char* fn, float* params, float* grads, float* exp_avg, float* exp_avg_sq, int* step, int n_params,
-                   float lr_position, float lr_orientation, float lr_scale, float lr_latent,
+// What the four tail entry points do NOT share: which views the launch's partials cover and what runs beside the chain.
+struct TailForm {
+  enum Kind { kViews, kObjects, kRecords } kind = kViews;
+  int n_obj = 1;                   // kObjects: workgroup k is object k, the launch tiles n_obj * V views
+  float* latents = nullptr;        // kObjects: where the updated latents go, packed (or NULL)
+  const float* records = nullptr;  // kRecords: the chain runs over V_total exchanged records, V views from view_begin
+  int V_total = 0, view_begin = 0; //           are this rank's shard (cam_pos / cam_quat hold all V_total cameras)
+  FusedDepth fd{};                 // sdfr_loop_tail_fused: the render step was one launch
+  float* decoder_tape = nullptr;   // ... and the next Linear stack runs in this launch
+  unsigned* arrivals = nullptr;
+};
+
+// The one host path to loop_tail_kernel: the shared argument checks (each entry point's own precedence and texts), the
+// argument block, the launch.
+int loop_tail_impl(const char* fn, const TailForm& x, float* params, float* grads, float* exp_avg, float* exp_avg_sq,
+                   int* step, int n_params, float lr_position, float lr_orientation, float lr_scale, float lr_latent,
                    int update_latent, const float* cam_pos, const float* cam_quat, int V,
                    const void* render_workspace, size_t render_partials_offset, int W, int H,
                    const void* pc_workspace, const int* offsets, int max_view_points, float* pos_c,
                    float* quat_c, float* inv_scale, float* scale_v, float* pc_loss,
                    const float* con_source, const float* con_target, float con_weight, float* con_loss,
-                   const sdfr_decoder* decoder, const float* decoder_t_mid, int device, void* stream,
-                   const FusedDepth& fd, float* decoder_tape = nullptr, unsigned* arrivals = nullptr) {
+                   const sdfr_decoder* decoder, const float* decoder_t_mid, int device, void* stream) {
+  const bool from_records = x.kind == TailForm::kRecords, objects = x.kind == TailForm::kObjects;
   if ((decoder != nullptr) != (decoder_t_mid != nullptr))
     return fail(SDFR_E_NULL, "%s: decoder and decoder_t_mid go together", fn);
-  if (V < 1 || V > kDeferredMaxViews) return fail(SDFR_E_INVALID, "%s: V=%d out of range [1,%d]", fn, V, kDeferredMaxViews);
+  if (from_records) {
+    if (x.V_total < 1 || x.V_total > 65535 || V < 0 || x.view_begin < 0 || x.view_begin + V > x.V_total)
+      return fail(SDFR_E_INVALID, "%s: shard [%d, %d) of %d views", fn, x.view_begin, x.view_begin + V, x.V_total);
+  } else {
+    if (x.n_obj < 1 || x.n_obj > 65535) return fail(SDFR_E_INVALID, "%s: n_objects=%d", fn, x.n_obj);
+    if (V < 1 || V > kDeferredMaxViews) return fail(SDFR_E_INVALID, "%s: V=%d out of range [1,%d]", fn, V, kDeferredMaxViews);
+    if ((long long)x.n_obj * V > 65535) return fail(SDFR_E_INVALID, "%s: %d objects x %d views exceed a launch", fn, x.n_obj, V);
+  }
   if (n_params < 8 || n_params > 256) return fail(SDFR_E_INVALID, "%s: n_params=%d out of range [8,256]", fn, n_params);
-  if (!params || !grads || !exp_avg || !exp_avg_sq || !step || !cam_pos || !cam_quat || !pos_c || !quat_c ||
-      !inv_scale || !scale_v)
+  if (!params || !grads || !exp_avg || !exp_avg_sq || !step || !cam_pos || !cam_quat || (from_records && !x.records) ||
+      ((!from_records || V > 0) && (!pos_c || !quat_c || !inv_scale || !scale_v)))
     return fail(SDFR_E_NULL, "%s: NULL pointer argument", fn);
   if (render_workspace && (W <= 0 || H <= 0)) return fail(SDFR_E_INVALID, "%s: W=%d H=%d", fn, W, H);
-  if (pc_workspace && (max_view_points <= 0 || (!offsets && V > 1)))
+  const int B = x.n_obj * V;   // the views of the render / sampler launch whose partials this one reduces
+  if (pc_workspace && (max_view_points <= 0 || (!offsets && B > 1)))
     return fail(SDFR_E_INVALID, "%s: bad sampler arguments", fn);
   if (con_source && !con_target) return fail(SDFR_E_NULL, "%s: constraint target is NULL", fn);
   if (render_workspace && ((uintptr_t)render_workspace % alignof(ViewSetup) || render_partials_offset % 16))
     return fail(SDFR_E_INVALID, "%s: render_workspace / partials offset misaligned", fn);
   SDFR_HIP_TRY(hipSetDevice(device));
-  // (the one-launch render step always works in 32 x 8 tiles)
-  const TileGeom geom = (render_workspace && !fd.view_cnt) ? backward_geom(V, W, H) : kSmallTile;
+  // (the tiling of the launch of ALL views; the one-launch render step always works in 32 x 8 tiles)
+  const TileGeom geom = (render_workspace && !x.fd.view_cnt) ? backward_geom(B, W, H) : kSmallTile;
   const int nblk = pc_workspace ? (max_view_points + kSamplerPts - 1) / kSamplerPts : 0;
   const float* pc_part = (const float*)pc_workspace;
   LoopTailArgs a{};
-  a.fd = fd;
+  a.fd = x.fd;
   a.params = params; a.grads = grads; a.m = exp_avg; a.v = exp_avg_sq; a.step = step; a.n = n_params;
   a.lr_pos = lr_position; a.lr_quat = lr_orientation; a.lr_scale = lr_scale; a.lr_latent = lr_latent;
   a.update_latent = update_latent;
-  a.cam_pos = cam_pos; a.cam_quat = cam_quat; a.V = V;
+  a.cam_pos = cam_pos + 3 * (size_t)x.view_begin; a.cam_quat = cam_quat + 4 * (size_t)x.view_begin; a.V = V;
+  if (from_records) { a.records = x.records; a.V_all = x.V_total; a.cam_quat_all = cam_quat; }
   a.setup = (const ViewSetup*)render_workspace;
   a.tile_part = render_workspace ? (const float*)((const char*)render_workspace + render_partials_offset) : nullptr;
   a.W = W; a.H = H;
@@ -1290,29 +1313,32 @@ int loop_tail_impl(const char* fn, float* params, float* grads, float* exp_avg, 
   a.tile_w = geom.w(); a.tile_h = geom.h();
   a.stride = (render_workspace && geom.sx * geom.sy > 1) ? backward_tile_stride(W, H) : 0;
   a.pc_part = pc_part;
-  a.pc_loss_part = (pc_workspace && pc_loss) ? pc_part + (size_t)V * nblk * 8 : nullptr;
+  a.pc_loss_part = (pc_workspace && pc_loss) ? pc_part + (size_t)B * nblk * 8 : nullptr;
   a.offsets = offsets; a.n_single = max_view_points; a.nblk = nblk;
   a.pos_c = pos_c; a.quat_c = quat_c; a.inv_scale = inv_scale; a.scale_v = scale_v; a.pc_loss = pc_loss;
   a.con_source = con_source; a.con_target = con_target; a.con_weight = con_weight; a.con_loss = con_loss;
-  if (decoder) {
+  a.n_obj = x.n_obj;
+  a.latents = x.latents;
+  if (decoder) {   // the VJP's last stage (objects: the batched one's, one row per object)
     decoder_fc_desc(decoder, &a.fc, &a.dec_params, nullptr);
     a.fc_one_wave = decoder_fc_one_wave(decoder, a.fc) ? 1 : 0;
     if (a.fc.width[0] != n_params - 8)
-      return fail(SDFR_E_INVALID, "%s: the decoder's latent has %d entries, the parameter vector %d", fn, a.fc.width[0],
-                  n_params - 8);
+      return objects ? fail(SDFR_E_INVALID, "%s: n_params=%d does not hold the decoder's latent (%d)", fn, n_params,
+                            a.fc.width[0])
+                     : fail(SDFR_E_INVALID, "%s: the decoder's latent has %d entries, the parameter vector %d", fn,
+                            a.fc.width[0], n_params - 8);
     a.t_mid = decoder_t_mid;
   }
-  a.n_obj = 1;
-  unsigned nwg = 1;
-  if (decoder_tape || arrivals) {
-    if (!decoder_tape || !arrivals) return fail(SDFR_E_NULL, "%s: decoder_tape and arrivals go together", fn);
+  unsigned nwg = (unsigned)x.n_obj;
+  if (x.decoder_tape || x.arrivals) {
+    if (!x.decoder_tape || !x.arrivals) return fail(SDFR_E_NULL, "%s: decoder_tape and arrivals go together", fn);
     if (!decoder || !update_latent || !a.fc_one_wave)
       return fail(SDFR_E_INVALID, "%s: the next Linear stack in this launch needs a decoder whose leading layers are "
                   "at most %d wide (and its one-wave form switched on), and update_latent", fn, kFcWaveWidth);
     size_t tape_fc_off = 0;
     decoder_fc_desc(decoder, &a.fc, &a.dec_params, &tape_fc_off);
-    a.fc_next = decoder_tape + tape_fc_off;
-    a.arrivals = arrivals;
+    a.fc_next = x.decoder_tape + tape_fc_off;
+    a.arrivals = x.arrivals;
     nwg = (unsigned)((a.fc.width[a.fc.n_fc] + kFcBlock - 1) / kFcBlock);
   }
   hipLaunchKernelGGL(loop_tail_kernel, dim3(nwg), dim3(256), 0, (hipStream_t)stream, a);
@@ -1329,11 +1355,11 @@ extern "C" int sdfr_loop_tail(float* params, float* grads, float* exp_avg, float
                               float* quat_c, float* inv_scale, float* scale_v, float* pc_loss,
                               const float* con_source, const float* con_target, float con_weight, float* con_loss,
                               const sdfr_decoder* decoder, const float* decoder_t_mid, int device, void* stream) {
-  return loop_tail_impl("sdfr_loop_tail", params, grads, exp_avg, exp_avg_sq, step, n_params, lr_position,
+  return loop_tail_impl("sdfr_loop_tail", TailForm{}, params, grads, exp_avg, exp_avg_sq, step, n_params, lr_position,
                         lr_orientation, lr_scale, lr_latent, update_latent, cam_pos, cam_quat, V, render_workspace,
                         render_partials_offset, W, H, pc_workspace, offsets, max_view_points, pos_c, quat_c, inv_scale,
                         scale_v, pc_loss, con_source, con_target, con_weight, con_loss, decoder, decoder_t_mid, device,
-                        stream, FusedDepth{});
+                        stream);
 }
 
 extern "C" int sdfr_loop_tail_fused(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int* step,
@@ -1350,16 +1376,17 @@ extern "C" int sdfr_loop_tail_fused(float* params, float* grads, float* exp_avg,
   if (!render_workspace) return fail(SDFR_E_NULL, "%s: render_workspace is NULL", fn);
   if (view_count_offset % 4 || tile_loss_offset % 16)
     return fail(SDFR_E_INVALID, "%s: view count / tile loss offsets misaligned", fn);
-  FusedDepth fd;
-  fd.view_cnt = (float*)((char*)render_workspace + view_count_offset);
-  fd.tile_loss = (const float*)((const char*)render_workspace + tile_loss_offset);
-  fd.weight = depth_weight;
-  fd.depth_loss = depth_loss;
-  return loop_tail_impl(fn, params, grads, exp_avg, exp_avg_sq, step, n_params, lr_position, lr_orientation, lr_scale,
+  TailForm x;
+  x.fd.view_cnt = (float*)((char*)render_workspace + view_count_offset);
+  x.fd.tile_loss = (const float*)((const char*)render_workspace + tile_loss_offset);
+  x.fd.weight = depth_weight;
+  x.fd.depth_loss = depth_loss;
+  x.decoder_tape = decoder_tape;
+  x.arrivals = arrivals;
+  return loop_tail_impl(fn, x, params, grads, exp_avg, exp_avg_sq, step, n_params, lr_position, lr_orientation, lr_scale,
                         lr_latent, update_latent, cam_pos, cam_quat, V, render_workspace, render_partials_offset, W, H,
                         pc_workspace, offsets, max_view_points, pos_c, quat_c, inv_scale, scale_v, pc_loss, con_source,
-                        con_target, con_weight, con_loss, decoder, decoder_t_mid, device, stream, fd, decoder_tape,
-                        arrivals);
+                        con_target, con_weight, con_loss, decoder, decoder_t_mid, device, stream);
 }
 
 extern "C" int sdfr_loop_tail_objects(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int* step,
@@ -1370,53 +1397,14 @@ extern "C" int sdfr_loop_tail_objects(float* params, float* grads, float* exp_av
                                       const int* offsets, int max_view_points, float* pos_c, float* quat_c,
                                       float* inv_scale, float* scale_v, float* pc_loss, const sdfr_decoder* decoder,
                                       const float* decoder_t_mid, float* latents, int device, void* stream) {
-  const char* fn = "sdfr_loop_tail_objects";
-  if ((decoder != nullptr) != (decoder_t_mid != nullptr))
-    return fail(SDFR_E_NULL, "%s: decoder and decoder_t_mid go together", fn);
-  if (n_objects < 1 || n_objects > 65535) return fail(SDFR_E_INVALID, "%s: n_objects=%d", fn, n_objects);
-  if (V < 1 || V > kDeferredMaxViews) return fail(SDFR_E_INVALID, "%s: V=%d out of range [1,%d]", fn, V, kDeferredMaxViews);
-  if ((long long)n_objects * V > 65535) return fail(SDFR_E_INVALID, "%s: %d objects x %d views exceed a launch", fn, n_objects, V);
-  if (n_params < 8 || n_params > 256) return fail(SDFR_E_INVALID, "%s: n_params=%d out of range [8,256]", fn, n_params);
-  if (!params || !grads || !exp_avg || !exp_avg_sq || !step || !cam_pos || !cam_quat || !pos_c || !quat_c ||
-      !inv_scale || !scale_v)
-    return fail(SDFR_E_NULL, "%s: NULL pointer argument", fn);
-  if (render_workspace && (W <= 0 || H <= 0)) return fail(SDFR_E_INVALID, "%s: W=%d H=%d", fn, W, H);
-  const int B = n_objects * V;
-  if (pc_workspace && (max_view_points <= 0 || (!offsets && B > 1)))
-    return fail(SDFR_E_INVALID, "%s: bad sampler arguments", fn);
-  if (render_workspace && ((uintptr_t)render_workspace % alignof(ViewSetup) || render_partials_offset % 16))
-    return fail(SDFR_E_INVALID, "%s: render_workspace / partials offset misaligned", fn);
-  SDFR_HIP_TRY(hipSetDevice(device));
-  const TileGeom geom = render_workspace ? backward_geom(B, W, H) : kSmallTile;   // the tiling of the launch of ALL views
-  const int nblk = pc_workspace ? (max_view_points + kSamplerPts - 1) / kSamplerPts : 0;
-  const float* pc_part = (const float*)pc_workspace;
-  LoopTailArgs a{};
-  a.params = params; a.grads = grads; a.m = exp_avg; a.v = exp_avg_sq; a.step = step; a.n = n_params;
-  a.lr_pos = lr_position; a.lr_quat = lr_orientation; a.lr_scale = lr_scale; a.lr_latent = lr_latent;
-  a.update_latent = update_latent;
-  a.cam_pos = cam_pos; a.cam_quat = cam_quat; a.V = V;
-  a.setup = (const ViewSetup*)render_workspace;
-  a.tile_part = render_workspace ? (const float*)((const char*)render_workspace + render_partials_offset) : nullptr;
-  a.W = W; a.H = H;
-  a.ntx = render_workspace ? geom.nx(W) : 0; a.nty = render_workspace ? geom.ny(H) : 0;
-  a.tile_w = geom.w(); a.tile_h = geom.h();
-  a.stride = (render_workspace && geom.sx * geom.sy > 1) ? backward_tile_stride(W, H) : 0;
-  a.pc_part = pc_part;
-  a.pc_loss_part = (pc_workspace && pc_loss) ? pc_part + (size_t)B * nblk * 8 : nullptr;
-  a.offsets = offsets; a.n_single = max_view_points; a.nblk = nblk;
-  a.pos_c = pos_c; a.quat_c = quat_c; a.inv_scale = inv_scale; a.scale_v = scale_v; a.pc_loss = pc_loss;
-  a.n_obj = n_objects;
-  a.latents = latents;
-  if (decoder) {   // the batched VJP's last stage (sdfr_decoder_backward_latent_deferred_batch), one row per object
-    decoder_fc_desc(decoder, &a.fc, &a.dec_params, nullptr);
-    if (a.fc.width[0] != n_params - 8)
-      return fail(SDFR_E_INVALID, "%s: n_params=%d does not hold the decoder's latent (%d)", fn, n_params, a.fc.width[0]);
-    a.fc_one_wave = decoder_fc_one_wave(decoder, a.fc) ? 1 : 0;
-    a.t_mid = decoder_t_mid;
-  }
-  hipLaunchKernelGGL(loop_tail_kernel, dim3((unsigned)n_objects), dim3(256), 0, (hipStream_t)stream, a);
-  SDFR_HIP_TRY(hipGetLastError());
-  return 0;
+  TailForm x;
+  x.kind = TailForm::kObjects;
+  x.n_obj = n_objects;
+  x.latents = latents;
+  return loop_tail_impl("sdfr_loop_tail_objects", x, params, grads, exp_avg, exp_avg_sq, step, n_params, lr_position,
+                        lr_orientation, lr_scale, lr_latent, update_latent, cam_pos, cam_quat, V, render_workspace,
+                        render_partials_offset, W, H, pc_workspace, offsets, max_view_points, pos_c, quat_c, inv_scale,
+                        scale_v, pc_loss, nullptr, nullptr, 0.0f, nullptr, decoder, decoder_t_mid, device, stream);
 }
 
 extern "C" int sdfr_loop_view_records(const void* render_workspace, size_t render_partials_offset, int W, int H,
@@ -1456,36 +1444,15 @@ extern "C" int sdfr_loop_tail_records(float* params, float* grads, float* exp_av
                                       float* quat_c, float* inv_scale, float* scale_v, const float* con_source,
                                       const float* con_target, float con_weight, float* con_loss,
                                       const sdfr_decoder* decoder, const float* decoder_t_mid, int device, void* stream) {
-  const char* fn = "sdfr_loop_tail_records";
-  if ((decoder != nullptr) != (decoder_t_mid != nullptr))
-    return fail(SDFR_E_NULL, "%s: decoder and decoder_t_mid go together", fn);
-  if (V_total < 1 || V_total > 65535 || V_local < 0 || view_begin < 0 || view_begin + V_local > V_total)
-    return fail(SDFR_E_INVALID, "%s: shard [%d, %d) of %d views", fn, view_begin, view_begin + V_local, V_total);
-  if (n_params < 8 || n_params > 256) return fail(SDFR_E_INVALID, "%s: n_params=%d out of range [8,256]", fn, n_params);
-  if (!params || !grads || !exp_avg || !exp_avg_sq || !step || !cam_pos || !cam_quat || !records ||
-      (V_local > 0 && (!pos_c || !quat_c || !inv_scale || !scale_v)))
-    return fail(SDFR_E_NULL, "%s: NULL pointer argument", fn);
-  if (con_source && !con_target) return fail(SDFR_E_NULL, "%s: constraint target is NULL", fn);
-  SDFR_HIP_TRY(hipSetDevice(device));
-  LoopTailArgs a{};
-  a.params = params; a.grads = grads; a.m = exp_avg; a.v = exp_avg_sq; a.step = step; a.n = n_params;
-  a.lr_pos = lr_position; a.lr_quat = lr_orientation; a.lr_scale = lr_scale; a.lr_latent = lr_latent;
-  a.update_latent = update_latent;
-  a.cam_pos = cam_pos + 3 * (size_t)view_begin; a.cam_quat = cam_quat + 4 * (size_t)view_begin; a.V = V_local;
-  a.records = records; a.V_all = V_total; a.cam_quat_all = cam_quat;
-  a.pos_c = pos_c; a.quat_c = quat_c; a.inv_scale = inv_scale; a.scale_v = scale_v;
-  a.con_source = con_source; a.con_target = con_target; a.con_weight = con_weight; a.con_loss = con_loss;
-  if (decoder) {
-    decoder_fc_desc(decoder, &a.fc, &a.dec_params, nullptr);
-    a.fc_one_wave = decoder_fc_one_wave(decoder, a.fc) ? 1 : 0;
-    if (a.fc.width[0] != n_params - 8)
-      return fail(SDFR_E_INVALID, "%s: the decoder's latent has %d entries, the parameter vector %d", fn, a.fc.width[0],
-                  n_params - 8);
-    a.t_mid = decoder_t_mid;
-  }
-  hipLaunchKernelGGL(loop_tail_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, a);
-  SDFR_HIP_TRY(hipGetLastError());
-  return 0;
+  TailForm x;
+  x.kind = TailForm::kRecords;
+  x.records = records;
+  x.V_total = V_total;
+  x.view_begin = view_begin;
+  return loop_tail_impl("sdfr_loop_tail_records", x, params, grads, exp_avg, exp_avg_sq, step, n_params, lr_position,
+                        lr_orientation, lr_scale, lr_latent, update_latent, cam_pos, cam_quat, V_local, nullptr, 0, 0, 0,
+                        nullptr, nullptr, 0, pos_c, quat_c, inv_scale, scale_v, nullptr, con_source, con_target,
+                        con_weight, con_loss, decoder, decoder_t_mid, device, stream);
 }
 
 extern "C" size_t sdfr_depth_l1_workspace_bytes(int V, int W, int H) {

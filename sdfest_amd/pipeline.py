@@ -10,12 +10,13 @@ Adam are a handful of torch ops on tiny tensors.  The initialisation network, lo
 visualisation and mesh export of the reference are out of scope.
 """
 import ctypes
-from typing import Dict, List, Optional, Sequence
+from typing import Callable, Dict, List, NamedTuple, Optional, Sequence
 
 import torch
 
 from . import _graphs, _lib
-from .differentiable_renderer import SDF_GRAD_EXACT, Camera, render_depth_batch
+from .differentiable_renderer import (BWD_SMALL_TILES, SDF_GRAD_DETERMINISTIC, SDF_GRAD_EXACT, VIEW_RECORD_FLOATS,
+                                      BatchRenderPlan, Camera, render_depth_batch)
 from .losses import pc_loss_batch, point_constraint_loss
 
 
@@ -161,6 +162,119 @@ def _capture_iterations(loop, iteration, state, warmup=None, **mode):
     sequences = (iteration, many) if loop.graph_iterations > 1 else (iteration,)
     graphs = _graphs.capture(loop.dev, sequences, warmup or iteration, state, **mode)
     return graphs[0], graphs[1] if len(graphs) > 1 else None
+
+
+def _loop_buffers(loop, device, config: Dict, n_views: int, track_inliers: Optional[bool]) -> None:
+    """What the two captured loops allocate alike, as attributes of `loop` (``loop.W``, ``loop.H`` and ``loop.L`` are
+    set): the resolved device; the observed point clouds of `n_views` views at CAPACITY; the camera-frame view poses;
+    the inlier options."""
+    loop.dev = torch.device(device)
+    if loop.dev.index is None:
+        loop.dev = torch.device("cuda", torch.cuda.current_device())
+    f32 = dict(dtype=torch.float32, device=loop.dev)
+    i32 = dict(dtype=torch.int32, device=loop.dev)
+    W, H = loop.W, loop.H
+    # Room for every pixel of every view, counts and offsets on the device (sdfr_depth_to_points_resident): a new
+    # observation changes no address, no grid size and needs no host read, so the captured graphs stay valid.  The
+    # sampler's grids are sized for W * H points per view; blocks beyond a view's count leave at once
+    # (sampler_device.hpp), the reducers take the real lengths from `offsets`: the same sums in the same order as with
+    # exactly-sized buffers.  (Compact patches: the sampler's backward pre-sums 256 consecutive points.)
+    loop.max_pts = W * H
+    loop.points = torch.zeros((n_views * W * H, 3), **f32)
+    loop.offsets = torch.zeros(n_views + 1, **i32)
+    loop.counts = torch.zeros(n_views, **i32)
+    loop.ws_points = torch.empty(max(loop.L.sdfr_depth_points_workspace_bytes(n_views, W, H), 256), dtype=torch.uint8,
+                                 device=loop.dev)
+    loop.pos_c = torch.empty((n_views, 3), **f32)
+    loop.quat_c = torch.empty((n_views, 4), **f32)
+    loop.inv_scale = torch.empty((n_views,), **f32)
+    loop.scale_v = torch.empty((n_views,), **f32)
+    # the argument run the tail launches share (every buffer keeps its address for good)
+    loop._view_poses = (loop.pos_c.data_ptr(), loop.quat_c.data_ptr(), loop.inv_scale.data_ptr(),
+                        loop.scale_v.data_ptr())
+    loop.strategy = _selection_strategy(config)
+    loop.track_inliers = (loop.strategy == "best_inlier_ratio") if track_inliers is None else bool(track_inliers)
+    loop.rel_thr = float(config.get("relative_inlier_threshold", 0.03))
+    loop.max_history = int(config["max_iterations"])
+
+
+FORMS = ("separate", "tail", "one_launch", "fc_in_tail", "records")
+
+
+class _LoopGraphs:
+    """The captured graphs of one constraint key: `one` iteration and `many` (``graph_iterations`` of them; sharded: the
+    head, and a tail followed by the next head), the sharded loop's `tail`, and -- ``graph_collective`` -- whole
+    iterations with the all-reduce inside (`whole_one`, `whole`)."""
+    __slots__ = ("one", "many", "tail", "whole_one", "whole")
+
+    def __init__(self):
+        self.one = self.many = self.tail = self.whole_one = self.whole = None
+
+
+class _Form(NamedTuple):
+    """The launch sequence of a :class:`FusedRenderAndCompare`, by name (of FORMS; one ``_iteration_*`` method each,
+    "records": ``_whole_iteration``), and the few facts that do not follow from it."""
+    name: str
+    defer_pose: bool       # the per-view reductions run inside the gradient chain's (or the tail's) launch
+    defer_loss: bool       # the depth loss's tile records are reduced by the backward's launch
+    big_exchange: bool     # records: the d/dSDF volume travels (shape optimisation, exchange="sdf")
+    det: bool              # SDF_GRAD_DETERMINISTIC
+
+    records_form = property(lambda self: self.name == "records")
+    fused_render = property(lambda self: self.name in ("one_launch", "fc_in_tail"))
+    fc_in_tail = property(lambda self: self.name == "fc_in_tail")
+
+
+def _choose_form(V_all: int, V: int, world: int, grouped: bool, latent_size: int, R: int, shape_opt: bool,
+                 sdf_grad_mode: int, form: str, fuse_depth_loss: bool, merge_launches: bool,
+                 fused_render: Optional[bool], fc_in_tail: Optional[bool], defer_loss: Optional[bool], exchange: str,
+                 narrow_linear_stack: Callable[[], bool]) -> _Form:
+    """The form of a loop over `V_all` views of which this rank renders `V` (`world` ranks; `grouped`: there is a
+    process group, of one rank even), from the constructor's options: plain values in, a :class:`_Form` out, no GPU.
+    `narrow_linear_stack()` (``SDFDecoder.narrow_linear_stack``) is asked only for a one-launch render step with shape
+    optimisation.  A form that was asked for and cannot run is refused here, not by its first iteration."""
+    if form not in ("auto", "tail", "records"):
+        raise ValueError(f"form must be 'auto', 'tail' or 'records', got {form!r}")
+    # the records form: head (decoder .. both backward passes .. view records), [exchange], tail (decoder VJP, chain
+    # over ALL views' records, Adam, next poses).  A single process takes it too when the pose sums are asked to be
+    # independent of the batch (BWD_SMALL_TILES): same arithmetic as the ranks'.
+    must = grouped or bool(sdf_grad_mode & BWD_SMALL_TILES)
+    if form == "tail" and must:
+        raise ValueError("a process group (and BWD_SMALL_TILES) needs the records form")
+    # (the one-workgroup tail kernels own one parameter per thread: vectors of more than 256 entries -- a latent above
+    # 248 -- take the separate launches, whose Adam step has no such bound)
+    n_vec = 8 + int(latent_size)
+    records = must or form == "records" or (form == "auto" and V_all >= 8 and bool(fuse_depth_loss) and n_vec <= 256)
+    if records and n_vec > 256:
+        raise ValueError(f"the records form's tail handles parameter vectors of up to 256 entries, this decoder's "
+                         f"latent makes {n_vec}")
+    if V == 0:
+        raise ValueError(f"{V_all} view(s) cannot be sharded over {world} ranks: every rank needs one")
+    if records and not fuse_depth_loss:
+        raise ValueError("the sharded loop runs the loss-fused kernels (fuse_depth_loss=True)")
+    det = bool(sdf_grad_mode & SDF_GRAD_DETERMINISTIC)
+    if det and not records:
+        raise ValueError("SDF_GRAD_DETERMINISTIC in the loop goes with BWD_SMALL_TILES (or a process group)")
+    # gradient chain, point constraint, Adam and the next iteration's view poses in one launch (sdfr_loop_tail), the
+    # render pair in its step form: 26 -> 22 launches per iteration
+    defer_pose = bool(merge_launches) and V <= 64
+    tail = defer_pose and bool(fuse_depth_loss) and n_vec <= 256 and not records
+    can_fuse = tail and R <= 128 and V <= 8 and sdf_grad_mode in (0, 1)
+    if fused_render and not can_fuse:
+        raise ValueError("fused_render needs the tail form over at most 8 views of a grid up to 128^3, the loss-fused "
+                         "kernels, sdf_grad_mode 0 / 1 and a parameter vector of at most 256 entries")
+    # (default: where it measured faster -- with shape optimisation up to 4 views: 1 view 0.111 -> 0.099 ms per
+    # iteration, 2: 0.112 -> 0.102, 3: 0.114 -> 0.107, 4: 0.119 -> 0.116, but 7: 0.126 -> 0.132 -- every view adds a
+    # megabyte to sum, to clear and to collide in; pose only, where no volume exists, wherever it applies)
+    fused = (can_fuse and (V <= 4 or not shape_opt)) if fused_render is None else bool(fused_render)
+    can_fc = bool(fused and shape_opt and narrow_linear_stack())
+    if fc_in_tail and not can_fc:
+        raise ValueError("fc_in_tail needs fused_render, shape optimisation and a decoder with a narrow Linear stack")
+    fc = can_fc if fc_in_tail is None else bool(fc_in_tail)
+    name = ("records" if records else "separate" if not tail else "fc_in_tail" if fc else "one_launch" if fused
+            else "tail")
+    return _Form(name, defer_pose, (V < 32) if defer_loss is None else bool(defer_loss),
+                 records and bool(shape_opt) and exchange == "sdf", det)
 
 
 class RenderAndCompare:
@@ -378,7 +492,8 @@ class FusedRenderAndCompare:
         platform is what ``self.graph_collective_error`` says afterwards (None: captured; a string: why not -- the loop
         then runs the two-graph form).  An experiment, off by default.
         fused_render: the render pair of an iteration as ONE launch (``sdfr_render_step_fused_l1_pc``: a tile runs the
-        backward of its hit pixels right behind their march; include/sdfr.h) -- for the tail form (at most 7 views; every
+        backward of its hit pixels right behind their march; include/sdfr.h) -- for the tail form (at most 8 views,
+        SDFR_FUSED_MAX_VIEWS -- form="auto" leaves the tail form at 8, so there only with form="tail"; every
         view's depth term has its own weight / count and so its own unscaled d/dSDF volume) of a grid up to 128^3,
         loss-fused, with plain ``sdf_grad_mode`` weights; default: where it measured faster (up to 4 views with shape
         optimisation, any tail-form loop without; C5: 0.110 -> 0.100 ms per iteration).  Depth
@@ -395,62 +510,41 @@ class FusedRenderAndCompare:
         (``sdfr_views_to_pose_grad_deferred``, up to 64 views); False: one launch each.  Same numbers.
         track_inliers: run the inlier-ratio bookkeeping of :177-211 every iteration (two small launches);
         default: only for ``result_selection_strategy == "best_inlier_ratio"``."""
-        from .differentiable_renderer import BatchRenderPlan
-        # True: the depth-L1 runs inside the render kernels (sdfr_render_forward_l1 / _backward_l1) and the
-        # point-cloud L1 inside the sampler's backward (sdfr_pc_l1_backward);
-        # False: every loss is a kernel of its own between a forward and a backward.  Same results.
-        self.fuse_depth_loss = bool(fuse_depth_loss)
+        from .parallel import resolve_group, shard_views
         self.graph_iterations = max(1, int(graph_iterations))
         self.graph_collective = bool(graph_collective)
-        self._defer_loss_arg = defer_loss
         self.graph_collective_error = None
-        self.graph_whole = self.graph_whole_one = None
-        self.L = _lib.lib()
-        self.check = _lib.check
-        self.dec = decoder
-        self.cam = camera
-        self.cfg = config
-        self.dev = torch.device(device)
-        if self.dev.index is None:
-            self.dev = torch.device("cuda", torch.cuda.current_device())
+        self.L, self.check = _lib.lib(), _lib.check
+        self.dec, self.cam, self.cfg = decoder, camera, config
         self.shape_opt = bool(shape_optimization)
-        from .differentiable_renderer import BWD_SMALL_TILES, SDF_GRAD_DETERMINISTIC, VIEW_RECORD_FLOATS
-        from .parallel import resolve_group, shard_views
         if exchange not in ("sdf", "latent"):
             raise ValueError(f"exchange must be 'sdf' or 'latent', got {exchange!r}")
         self.group, self.rank, self.world = resolve_group(process_group)
         self.exchange = exchange
         self.sdf_grad_mode = int(sdf_grad_mode)
-        self.det = bool(self.sdf_grad_mode & SDF_GRAD_DETERMINISTIC)
-        # the records form of the iteration: head (decoder .. both backward passes .. view records), [exchange],
-        # tail (decoder VJP, chain over ALL views' records, Adam, next poses).  A single process takes it too when
-        # the pose sums are asked to be independent of the batch (BWD_SMALL_TILES): same arithmetic as the ranks'.
         if depth_images is None and views is None:
             raise ValueError("give the first observation (depth_images) or the number of views (views=)")
         self.V_all = int(depth_images.shape[0]) if depth_images is not None else int(views)
         if views is not None and int(views) != self.V_all:
             raise ValueError(f"views={views} but depth_images holds {self.V_all}")
-        if form not in ("auto", "tail", "records"):
-            raise ValueError(f"form must be 'auto', 'tail' or 'records', got {form!r}")
-        must = self.group is not None or bool(self.sdf_grad_mode & BWD_SMALL_TILES)
-        if form == "tail" and must:
-            raise ValueError("a process group (and BWD_SMALL_TILES) needs the records form")
-        # (the one-workgroup tail kernels own one parameter per thread: vectors of more than 256 entries -- a latent
-        # above 248 -- take the separate launches, whose Adam step has no such bound; a form that cannot is refused here,
-        # not by its first iteration)
-        n_vec = 8 + int(decoder.latent_size)
-        self.records_form = must or form == "records" or (form == "auto" and self.V_all >= 8 and bool(fuse_depth_loss)
-                                                          and n_vec <= 256)
-        if self.records_form and n_vec > 256:
-            raise ValueError(f"the records form's tail handles parameter vectors of up to 256 entries, this decoder's "
-                             f"latent makes {n_vec}")
         self.view_begin, self.view_end = shard_views(self.V_all, self.rank, self.world)
-        if self.view_end == self.view_begin:
-            raise ValueError(f"{self.V_all} view(s) cannot be sharded over {self.world} ranks: every rank needs one")
-        if self.records_form and not fuse_depth_loss:
-            raise ValueError("the sharded loop runs the loss-fused kernels (fuse_depth_loss=True)")
-        if self.det and not self.records_form:
-            raise ValueError("SDF_GRAD_DETERMINISTIC in the loop goes with BWD_SMALL_TILES (or a process group)")
+        V, H, W = self.view_end - self.view_begin, int(camera.height), int(camera.width)
+        R = decoder._volume_size
+        # which launch sequence an iteration is: decided here, once (iteration() and _prime() dispatch on it)
+        self._form = f = _choose_form(
+            self.V_all, V, self.world, self.group is not None, decoder.latent_size, R, self.shape_opt,
+            self.sdf_grad_mode, form, fuse_depth_loss, merge_launches, fused_render, fc_in_tail, defer_loss, exchange,
+            getattr(decoder, "narrow_linear_stack", lambda: False))
+        self.records_form, self.fused_render, self.fc_in_tail = f.records_form, f.fused_render, f.fc_in_tail
+        self.defer_pose, self.defer_loss, self.big_exchange, self.det = f[1:]
+        # True: the depth-L1 runs inside the render kernels (sdfr_render_forward_l1 / _backward_l1) and the
+        # point-cloud L1 inside the sampler's backward (sdfr_pc_l1_backward);
+        # False: every loss is a kernel of its own between a forward and a backward.  Same results.
+        self.fuse_depth_loss = bool(fuse_depth_loss)
+        if depth_images is not None and tuple(depth_images.shape[1:]) != (H, W):
+            raise ValueError(f"depth_images must be (V, {H}, {W}) for this camera, got {tuple(depth_images.shape)}")
+        self.V, self.H, self.W, self.R = V, H, W, R
+        _loop_buffers(self, device, config, V, track_inliers)
         f32 = dict(dtype=torch.float32, device=self.dev)
         # every rank keeps the WHOLE camera list (the records form's tail chains over all views); its own shard's is a
         # view of it.  Allocated once: ``rebind`` copies a new observation's cameras in place
@@ -458,33 +552,11 @@ class FusedRenderAndCompare:
         self.cam_quat_all = torch.zeros((self.V_all, 4), **f32)
         self.cam_pos = self.cam_pos_all[self.view_begin:self.view_end]
         self.cam_quat = self.cam_quat_all[self.view_begin:self.view_end]
-        V, H, W = self.view_end - self.view_begin, int(camera.height), int(camera.width)
-        if depth_images is not None and tuple(depth_images.shape[1:]) != (H, W):
-            raise ValueError(f"depth_images must be (V, {H}, {W}) for this camera, got {tuple(depth_images.shape)}")
-        self.V, self.H, self.W = V, H, W
-        self.defer_loss = (V < 32) if self._defer_loss_arg is None else bool(self._defer_loss_arg)
-        self.defer_pose = bool(merge_launches) and V <= 64
-        # the iteration's tail -- gradient chain, point constraint, Adam and the next iteration's view poses -- in
-        # one launch (sdfr_loop_tail), the render pair in its step form: 26 -> 22 launches per iteration
-        self.merge_tail = bool(merge_launches) and V <= 64
         self.target = torch.zeros((V, H, W), **f32)
-        # The observed point clouds at CAPACITY -- room for every pixel of every view, counts and offsets on the
-        # device (sdfr_depth_to_points_resident) -- so that a new observation changes no address, no grid size and
-        # needs no host read: the captured graphs stay valid.  The sampler's grids are sized for W * H points per
-        # view; blocks beyond a view's count leave at once (sampler_device.hpp), the reducers take the real lengths
-        # from `offsets`: the same sums in the same order as with exactly-sized buffers.
-        # (compact patches: the sampler's backward pre-sums 256 consecutive points before its global atomics)
-        self.max_pts = W * H
-        self.points = torch.zeros((V * W * H, 3), **f32)
-        self.offsets = torch.zeros(V + 1, dtype=torch.int32, device=self.dev)
-        self.counts = torch.zeros(V, dtype=torch.int32, device=self.dev)
-        self.ws_points = torch.empty(max(self.L.sdfr_depth_points_workspace_bytes(V, W, H), 256), dtype=torch.uint8,
-                                     device=self.dev)
         self.Lz = decoder.latent_size
         n = 8 + self.Lz
         # the run's state in ONE buffer, [params | everything a run starts from zero]: one fill resets a run
         n4 = (n + 3) // 4 * 4
-        self.max_history = int(config["max_iterations"])
         nh = (max(self.max_history, 1) + 3) // 4 * 4
         self._state = torch.zeros(4 * n4 + nh + 8, **f32)
         self.params = self._state[0:n]
@@ -501,10 +573,7 @@ class FusedRenderAndCompare:
         self.arrivals = ints[3:4]                     # sdfr_loop_tail_fused(decoder_tape=): zero at a run's start
         self._state_zero = self._state[n4:]           # (everything but the parameters)
         self.grads = torch.zeros(n, **f32)
-        R = decoder._volume_size
-        self.R = R
         n_rec = self.V_all * VIEW_RECORD_FLOATS
-        self.big_exchange = self.records_form and self.shape_opt and exchange == "sdf"
         self.plan = BatchRenderPlan(R, V, camera, device=self.dev, sdf_grad_mode=self.sdf_grad_mode,
                                     grad_tail_words=n_rec if (self.big_exchange and not self.det) else 0)
         self.xbuf = self.records = None
@@ -523,13 +592,7 @@ class FusedRenderAndCompare:
                 if with_g:
                     self.grads = self.xbuf[n_rec:n_rec + n]
             self.owns_last = self.view_end == self.V_all
-        self.pos_c = torch.empty((V, 3), **f32)
-        self.quat_c = torch.empty((V, 4), **f32)
-        self.inv_scale = torch.empty((V,), **f32)
-        self.scale_v = torch.empty((V,), **f32)
-        # the argument runs the tail launches and the Adam step share (every buffer keeps its address for good)
-        self._view_poses = (self.pos_c.data_ptr(), self.quat_c.data_ptr(), self.inv_scale.data_ptr(),
-                            self.scale_v.data_ptr())
+        # the argument run the tail launches and the Adam step share (every buffer keeps its address for good)
         self._adam = (self.params.data_ptr(), self.grads.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
                       self.step.data_ptr(), n, *_ADAM_RATES, int(self.shape_opt))
         # (the gradient image and the per-point arrays exist only when the losses run as kernels of their own)
@@ -550,27 +613,10 @@ class FusedRenderAndCompare:
                                       self.L.sdfr_decoder_backward_workspace_bytes(decoder._h, 1), 256), **u8)
         self.ws_loss = torch.empty(max(self.L.sdfr_depth_l1_workspace_bytes(V, W, H), 256), **u8)
         self.ws_pc = torch.empty(max(self.L.sdfr_pc_loss_backward_workspace_bytes(V, self.max_pts), 256), **u8)
-        can_fuse = (self.merge_tail and not self.records_form and self.fuse_depth_loss and R <= 128 and V <= 8
-                    and self.max_pts > 0 and self.sdf_grad_mode in (0, 1) and 8 + self.Lz <= 256)
-        if fused_render and not can_fuse:
-            raise ValueError("fused_render needs the tail form over at most 8 views of a grid up to 128^3, the loss-fused "
-                             "kernels, sdf_grad_mode 0 / 1 and a parameter vector of at most 256 entries")
-        # (default: where it measured faster -- with shape optimisation up to 4 views: 1 view 0.111 -> 0.099 ms per
-        # iteration, 2: 0.112 -> 0.102, 3: 0.114 -> 0.107, 4: 0.119 -> 0.116, but 7: 0.126 -> 0.132 -- every view adds a
-        # megabyte to sum, to clear and to collide in; pose only, where no volume exists, wherever it applies)
-        auto = can_fuse and (V <= 4 or not self.shape_opt)
-        self.fused_render = auto if fused_render is None else bool(fused_render)
-        can_fc = bool(self.fused_render and self.shape_opt and getattr(decoder, "narrow_linear_stack", lambda: False)())
-        if fc_in_tail and not can_fc:
-            raise ValueError("fc_in_tail needs fused_render, shape optimisation and a decoder with a narrow Linear stack")
-        self.fc_in_tail = can_fc if fc_in_tail is None else bool(fc_in_tail)
         self._sums_open = False
         if self.fused_render:
             # what the one-launch step ADDS into must start from zero (its consumers clear what they have read)
             self._zero_fused_sums()
-        self.strategy = _selection_strategy(config)
-        self.track_inliers = (self.strategy == "best_inlier_ratio") if track_inliers is None else bool(track_inliers)
-        self.rel_thr = float(config.get("relative_inlier_threshold", 0.03))
         # the point constraint's two points live in buffers of this object (``rebind`` copies new ones in place);
         # whether there is one, and its weight, are launch ARGUMENTS and so part of a captured graph: graphs are kept
         # per (constraint present, weight) -- a caller alternating between "none" and one weight captures twice, once
@@ -580,10 +626,15 @@ class FusedRenderAndCompare:
         # (at most 4 sets: a caller whose constraint weight changes from call to call re-captures instead of
         # collecting graphs without bound)
         self._graphs = _graphs.BoundedCache(4)
-        self.graph = self.graph_many = self.graph_tail = None
+        self._captured = _LoopGraphs()
         self.bound = False
         if depth_images is not None:
             self.rebind(depth_images, camera_positions, camera_orientations, point_constraint)
+
+    # the launch sequence's name (FORMS) and the current constraint key's graphs, read-only
+    form = property(lambda self: self._form.name)
+    graph, graph_many, graph_tail, graph_whole_one, graph_whole = (
+        property(lambda self, field=field: getattr(self._captured, field)) for field in _LoopGraphs.__slots__)
 
     def rebind(self, depth_images: torch.Tensor, camera_positions: Optional[torch.Tensor] = None,
                camera_orientations: Optional[torch.Tensor] = None, point_constraint: Optional[Sequence] = None,
@@ -618,9 +669,8 @@ class FusedRenderAndCompare:
                 self.pc_source, self.pc_weight = None, 0.0
         key = None if self.pc_source is None else self.pc_weight
         # (the whole-iteration graphs of `graph_collective` carry the constraint's launch arguments too: they belong
-        # to the key like the others -- until round 6 a rebind to another constraint kept replaying the old ones)
-        (self.graph, self.graph_many, self.graph_tail, self.graph_whole_one,
-         self.graph_whole) = self._graphs.get(key, (None, None, None, None, None))
+        # to the key like the others)
+        self._captured = self._graphs.get(key) or _LoopGraphs()
         self._graph_key = key
         self.bound = True
         return self
@@ -634,8 +684,8 @@ class FusedRenderAndCompare:
         self._sums_open = False
 
     def _keep_graphs(self):
-        self._graphs[self._graph_key] = (self.graph, self.graph_many, self.graph_tail, self.graph_whole_one,
-                                         self.graph_whole)
+        """after a capture that succeeded: the key's graphs enter the cache"""
+        self._graphs[self._graph_key] = self._captured
 
     def view_point_counts(self) -> torch.Tensor:
         """observed points per view of this rank's shard, (V,) int32 on the device (reading it synchronises)"""
@@ -677,129 +727,82 @@ class FusedRenderAndCompare:
 
     def _prime(self):
         """what the FIRST iteration of a run finds where every later one finds the previous tail's results: the views'
-        poses of the initial estimate and -- ``fc_in_tail`` -- its Linear-stack output"""
+        poses of the initial estimate (every form but "separate", whose iteration computes them) and -- "fc_in_tail" --
+        its Linear-stack output"""
+        if self.form == "separate":
+            return
         st = self._stream()
         self._poses_to_views(st)
         if self.fc_in_tail:
             self._decode(st, True, stages=1)
 
-    def iteration(self):
-        """One iteration of simple_setup.py:408-462 as a launch sequence on the current stream."""
+    def _iteration_separate(self):
+        """pose chain, render pair, the sampler, the reductions, gradient chain, point constraint, decoder VJP and Adam
+        as launches of their own -- in three variants of how the losses run"""
         L, d, st = self.L, self.dev.index, self._stream()
-        p = self.params.data_ptr()
-        pos, quat, scale = p, p + 12, p + 28
-        g = self.grads.data_ptr()
+        p, g = self.params.data_ptr(), self.grads.data_ptr()
+        quat, scale = p + 12, p + 28
         if self.shape_opt:
-            self._decode(st, True, stages=2 if self.fc_in_tail else 3)
+            self._decode(st, True)
         sdf = self.sdf[0, 0]
-        if self._tail_form():
-            # [decoder] -> render pair as a step -> [decoder VJP] -> sdfr_loop_tail; the camera-frame poses of THIS
-            # iteration were left by the previous tail (or by _poses_to_views before the first one)
-            # (the depth loss values are reduced inside the backward's launch: no launch between the image kernels)
-            if self.fused_render:
-                return self._iteration_one_launch(L, d, st, p, sdf)
-            self.plan.forward_l1(sdf, self.pos_c, self.quat_c, self.inv_scale, self.cfg["threshold"], self.target,
-                                 prepare_backward=True, defer_loss=self.defer_loss)
-            self.loss_depth = self.plan.loss
-            g_sdf = self.plan.backward_l1_pc(self.target, sdf, self.pos_c, self.quat_c, self.inv_scale,
-                                             self.scale_v, self.points, self.offsets, self.max_pts, self.ws_pc,
-                                             weight=self.cfg["depth_weight"], pc_weight=self.cfg["pc_weight"])
-            t_mid = None
-            if self.shape_opt:
-                # the VJP's last launch (one workgroup) runs inside the tail's launch
-                t_mid = ctypes.c_void_p()
-                self.check(L.sdfr_decoder_backward_latent_deferred(
-                    self.dec._h, self.latent.data_ptr(), self.tape.data_ptr(), g_sdf.data_ptr(), self.ws_dec.data_ptr(),
-                    self.ws_dec.numel(), st, ctypes.byref(t_mid)), "sdfr_decoder_backward_latent_deferred")
-            self.check(L.sdfr_loop_tail(
-                *self._adam, self.cam_pos.data_ptr(), self.cam_quat.data_ptr(), self.V,
-                self.plan.workspace.data_ptr(), self.plan.partials_offset, self.W, self.H, self.ws_pc.data_ptr(),
-                self.offsets.data_ptr(), self.max_pts, *self._view_poses, self.loss_pc.data_ptr(),
-                *self._constraint_args(), self.dec._h if t_mid is not None else None, t_mid, d, st), "sdfr_loop_tail")
-            self._inliers(L, p, d, st)
-            return
         self._poses_to_views(st)
         # the renderer's and the sampler's per-view reductions run inside the gradient chain's launch
         # (sdfr_views_to_pose_grad_deferred: two launches less per iteration)
         defer = self.defer_pose
-        have_pts = self.max_pts > 0
-        summed = False   # the sampler's d/dSDF already added to the renderer's
-        if self.fuse_depth_loss and defer and have_pts:
-            # both backward passes side by side in one launch (they are independent and neither fills the chip)
-            self.plan.forward_l1(sdf, self.pos_c, self.quat_c, self.inv_scale, self.cfg["threshold"],
-                                 self.target)
+        pc_grads = (None, None, None) if defer else (self.g_pos_pc.data_ptr(), self.g_quat_pc.data_ptr(),
+                                                     self.g_scale_pc.data_ptr())
+        if self.fuse_depth_loss:
+            self.plan.forward_l1(sdf, self.pos_c, self.quat_c, self.inv_scale, self.cfg["threshold"], self.target)
             self.loss_depth = self.plan.loss
+        if self.fuse_depth_loss and defer:
+            # both backward passes side by side in one launch (they are independent and neither fills the chip)
             g_sdf = self.plan.backward_l1_pc(self.target, sdf, self.pos_c, self.quat_c, self.inv_scale,
                                              self.scale_v, self.points, self.offsets, self.max_pts, self.ws_pc,
                                              weight=self.cfg["depth_weight"], pc_weight=self.cfg["pc_weight"])
-            g_pos = g_quat = g_is = None
-            summed = True
         elif self.fuse_depth_loss:
-            self.plan.forward_l1(sdf, self.pos_c, self.quat_c, self.inv_scale, self.cfg["threshold"],
-                                 self.target)
-            self.loss_depth = self.plan.loss
-            g_sdf, g_pos, g_quat, g_is = self.plan.backward_l1(self.target, sdf, self.pos_c, self.quat_c,
-                                                               self.inv_scale,
-                                                               weight=self.cfg["depth_weight"], defer_pose=defer)
-        else:
-            est = self.plan.forward(sdf, self.pos_c, self.quat_c, self.inv_scale, self.cfg["threshold"])
-            self.check(L.sdfr_depth_l1_loss(est.data_ptr(), self.target.data_ptr(), self.V, self.W, self.H,
-                                            self.cfg["depth_weight"], self.loss_depth.data_ptr(),
-                                            self.grad_est.data_ptr(), self.ws_loss.data_ptr(),
-                                            self.ws_loss.numel(), d, st), "sdfr_depth_l1_loss")
-            g_sdf, g_pos, g_quat, g_is = self.plan.backward(self.grad_est, sdf, self.pos_c, self.quat_c,
-                                                            self.inv_scale, defer_pose=defer)
-        if summed:
-            pass
-        elif have_pts and self.fuse_depth_loss:
+            g_sdf, g_pos, g_quat, g_is = self.plan.backward_l1(self.target, sdf, self.pos_c, self.quat_c, self.inv_scale,
+                                                               weight=self.cfg["depth_weight"], defer_pose=False)
             # the point-cloud term in one pass: loss value and gradients, no sampler forward, no loss kernel;
             # its d/dSDF goes straight into the volume the renderer's backward has just written
             self.check(L.sdfr_pc_l1_backward_accumulate(
                 self.cfg["pc_weight"], self.loss_pc.data_ptr(), self.points.data_ptr(), self.offsets.data_ptr(),
                 self.V, self.max_pts, self.pos_c.data_ptr(), self.quat_c.data_ptr(), self.scale_v.data_ptr(),
-                sdf.data_ptr(), self.R, 0, g_sdf.data_ptr(), 0, None if defer else self.g_pos_pc.data_ptr(),
-                None if defer else self.g_quat_pc.data_ptr(), None if defer else self.g_scale_pc.data_ptr(),
-                self.ws_pc.data_ptr(), self.ws_pc.numel(), d, st),
-                "sdfr_pc_l1_backward_accumulate")
-            summed = True
-        elif have_pts:
-            self.check(L.sdfr_pc_loss_forward(self.points.data_ptr(), self.offsets.data_ptr(), self.V,
-                                              self.max_pts, self.pos_c.data_ptr(), self.quat_c.data_ptr(),
-                                              self.scale_v.data_ptr(), sdf.data_ptr(), self.R, 0,
-                                              self.vals.data_ptr(), d, st), "sdfr_pc_loss_forward")
+                sdf.data_ptr(), self.R, 0, g_sdf.data_ptr(), 0, *pc_grads, self.ws_pc.data_ptr(), self.ws_pc.numel(),
+                d, st), "sdfr_pc_l1_backward_accumulate")
+        else:
+            est = self.plan.forward(sdf, self.pos_c, self.quat_c, self.inv_scale, self.cfg["threshold"])
+            self.check(L.sdfr_depth_l1_loss(est.data_ptr(), self.target.data_ptr(), self.V, self.W, self.H,
+                                            self.cfg["depth_weight"], self.loss_depth.data_ptr(), self.grad_est.data_ptr(),
+                                            self.ws_loss.data_ptr(), self.ws_loss.numel(), d, st), "sdfr_depth_l1_loss")
+            g_sdf, g_pos, g_quat, g_is = self.plan.backward(self.grad_est, sdf, self.pos_c, self.quat_c,
+                                                            self.inv_scale, defer_pose=defer)
+            self.check(L.sdfr_pc_loss_forward(self.points.data_ptr(), self.offsets.data_ptr(), self.V, self.max_pts,
+                                              self.pos_c.data_ptr(), self.quat_c.data_ptr(), self.scale_v.data_ptr(),
+                                              sdf.data_ptr(), self.R, 0, self.vals.data_ptr(), d, st), "sdfr_pc_loss_forward")
             self.check(L.sdfr_pc_l1_loss(self.vals.data_ptr(), self.offsets.data_ptr(), self.V, self.max_pts,
                                          self.cfg["pc_weight"], self.loss_pc.data_ptr(),
                                          self.grad_vals.data_ptr(), d, st), "sdfr_pc_l1_loss")
-            self.check(L.sdfr_pc_loss_backward(self.grad_vals.data_ptr(), self.points.data_ptr(),
-                                               self.offsets.data_ptr(), self.V, self.max_pts,
-                                               self.pos_c.data_ptr(), self.quat_c.data_ptr(),
-                                               self.scale_v.data_ptr(), sdf.data_ptr(), self.R, 0,
-                                               self.g_sdf_pc.data_ptr(), 0,
-                                               None if defer else self.g_pos_pc.data_ptr(),
-                                               None if defer else self.g_quat_pc.data_ptr(),
-                                               None if defer else self.g_scale_pc.data_ptr(),
-                                               self.ws_pc.data_ptr(), self.ws_pc.numel(), d, st),
-                       "sdfr_pc_loss_backward")
+            self.check(L.sdfr_pc_loss_backward(
+                self.grad_vals.data_ptr(), self.points.data_ptr(), self.offsets.data_ptr(), self.V, self.max_pts,
+                self.pos_c.data_ptr(), self.quat_c.data_ptr(), self.scale_v.data_ptr(), sdf.data_ptr(), self.R, 0,
+                self.g_sdf_pc.data_ptr(), 0, *pc_grads, self.ws_pc.data_ptr(), self.ws_pc.numel(), d, st),
+                "sdfr_pc_loss_backward")
         if defer:
             self.check(L.sdfr_views_to_pose_grad_deferred(
                 quat, scale, self.cam_quat.data_ptr(), self.V, self.plan.workspace.data_ptr(), self.W, self.H,
-                self.ws_pc.data_ptr() if have_pts else None, self.offsets.data_ptr() if have_pts else None,
-                self.max_pts, self.quat_c.data_ptr(),
-                self.loss_pc.data_ptr() if (have_pts and self.fuse_depth_loss) else None,
-                g, g + 12, g + 28, d, st), "sdfr_views_to_pose_grad_deferred")
+                self.ws_pc.data_ptr(), self.offsets.data_ptr(), self.max_pts, self.quat_c.data_ptr(),
+                self.loss_pc.data_ptr() if self.fuse_depth_loss else None, g, g + 12, g + 28, d, st),
+                "sdfr_views_to_pose_grad_deferred")
         else:
             self.check(L.sdfr_views_to_pose_grad(quat, scale, self.cam_quat.data_ptr(), self.V, g_pos.data_ptr(),
-                                                 g_quat.data_ptr(), g_is.data_ptr(),
-                                                 self.g_pos_pc.data_ptr() if have_pts else None,
-                                                 self.g_quat_pc.data_ptr() if have_pts else None,
-                                                 self.g_scale_pc.data_ptr() if have_pts else None,
+                                                 g_quat.data_ptr(), g_is.data_ptr(), *pc_grads,
                                                  g, g + 12, g + 28, d, st), "sdfr_views_to_pose_grad")
         if self.pc_source is not None:   # + the point constraint's gradient on the orientation parameter
             self.check(L.sdfr_point_constraint(quat, self.pc_source.data_ptr(), self.pc_target.data_ptr(),
                                                self.pc_weight, self.loss_con.data_ptr(), g + 12, d, st),
                        "sdfr_point_constraint")
         if self.shape_opt:
-            if have_pts and not summed:
+            if not self.fuse_depth_loss:   # (the loss-fused sampler has added its d/dSDF to the renderer's already)
                 self.check(L.sdfr_add_inplace(g_sdf.data_ptr(), self.g_sdf_pc.data_ptr(), g_sdf.numel(), d, st),
                            "sdfr_add_inplace")
             self.check(L.sdfr_decoder_backward_latent(self.dec._h, self.latent.data_ptr(), self.tape.data_ptr(),
@@ -808,11 +811,45 @@ class FusedRenderAndCompare:
         self.check(L.sdfr_adam_step(*self._adam, d, st), "sdfr_adam_step")
         self._inliers(L, p, d, st)
 
-    def _iteration_one_launch(self, L, d, st, p, sdf):
-        """The tail form with the render pair as ONE launch (``fused_render``): [decoder] -> render forward + backward +
-        the sampler's blocks (``sdfr_render_step_fused_l1_pc``; the depth term's sums come out unscaled, beside the view's
-        overlap count) -> [decoder VJP on  point-cloud volume + k depth volume, which it clears afterwards] -> the tail
-        (multiplies the pose sums by k, writes the depth loss, resets the count)."""
+    def _iteration_tail(self):
+        """[decoder] -> render pair as a step -> [decoder VJP] -> sdfr_loop_tail; the camera-frame poses of THIS
+        iteration were left by the previous tail (or by _prime before the first one).  The depth loss values are reduced
+        inside the backward's launch: no launch between the image kernels."""
+        L, d, st = self.L, self.dev.index, self._stream()
+        if self.shape_opt:
+            self._decode(st, True)
+        sdf = self.sdf[0, 0]
+        self.plan.forward_l1(sdf, self.pos_c, self.quat_c, self.inv_scale, self.cfg["threshold"], self.target,
+                             prepare_backward=True, defer_loss=self.defer_loss)
+        self.loss_depth = self.plan.loss
+        g_sdf = self.plan.backward_l1_pc(self.target, sdf, self.pos_c, self.quat_c, self.inv_scale,
+                                         self.scale_v, self.points, self.offsets, self.max_pts, self.ws_pc,
+                                         weight=self.cfg["depth_weight"], pc_weight=self.cfg["pc_weight"])
+        t_mid = None
+        if self.shape_opt:
+            # the VJP's last launch (one workgroup) runs inside the tail's launch
+            t_mid = ctypes.c_void_p()
+            self.check(L.sdfr_decoder_backward_latent_deferred(
+                self.dec._h, self.latent.data_ptr(), self.tape.data_ptr(), g_sdf.data_ptr(), self.ws_dec.data_ptr(),
+                self.ws_dec.numel(), st, ctypes.byref(t_mid)), "sdfr_decoder_backward_latent_deferred")
+        self.check(L.sdfr_loop_tail(
+            *self._adam, self.cam_pos.data_ptr(), self.cam_quat.data_ptr(), self.V,
+            self.plan.workspace.data_ptr(), self.plan.partials_offset, self.W, self.H, self.ws_pc.data_ptr(),
+            self.offsets.data_ptr(), self.max_pts, *self._view_poses, self.loss_pc.data_ptr(),
+            *self._constraint_args(), self.dec._h if t_mid is not None else None, t_mid, d, st), "sdfr_loop_tail")
+        self._inliers(L, self.params.data_ptr(), d, st)
+
+    def _iteration_one_launch(self):
+        """The tail form with the render pair as ONE launch ("one_launch", "fc_in_tail"): [decoder] -> render forward +
+        backward + the sampler's blocks (``sdfr_render_step_fused_l1_pc``; the depth term's sums come out unscaled, beside
+        the view's overlap count) -> [decoder VJP on  point-cloud volume + k depth volume, which it clears afterwards] ->
+        the tail (multiplies the pose sums by k, writes the depth loss, resets the count).  With ``fc_in_tail`` the decode
+        is its stage 2 (the Linear stack's output is in the tape: the previous tail's launch, or _prime, left it there)
+        and the tail takes the tape."""
+        L, d, st = self.L, self.dev.index, self._stream()
+        if self.shape_opt:
+            self._decode(st, True, stages=2 if self.fc_in_tail else 3)
+        sdf = self.sdf[0, 0]
         plan = self.plan
         g_pc = plan._g_sdf_ring[0] if self.shape_opt else None
         self._sums_open = True     # (until the tail has been enqueued: __call__ re-zeroes after an interrupted iteration)
@@ -838,14 +875,13 @@ class FusedRenderAndCompare:
             self.tape.data_ptr() if self.fc_in_tail else None, self.arrivals.data_ptr() if self.fc_in_tail else None,
             d, st), "sdfr_loop_tail_fused")
         self._sums_open = False
-        self._inliers(L, p, d, st)
+        self._inliers(L, self.params.data_ptr(), d, st)
 
     # ---- the records form: head | exchange | tail (the loop sharded over ranks) -----------------------------------
 
     def _head(self):
         """This rank's share of simple_setup.py:408-446: the (replicated) decoder, the render / compare / sample of its
         own views with both backward passes, and its views' exchange records."""
-        from .differentiable_renderer import VIEW_RECORD_FLOATS
         L, d, st = self.L, self.dev.index, self._stream()
         if self.shape_opt:
             self._decode(st, True)
@@ -853,7 +889,6 @@ class FusedRenderAndCompare:
         self.plan.ring_reset()       # always the plan's first volume: the bucket's address is part of captured graphs
         # (views without an observed point: their sampler blocks leave at once, their point-cloud loss is the NaN of
         # torch.mean over nothing, simple_setup.py:144, and they contribute no gradient -- as in the reference)
-        have_pts = True
         self.plan.forward_l1(sdf, self.pos_c, self.quat_c, self.inv_scale, self.cfg["threshold"], self.target,
                              prepare_backward=True, defer_loss=self.defer_loss)
         g_sdf = self.plan.backward_l1_pc(self.target, sdf, self.pos_c, self.quat_c, self.inv_scale, self.scale_v,
@@ -869,8 +904,7 @@ class FusedRenderAndCompare:
             self.xbuf[:self.R ** 3].copy_(self.plan.g_sdf_fixed().view(-1))
         self.check(L.sdfr_loop_view_records(
             self.plan.workspace.data_ptr(), self.plan.partials_offset, self.W, self.H, self.sdf_grad_mode,
-            self.ws_pc.data_ptr() if have_pts else None, 1 if have_pts else 0,
-            self.offsets.data_ptr() if have_pts else None, self.max_pts, self.quat_c.data_ptr(),
+            self.ws_pc.data_ptr(), 1, self.offsets.data_ptr(), self.max_pts, self.quat_c.data_ptr(),
             self.plan.loss.data_ptr(), self.view_begin, self.V, self.V_all, self.records.data_ptr(), d, st),
             "sdfr_loop_view_records")
         if self.track_inliers and self.owns_last:
@@ -892,7 +926,6 @@ class FusedRenderAndCompare:
     def _tail(self):
         """simple_setup.py:448-462 on every rank alike: decoder VJP of the summed volume, the chain over all views'
         records, point constraint, Adam, renormalisation -- and this rank's view poses for the next iteration."""
-        from .differentiable_renderer import VIEW_RECORD_FLOATS
         L, d, st = self.L, self.dev.index, self._stream()
         p = self.params.data_ptr()
         t_mid = None
@@ -919,7 +952,6 @@ class FusedRenderAndCompare:
         """(depth loss, point-cloud loss) of every view of the last iteration, (V_all,) each -- on every rank after
         the exchange of the records form; this process's own views otherwise."""
         if self.records_form:
-            from .differentiable_renderer import VIEW_RECORD_FLOATS
             rec = self.records.view(self.V_all, VIEW_RECORD_FLOATS)
             return rec[:, 16], rec[:, 17]
         return self.loss_depth, self.loss_pc
@@ -930,12 +962,17 @@ class FusedRenderAndCompare:
         self._exchange()
         self._tail()
 
-    def _run_records(self, n_iter, use_graph, history):
-        state = (self._state,)
-        record = (lambda it: self._record_history(history)) if history is not None else None
-        if self.group is None:
-            return self._run_records_single(n_iter, use_graph, state, record)
-        if use_graph and self.graph is None:
+    _ITERATIONS = {"separate": _iteration_separate, "tail": _iteration_tail, "one_launch": _iteration_one_launch,
+                   "fc_in_tail": _iteration_one_launch, "records": _whole_iteration}
+
+    def iteration(self):
+        """One iteration of simple_setup.py:408-462 as a launch sequence on the current stream: the form's."""
+        self._ITERATIONS[self.form](self)
+
+    def _run_sharded(self, n_iter, use_graph, record):
+        """a run of the records form over a process group: the collective is issued between graphs"""
+        state, g = (self._state,), self._captured
+        if use_graph and g.one is None:
             # the warm-up: every rank takes part in the exchange.  The collective stays outside the graphs --
             # head | all-reduce | tail+head | all-reduce | ... | tail
             # (thread-local capture: the process group's watchdog thread may query events while this thread captures)
@@ -945,30 +982,30 @@ class FusedRenderAndCompare:
                 self._tail()
                 self._head()
 
-            self.graph, self.graph_tail, self.graph_many = _graphs.capture(
+            g.one, g.tail, g.many = _graphs.capture(
                 self.dev, (self._head, self._tail, tail_head), self._whole_iteration, state, **mode)
             if self.graph_collective:
                 self._capture_with_collective(state, mode)
-            self._poses_to_views(self._stream())
+            self._prime()
             self._keep_graphs()
-        if use_graph and self.graph_whole_one is not None:
+        if use_graph and g.whole_one is not None:
             # the collective is a node of the graphs: whole iterations replay, nothing is issued in between
-            return _graphs.run(n_iter, self.graph_whole_one, self.graph_whole, self.graph_iterations, None, record)
-        fused = use_graph and history is None
+            return _graphs.run(n_iter, g.whole_one, g.whole, self.graph_iterations, None, record)
+        fused = use_graph and record is None
         for it in range(n_iter):
             if not use_graph:
                 self._head()
             elif not fused or it == 0:
-                self.graph.replay()
+                g.one.replay()
             self._exchange()
             if not use_graph:
                 self._tail()
             elif fused and it + 1 < n_iter:
-                self.graph_many.replay()     # this iteration's tail and the next one's head
+                g.many.replay()     # this iteration's tail and the next one's head
             else:
-                self.graph_tail.replay()
-            if history is not None:
-                self._record_history(history)
+                g.tail.replay()
+            if record is not None:
+                record(it)
 
     def _capture_with_collective(self, state, mode):
         """the experiment of ``graph_collective``: head | all-reduce | tail as ONE captured sequence"""
@@ -977,21 +1014,11 @@ class FusedRenderAndCompare:
             if dist.get_backend(self.group) != "nccl":
                 raise RuntimeError(f"backend {dist.get_backend(self.group)!r}: only RCCL's collectives are stream work")
             # (no second warm-up: the two-graph form's has just run the same launches)
-            self.graph_whole_one, self.graph_whole = _capture_iterations(self, self._whole_iteration, state,
-                                                                         warmup=lambda: None, **mode)
+            self._captured.whole_one, self._captured.whole = _capture_iterations(
+                self, self._whole_iteration, state, warmup=lambda: None, **mode)
         except Exception as e:      # capture refused: the two-graph form stays
             torch.cuda.synchronize(self.dev)
             self.graph_collective_error = f"{type(e).__name__}: {e}"
-
-    def _run_records_single(self, n_iter, use_graph, state, record):
-        """the records form without a process group: no collective, so whole iterations are captured -- one graph per
-        iteration, and one of ``graph_iterations`` iterations, as in the tail form"""
-        if use_graph and self.graph is None:
-            self.graph, self.graph_many = _capture_iterations(self, self._whole_iteration, state)
-            self._poses_to_views(self._stream())
-            self._keep_graphs()
-        one, many = (self.graph, self.graph_many) if use_graph else (None, None)
-        _graphs.run(n_iter, one, many, self.graph_iterations, self._whole_iteration, record)
 
     def _record_history(self, history):
         ld, lp = self.view_losses()
@@ -1000,10 +1027,6 @@ class FusedRenderAndCompare:
                         "loss_depth": ld.clone(), "loss_pc": lp.clone(),
                         "position": self.position.clone()[None], "orientation": self.orientation.clone()[None],
                         "scale": self.scale.clone(), "latent": self.latent.clone()[None]})
-
-    def _tail_form(self) -> bool:
-        return (self.merge_tail and self.fuse_depth_loss and self.defer_pose and self.max_pts > 0
-                and 8 + self.Lz <= 256)
 
     def _poses_to_views(self, st):
         p = self.params.data_ptr()
@@ -1045,29 +1068,19 @@ class FusedRenderAndCompare:
         if not self.shape_opt:
             self._decode(self._stream(), False)
         n_iter = self.cfg["max_iterations"]
-        if self.records_form:
-            self._poses_to_views(self._stream())
-            self._run_records(n_iter, use_graph, history)
-            return (self.position.clone()[None], self.orientation.clone()[None], self.scale.clone(),
-                    self.latent.clone()[None])
-        if self._tail_form():
-            self._prime()   # every later iteration gets its view poses from the tail before it
-        if use_graph and self.graph is None:
-            self.graph, self.graph_many = _capture_iterations(self, self.iteration, (self._state,))
-            if self._tail_form():
+        record = (lambda it: self._record_history(history)) if history is not None else None
+        self._prime()   # every later iteration gets its view poses from the tail before it
+        if self.group is not None:
+            self._run_sharded(n_iter, use_graph, record)
+        else:
+            g = self._captured
+            if use_graph and g.one is None:
+                # (self.iteration: looked up now, so that an instance's replacement is what gets captured)
+                g.one, g.many = _capture_iterations(self, self.iteration, (self._state,))
                 self._prime()   # the warm-up's tail left the poses of ITS updated parameters
-            self._keep_graphs()
-
-        def record(it):
-            history.append({"loss": (self.cfg["depth_weight"] * self.loss_depth.sum()
-                                     + self.cfg["pc_weight"] * self.loss_pc.sum()
-                                     + self.loss_con.sum()).clone(),
-                            "position": self.position.clone()[None],
-                            "orientation": self.orientation.clone()[None],
-                            "scale": self.scale.clone(), "latent": self.latent.clone()[None]})
-
-        one, many = (self.graph, self.graph_many) if use_graph else (None, None)
-        _graphs.run(n_iter, one, many, self.graph_iterations, self.iteration, record if history is not None else None)
+                self._keep_graphs()
+            one, many = (g.one, g.many) if use_graph else (None, None)
+            _graphs.run(n_iter, one, many, self.graph_iterations, self.iteration, record)
         # "best_inlier_ratio": the reference returns the parameter tensors themselves, i.e. the last
         # iterate (_BestEstimate); the snapshot taken at the best ratio is in best_estimate()
         return (self.position.clone()[None], self.orientation.clone()[None], self.scale.clone(),
@@ -1113,12 +1126,8 @@ class MultiObjectRenderAndCompare:
     def __init__(self, decoder, camera: Camera, config: Dict, objects: int, shape_optimization: bool = True,
                  device="cuda", graph_iterations: int = 5, sdf_grad_mode: int = SDF_GRAD_EXACT, views: int = 1,
                  track_inliers: Optional[bool] = None):
-        from .differentiable_renderer import BatchRenderPlan
         self.L, self.check = _lib.lib(), _lib.check
         self.dec, self.cam, self.cfg = decoder, camera, config
-        self.dev = torch.device(device)
-        if self.dev.index is None:
-            self.dev = torch.device("cuda", torch.cuda.current_device())
         K = self.K = int(objects)
         if K < 1:
             raise ValueError("objects must be >= 1")
@@ -1133,14 +1142,15 @@ class MultiObjectRenderAndCompare:
         self.graph_iterations = max(1, int(graph_iterations))
         H, W = int(camera.height), int(camera.width)
         self.H, self.W = H, W
-        f32 = dict(dtype=torch.float32, device=self.dev)
-        i32 = dict(dtype=torch.int32, device=self.dev)
-        u8 = dict(dtype=torch.uint8, device=self.dev)
         R = self.R = decoder._volume_size
         self.Lz = decoder.latent_size
         n = self.n = 8 + self.Lz
         if n > 256:
             raise ValueError("the tail handles parameter vectors of up to 256 entries")
+        _loop_buffers(self, device, config, B, track_inliers)     # (view k V + v: object k from camera v)
+        f32 = dict(dtype=torch.float32, device=self.dev)
+        i32 = dict(dtype=torch.int32, device=self.dev)
+        u8 = dict(dtype=torch.uint8, device=self.dev)
         self.params = torch.zeros((K, n), **f32)
         self._zeroed = torch.zeros((3, K, n), **f32)          # Adam's moments and the gradients: one fill resets a run
         self.m, self.v, self.grads = self._zeroed[0], self._zeroed[1], self._zeroed[2]
@@ -1152,20 +1162,9 @@ class MultiObjectRenderAndCompare:
         self.target = torch.zeros((B, H, W), **f32)           # [K][V] images
         # (the bookkeeping reads K contiguous images: with V > 1 the objects' last views get a copy at rebind)
         self.target_last = self.target if V == 1 else torch.zeros((K, H, W), **f32)
-        self.max_pts = W * H
-        self.points = torch.zeros((B * W * H, 3), **f32)
-        self.offsets = torch.zeros(B + 1, **i32)
-        self.counts = torch.zeros(B, **i32)
-        self.ws_points = torch.empty(max(self.L.sdfr_depth_points_workspace_bytes(B, W, H), 256), **u8)
         self.sdf_grad_mode = int(sdf_grad_mode)     # SDF_GRAD_EXACT / SDF_GRAD_CUDA_COMPAT
         self.plan = BatchRenderPlan(R, B, camera, device=self.dev, per_view_sdf=True, close_views=False,
                                     sdf_grad_mode=self.sdf_grad_mode)
-        self.pos_c = torch.empty((B, 3), **f32)
-        self.quat_c = torch.empty((B, 4), **f32)
-        self.inv_scale = torch.empty((B,), **f32)
-        self.scale_v = torch.empty((B,), **f32)
-        self._view_poses = (self.pos_c.data_ptr(), self.quat_c.data_ptr(), self.inv_scale.data_ptr(),
-                            self.scale_v.data_ptr())
         self.loss_pc = torch.zeros((B,), **f32)
         self.sdf_objects = torch.empty((K, 1, R, R, R), **f32)      # what the decoder writes
         self.sdf = self.sdf_objects if V == 1 else torch.empty((B, 1, R, R, R), **f32)     # what the views read
@@ -1175,12 +1174,8 @@ class MultiObjectRenderAndCompare:
                                       self.L.sdfr_decoder_backward_workspace_bytes(decoder._h, K), 256), **u8)
         self.ws_pc = torch.empty(max(self.L.sdfr_pc_loss_backward_workspace_bytes(B, self.max_pts), 256), **u8)
         self.defer_loss = B < 32
-        self.strategy = _selection_strategy(config)
-        self.track_inliers = (self.strategy == "best_inlier_ratio") if track_inliers is None else bool(track_inliers)
-        self.rel_thr = float(config.get("relative_inlier_threshold", 0.03))
         # the bookkeeping's state in ONE buffer, [counts K x 2 (int; first: each pair 8-byte aligned, one atomic adds both)
         # | history K x max_iterations | best state K x 3 | best parameters K x n]: one fill resets a run
-        self.max_history = int(config["max_iterations"])
         mh = max(self.max_history, 1)
         self._inliers_state = torch.zeros(K * (2 + mh + 3 + n), **f32)
         self.inlier_counts = self._inliers_state[0:K * 2].view(torch.int32).view(K, 2)

@@ -85,8 +85,8 @@ def test_sharded_loop_matches_the_single_process_loop(tmp_path, scene, exchange)
 def test_records_form_multi_iteration_graph_replays(tmp_path, monkeypatch):
     """The records form's replay paths that run only WITHOUT a history (the default for 8 or more views, and the only
     form a process group can use): two ranks replaying `tail + next head` between the all-reduces
-    (``_run_records``' graph_many), and a single process replaying graphs of 3 and of 5 iterations with a remainder
-    (``_run_records_single``) -- the plan's ring_reset and volume bookkeeping inside a multi-iteration capture, the
+    (``_run_sharded``'s graph_many), and a single process replaying graphs of 3 and of 5 iterations with a remainder
+    (``__call__``'s single-process path) -- the plan's ring_reset and volume bookkeeping inside a multi-iteration capture, the
     head / tail interleaving around the collective.  Deterministic mode: final parameters, step count and inlier
     history are BITWISE the eager run's."""
     from sdfest_amd.differentiable_renderer import BWD_SMALL_TILES, SDF_GRAD_DETERMINISTIC
